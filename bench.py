@@ -1,9 +1,11 @@
 #!/usr/bin/env python3
 """bench.py — 1080p yuv420p frames/sec of the MI355X encode hot path (BASELINE.json metric).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
       N > 1 without a launcher: this script starts `python -m torch.distributed.run --nproc-per-node N` on itself (before any
       GPU call) and exits with its code; under a launcher (WORLD_SIZE set) it is one rank of N.
+      --dump-outputs DIR: the last timed step's outputs as DIR/mb_records.npy and DIR/levels.npy (see dump_outputs).
+      --full: everything below beside the headline; without it the run sets up, warms up, times the K steps and prints the line.
 
 A *step* is one lock-step pass of the hot path over one batch of synthetic input: every one of the `--streams` independent
 closed-GOP streams on this GPU advances by one CODED picture through the C ABI x264gpu_encode_pictures() of libx264gpu.so:
@@ -21,10 +23,10 @@ CABAC sizes, psy-rd 1.0), trellis 1, 8x8dct, all partitions, B pictures (spatial
 lists what still differs (weightp's fade analysis, b-adapt 1, the lookahead-driven tools).  `--bframes 0` measures the I / P stream of the earlier
 rounds, `--rd cavlc` medium --no-cabac, `--rd off` the subme-5 toolset, for comparison.
 
-Rank 0 prints ONE JSON line with `roofline` (the macroblock kernel, HIP-event timed inside the timed region, HBM fraction + VALU
-issue utilisation from the committed PMC profile), `cpu_baseline` (the oracle restatement on 1 and on all host cores, plus a
-run-time probe for a real libx264 / x264 / ffmpeg), and `e2e` (ONE stream through x264_encoder_encode: PCIe + host entropy coding
-included).
+Rank 0 prints ONE JSON line: the headline (`value`, `ms_per_step`, `config`); with --full also `roofline` (the macroblock kernel,
+HIP-event timed inside the timed region, HBM fraction + VALU issue utilisation from the committed PMC profile), `cpu_baseline` (the
+oracle restatement on 1 and on all host cores, plus a run-time probe for a real libx264 / x264 / ffmpeg), and `e2e` (ONE stream
+through x264_encoder_encode: PCIe + host entropy coding included).
 """
 import argparse
 import ctypes as C
@@ -40,7 +42,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0   # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
-TOOLSET_GAPS = "x264 medium with a fixed picture structure and constant quantisers: the lock-step batch codes the same picture type in every stream, so the lookahead's DECISIONS (b-adapt 1, scenecut, fade weights, AQ / mbtree / rate control) are not taken — its device work for the same streams is timed beside `value` (`lookahead`: lowres, AQ offsets, frame costs, macroblock-tree; `value_with_lookahead`); --weightp 2's duplicate reference with offset -1 on every P picture IS in; entropy coding (CABAC bitstream writing) runs on host threads and is outside `value` (inside `e2e`)"
+TOOLSET_GAPS = "x264 medium with a fixed picture structure and constant quantisers: the lock-step batch codes the same picture type in every stream, so the lookahead's DECISIONS (b-adapt 1, scenecut, fade weights, AQ / mbtree / rate control) are not taken — its device work for the same streams is timed beside `value` under --full (`lookahead`: lowres, AQ offsets, frame costs, macroblock-tree; `value_with_lookahead`); --weightp 2's duplicate reference with offset -1 on every P picture IS in; entropy coding (CABAC bitstream writing) runs on host threads and is outside `value` (inside `e2e`)"
 TOOLSET_GAPS_NOB = "x264 medium minus: B-frames (bframes 3 -> 0), the fade analysis of weightp 2; entropy coding (CABAC/CAVLC bitstream writing) runs on host threads and is outside `value` (inside `e2e`)"
 TOOLSET_GAPS_NORD = "x264 medium minus: RD mode decision + psy-rd (subme 7 -> 5), trellis 1, the lookahead's decisions (b-adapt 1, fade weights, rate control); entropy coding runs on host threads and is outside `value`"
 
@@ -86,6 +88,10 @@ def parse_args():
                     "white noise + strong sensor noise, harder than camera material; 'smooth' = the same scene with band-limited textures and light noise; "
                     "'survey' = SURVEY.md §8(d) read with natural textures: gradient + 3 moving band-limited rectangles + noise of +-4 on luma, +-2 on chroma")
     ap.add_argument("--survey-leg", type=int, default=1, help="1 (default): time the same job on --content survey too and report it as value_survey_content in the same line; 0 = skip")
+    ap.add_argument("--full", action="store_true", help="also run every leg beside the headline: the survey-content pass, the roofline, the BGRA ingest probe, the lookahead, "
+                    "the CPU baseline, the end-to-end legs and the decoder probe (each still subject to its own option above); off: the headline pass alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the last step's outputs (macroblock records and levels, float32) "
+                    "as DIR/<name>.npy; a fixed sample of streams when the whole batch exceeds DUMP_BYTES")
     ap.add_argument("--cpu-worker", type=int, default=-1, help=argparse.SUPPRESS)
     return ap.parse_args()
 
@@ -299,6 +305,29 @@ def loaded_product_libraries():
     except OSError:
         pass
     return found
+
+
+DUMP_BYTES = 60 << 20       # --dump-outputs: at most this many bytes of float32 in all
+
+
+def dump_outputs(torch, dirname, mbs, lvs, seed=0x264):
+    """--dump-outputs: what x264gpu_encode_pictures handed its caller in the last timed step — per stream the macroblock records (the 64 bytes of
+    struct x264gpu_mb, include/x264gpu.h) and the levels (X264GPU_MB_LEVELS int16 per macroblock), as float32 [streams, macroblocks, 64 | 416].
+    The records are written byte for byte, as the caller receives them: bytes 28..43 are the list-0 vectors (little-endian int16 pairs), 44..47 nnz,
+    and 48..63 hold the list-1 vectors in the inter macroblocks of B slices but the analysis costs (cost, aux: diagnostics) elsewhere, so two builds
+    that code alike can still differ there.  Every stream when the batch fits in DUMP_BYTES, else a fixed sample of whole streams (seeded: the same
+    streams for the same arguments); when one stream alone exceeds it, that stream's leading macroblocks.  Returns (streams, macroblocks per stream)."""
+    import numpy as np
+    S, n = mbs.shape[0], mbs.shape[1]
+    per_mb = (mbs.shape[2] + lvs.shape[2]) * 4
+    m = min(n, DUMP_BYTES // per_mb)
+    k = max(1, min(S, DUMP_BYTES // (m * per_mb)))
+    idx = np.arange(S) if k == S else np.sort(np.random.default_rng(seed).choice(S, k, replace=False))
+    sel = torch.from_numpy(idx).to(mbs.device)
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "mb_records.npy"), mbs.index_select(0, sel)[:, :m].cpu().numpy().astype(np.float32))
+    np.save(os.path.join(dirname, "levels.npy"), lvs.index_select(0, sel)[:, :m].cpu().numpy().astype(np.float32))
+    return [int(i) for i in idx], m
 
 
 def csp_probe(torch, lib, dev, W, H, frames=64, iters=10):
@@ -671,7 +700,7 @@ def main():
     for var in ("X264GPU_LIB", "X264GPU_HOST_LIB"):
         if os.environ.get(var):
             raise SystemExit(f"bench.py: {var} is set ({os.environ[var]}): the benchmark measures x264vfw_amd/libx264gpu.so and libx264gpu_host.so only; unset it")
-    cpu = cpu_baseline(args) if (rank == 0 and world == 1 and args.cpu_frames > 0) else None      # before the GPU is touched (child processes)
+    cpu = cpu_baseline(args) if (args.full and rank == 0 and world == 1 and args.cpu_frames > 0) else None      # before the GPU is touched (child processes)
 
     import torch
     from x264vfw_amd import shard
@@ -708,8 +737,9 @@ def main():
         if dist is not None:
             dist.barrier()
 
-    def timed_pass(content, keep_last=False):
-        """Wu untimed + K timed pictures of S lock-step streams on synthetic `content`, inputs resident in HBM before the clock starts."""
+    def timed_pass(content, keep_last=False, dump=None):
+        """Wu untimed + K timed pictures of S lock-step streams on synthetic `content`, inputs resident in HBM before the clock starts.
+        dump: directory for the last timed step's outputs (rank 0)."""
         base = synth_batch(torch, D, L, W, H, shard.stream_seed(0x264, gids[0]), dev, smooth=content != "noise", scene_len=97, luma_noise=4 if content == "survey" else None)
         data = base if D == S else base.repeat(1, (S + D - 1) // D, 1)[:, :S].contiguous()
         del base
@@ -757,6 +787,9 @@ def main():
         if rank == 0 and keep_last:
             import numpy as np
             res["mbt"] = np.bincount(mbs[:min(S, 64)].cpu().numpy()[:, :, 0].reshape(-1), minlength=11)
+        if rank == 0 and dump:
+            kept, m = dump_outputs(torch, dump, mbs, lvs)
+            print(f"bench.py: the last timed step's outputs of {len(kept)} of {S} streams ({m} of {n} macroblocks each) written to {dump}", file=sys.stderr, flush=True)
         lib.x264gpu_encoder_destroy(h)
         del mbs, lvs
         torch.cuda.empty_cache()
@@ -764,16 +797,12 @@ def main():
 
     # the same job on SURVEY.md 8(d)'s generator first (reported as value_survey_content beside the headline), then the headline's own content
     survey = None
-    if args.survey_leg and args.content != "survey":
+    if args.full and args.survey_leg and args.content != "survey":
         survey, sdata = timed_pass("survey")
         del sdata
         torch.cuda.empty_cache()
-    main_res, data = timed_pass(args.content, keep_last=True)
+    main_res, data = timed_pass(args.content, keep_last=args.full, dump=args.dump_outputs)
     dt, fps, step_ms, names, ms, cnt, nst = (main_res[k_] for k_ in ("dt", "fps", "step_ms", "names", "ms", "cnt", "nst"))
-    # ---- roofline of the dominant kernel: the macroblock loop (k_mb_slice) ----
-    Sb = 1.5 * W * H
-    # algorithmic HBM bytes per frame and stage (DESIGN.md "kernels"): planes each stage must read / write once.  The macroblock loop reads the
-    # source and one reference per list it predicts from and writes the reconstruction it keeps (I 2 S, P 3 S, B reference 4 S, b 3 S)
     tname = {0: "I", 1: "I", 2: "P", 3: "Bref", 4: "b"}
     kind = {0: "I", 1: "I", 2: "P", 3: "B", 4: "B"}
     tcount = {"I": 0, "P": 0, "Bref": 0, "b": 0}
@@ -781,31 +810,6 @@ def main():
     for c in range(K):
         tcount[tname[order[Wu + c][1]]] += 1
         tms[tname[order[Wu + c][1]]] += step_ms[c]
-    alg_mb = (2 * tcount["I"] + 3 * tcount["P"] + 4 * tcount["Bref"] + 3 * tcount["b"]) * Sb / K
-    alg = {"ingest": 2 * Sb, "macroblocks": alg_mb, "unused": 0, "settle_qp": 0, "deblock": 2 * Sb, "hpel_filter": 4.5 * W * H}
-    dom = max(range(nst), key=lambda i: ms[i])
-    avg_ms = ms[dom] / max(cnt[dom], 1)
-    achieved = alg[names[dom]] * S / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
-    traffic, valu, pmc_src = pmc_evidence("k_mb_slice" if names[dom] == "macroblocks" else names[dom], avg_ms, S, args.content)
-    if args.rd != "cabac" or args.no_trellis:
-        traffic, valu, pmc_src = None, None, None                            # the committed counters are the headline kernel's (RD with CABAC sizes)
-    per_type = {t: round(tms[t] / tcount[t], 2) for t in tms if tcount[t]}
-    # the same per-type step times in the proportions of a --keyint GOP (1 I, then runs of bframes B pictures closed by P pictures)
-    blended = None
-    if all(t in per_type for t in (("I", "P", "Bref", "b") if args.bframes > 1 else ("I", "P", "b") if args.bframes else ("I", "P"))):
-        gt = display_types(args.keyint, args.bframes, args.keyint)
-        go = gop.schedule(gt, 1)
-        tot = sum(per_type[tname[pt]] for _, pt in go)
-        blended = round(S * world * len(go) / (tot * 1e-3), 2)
-    roof = {"bound": "hbm", "binding_resource": "instruction issue of a raster-serial macroblock loop (neither HBM nor MFMA binds this integer path; the HBM fraction is reported because the contract asks for one of the two)", "kernel": "k_mb_slice (macroblock loop)" if names[dom] == "macroblocks" else names[dom], "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-            "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic, "valu": valu,
-            # traffic and valu.insts_* are the committed rocprofv3 --pmc passes' figures (counters cannot be read inside an un-profiled run), scaled to this
-            # run's streams; valu_issue_frac = those wave-level VALU instructions / (1024 SIMDs x 2.4 GHz / 4 cycles an instruction) / THIS run's kernel time
-            "traffic_from": pmc_src if traffic is not None else None, "valu_from": pmc_src if valu else None,
-            "valu_issue_frac": valu["issue_util"] if valu else None,
-            "note": "two wavefronts per SIMD (256 VGPRs, 20 KB of LDS each); each waits 0.42 - 0.46 of its cycles (LDS / L2 round trips of a raster-serial loop), VALU issue 0.42 - 0.48 of the SIMDs' peak: profiles/r06_pmc_per_launch.json, DESIGN.md 5",
-            "avg_launch_ms": round(avg_ms, 4), "step_ms_by_picture_type": per_type, "frames_per_s_in_keyint_proportions": blended,
-            "stage_ms_per_step": {names[i]: round(ms[i] / K, 4) for i in range(nst) if names[i] != "unused"}}
     mix = " + ".join(f"{tcount[t]} {t}" for t in ("I", "P", "Bref", "b") if tcount[t])
     out = {"metric": "1080p yuv420p frames/sec at preset=medium as the device runs it (see config.toolset_gaps), hot path on MI355X",
            "value": round(fps, 2), "unit": "frames/s", "n_gpus": world, "steps": K, "warmup": Wu,
@@ -817,19 +821,49 @@ def main():
                       "streams_per_gpu": S, "distinct_sequences": D, "frames_per_sequence": L, "content": args.content, "frames_per_step": S * world, "keyint_for_proportions": args.keyint,
                       "mb_per_frame": ((W + 15) // 16) * ((H + 15) // 16),
                       # launches of the three macroblock-loop instantiations before / inside the timed window (tools/profile_summarise.py folds the counters of the timed ones)
-                      "launch_plan": {t: {"warmup": sum(1 for _, pt in order[:Wu] if kind[pt] == t), "timed": sum(1 for _, pt in order[Wu:] if kind[pt] == t)} for t in ("I", "P", "B")}},
-           "roofline": roof}
+                      "launch_plan": {t: {"warmup": sum(1 for _, pt in order[:Wu] if kind[pt] == t), "timed": sum(1 for _, pt in order[Wu:] if kind[pt] == t)} for t in ("I", "P", "B")}}}
+    if args.full:
+        # ---- roofline of the dominant kernel: the macroblock loop (k_mb_slice); its stage times come from the events the timed pass arms in every run ----
+        Sb = 1.5 * W * H
+        # algorithmic HBM bytes per frame and stage (DESIGN.md "kernels"): planes each stage must read / write once.  The macroblock loop reads the
+        # source and one reference per list it predicts from and writes the reconstruction it keeps (I 2 S, P 3 S, B reference 4 S, b 3 S)
+        alg_mb = (2 * tcount["I"] + 3 * tcount["P"] + 4 * tcount["Bref"] + 3 * tcount["b"]) * Sb / K
+        alg = {"ingest": 2 * Sb, "macroblocks": alg_mb, "unused": 0, "settle_qp": 0, "deblock": 2 * Sb, "hpel_filter": 4.5 * W * H}
+        dom = max(range(nst), key=lambda i: ms[i])
+        avg_ms = ms[dom] / max(cnt[dom], 1)
+        achieved = alg[names[dom]] * S / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
+        traffic, valu, pmc_src = pmc_evidence("k_mb_slice" if names[dom] == "macroblocks" else names[dom], avg_ms, S, args.content)
+        if args.rd != "cabac" or args.no_trellis:
+            traffic, valu, pmc_src = None, None, None                            # the committed counters are the headline kernel's (RD with CABAC sizes)
+        per_type = {t: round(tms[t] / tcount[t], 2) for t in tms if tcount[t]}
+        # the same per-type step times in the proportions of a --keyint GOP (1 I, then runs of bframes B pictures closed by P pictures)
+        blended = None
+        if all(t in per_type for t in (("I", "P", "Bref", "b") if args.bframes > 1 else ("I", "P", "b") if args.bframes else ("I", "P"))):
+            gt = display_types(args.keyint, args.bframes, args.keyint)
+            go = gop.schedule(gt, 1)
+            tot = sum(per_type[tname[pt]] for _, pt in go)
+            blended = round(S * world * len(go) / (tot * 1e-3), 2)
+        out["roofline"] = {"bound": "hbm", "binding_resource": "instruction issue of a raster-serial macroblock loop (neither HBM nor MFMA binds this integer path; the HBM fraction is reported because the contract asks for one of the two)", "kernel": "k_mb_slice (macroblock loop)" if names[dom] == "macroblocks" else names[dom], "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                           "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic, "valu": valu,
+                           # traffic and valu.insts_* are the committed rocprofv3 --pmc passes' figures (counters cannot be read inside an un-profiled run), scaled to this
+                           # run's streams; valu_issue_frac = those wave-level VALU instructions / (1024 SIMDs x 2.4 GHz / 4 cycles an instruction) / THIS run's kernel time
+                           "traffic_from": pmc_src if traffic is not None else None, "valu_from": pmc_src if valu else None,
+                           "valu_issue_frac": valu["issue_util"] if valu else None,
+                           "note": "two wavefronts per SIMD (256 VGPRs, 20 KB of LDS each); each waits 0.42 - 0.46 of its cycles (LDS / L2 round trips of a raster-serial loop), VALU issue 0.42 - 0.48 of the SIMDs' peak: profiles/r06_pmc_per_launch.json, DESIGN.md 5",
+                           "avg_launch_ms": round(avg_ms, 4), "step_ms_by_picture_type": per_type, "frames_per_s_in_keyint_proportions": blended,
+                           "stage_ms_per_step": {names[i]: round(ms[i] / K, 4) for i in range(nst) if names[i] != "unused"}}
     if survey is not None:
         out["value_survey_content"] = round(survey["fps"], 2)
         out["ms_per_step_survey_content"] = round(survey["dt"] / K * 1e3, 4)
     if rank == 0:
-        mbt = main_res["mbt"]
-        tot = float(mbt.sum())
-        out["config"]["mb_type_share_last_step"] = {k: round(int(v) / tot, 4) for k, v in (("I4x4", mbt[0]), ("I8x8", mbt[1]), ("I16x16", mbt[2]), ("P16x16/16x8/8x16", mbt[4]),
-                                                                                          ("P8x8", mbt[5]), ("P_Skip", mbt[6]), ("B_Direct", mbt[7]), ("B_Skip", mbt[8]), ("B L0/L1/Bi", mbt[9]), ("B_8x8", mbt[10]))}
-        out["csp_ingest"] = csp_probe(torch, lib, dev, W, H)
+        if args.full:
+            mbt = main_res["mbt"]
+            tot = float(mbt.sum())
+            out["config"]["mb_type_share_last_step"] = {k: round(int(v) / tot, 4) for k, v in (("I4x4", mbt[0]), ("I8x8", mbt[1]), ("I16x16", mbt[2]), ("P16x16/16x8/8x16", mbt[4]),
+                                                                                              ("P8x8", mbt[5]), ("P_Skip", mbt[6]), ("B_Direct", mbt[7]), ("B_Skip", mbt[8]), ("B L0/L1/Bi", mbt[9]), ("B_8x8", mbt[10]))}
+            out["csp_ingest"] = csp_probe(torch, lib, dev, W, H)
         out["config"]["product_libraries"] = loaded_product_libraries()
-    if args.lookahead and args.bframes:
+    if args.full and args.lookahead and args.bframes:
         # ---- the lookahead's device work for the same streams and pictures, beside the headline ----
         la_dt, la_calls = lookahead_probe(torch, lib, dev, args, data, Wu, K, S, W, H)
         la_dt = shard.max_over_ranks(la_dt, dist, dev)
@@ -842,9 +876,9 @@ def main():
     if rank == 0:
         if cpu is not None:
             out["cpu_baseline"] = cpu
-        if world == 1 and args.e2e_frames > 0:
+        if args.full and world == 1 and args.e2e_frames > 0:
             out["e2e"] = e2e_probe(args)
-        if world == 1:
+        if args.full and world == 1:
             # a decoder nobody here wrote, if the box has one (tools/decoder_probe.py): the only independent check the entropy tables and the
             # normative reconstruction can get while no libx264 exists to pin the oracle
             sys.path.insert(0, os.path.join(ROOT, "tools"))

@@ -94,6 +94,45 @@ def test_bench_refuses_a_library_override():
         assert r.returncode != 0 and var.encode() in r.stderr, (var, r.returncode, r.stderr[-300:])
 
 
+def test_bench_plain_run_is_the_headline_alone(monkeypatch):
+    """bench.py without options times the headline pass only: --full (the other legs) is off and nothing is dumped"""
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "7", "--warmup", "3"])
+    args = bench.parse_args()
+    assert (args.full, args.dump_outputs, args.steps, args.warmup) == (False, None, 7, 3)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    args = bench.parse_args()
+    assert (args.full, args.dump_outputs) == (True, "out")
+
+
+def test_bench_dump_outputs_are_float32_within_the_budget(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the macroblock records and levels of the last step as float32 .npy files; the whole batch when it fits in
+    DUMP_BYTES, else a sample of whole streams that is the same from call to call and stays within DUMP_BYTES, and when one stream alone
+    exceeds it, that stream's leading macroblocks"""
+    import numpy as np
+    import torch
+    import bench
+    S, n = 24, 30
+    g = torch.Generator().manual_seed(5)
+    mbs = torch.randint(0, 256, (S, n, 64), generator=g, dtype=torch.uint8)
+    lvs = torch.randint(-2000, 2000, (S, n, 416), generator=g, dtype=torch.int16)
+    kept, m = bench.dump_outputs(torch, str(tmp_path / "all"), mbs, lvs)
+    assert kept == list(range(S)) and m == n
+    rec, lev = np.load(tmp_path / "all" / "mb_records.npy"), np.load(tmp_path / "all" / "levels.npy")
+    assert rec.dtype == lev.dtype == np.float32
+    assert np.array_equal(rec, mbs.numpy()) and np.array_equal(lev, lvs.numpy())
+    per_mb = (64 + 416) * 4
+    for budget, streams, mbs_each in ((5 * n * per_mb + n * per_mb // 2, 5, n), (7 * per_mb + per_mb // 2, 1, 7)):
+        monkeypatch.setattr(bench, "DUMP_BYTES", budget)
+        kept, m = bench.dump_outputs(torch, str(tmp_path / "a"), mbs, lvs)
+        assert len(kept) == streams and m == mbs_each and kept == sorted(set(kept))
+        assert (kept, m) == bench.dump_outputs(torch, str(tmp_path / "b"), mbs, lvs)
+        for d in ("a", "b"):
+            rec, lev = np.load(tmp_path / d / "mb_records.npy"), np.load(tmp_path / d / "levels.npy")
+            assert rec.nbytes + lev.nbytes <= budget
+            assert np.array_equal(rec, mbs.numpy()[kept, :m]) and np.array_equal(lev, lvs.numpy()[kept, :m])
+
+
 def test_decoder_probe_reports_what_it_finds_without_a_gpu():
     """tools/decoder_probe.py: with no third-party decoder CLI on the box the probe says so and claims nothing (no encode, no GPU needed); the keys bench.py prints are there"""
     import os

@@ -10,7 +10,7 @@ libraries that are present without a CLI to drive them (librocdecode.so, libva.s
 
     python tools/decoder_probe.py            # prints the probe's JSON (needs a GPU for the encode)
 
-Used by bench.py (`decoder_probe` in the bench line) and tests/test_gpu_host.py::test_third_party_decoder_agrees (skips when nothing is found)."""
+Used by bench.py --full (`decoder_probe` in its line) and tests/test_gpu_host.py::test_third_party_decoder_agrees (skips when nothing is found)."""
 import ctypes as C
 import glob
 import json

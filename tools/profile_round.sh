@@ -2,6 +2,7 @@
 # Collect the per-round rocprofv3 evidence on the GPU box (run through gpurun from the repo root):
 #   bash tools/profile_round.sh r01 [extra bench.py flags]
 # pass 1: --kernel-trace --stats of the default bench workload (average launch duration per kernel)
+# --full keeps the roofline (the figure the kernel trace is checked against) and the ingest probe in every pass; the other legs are off
 # pass 2/3: FETCH_SIZE and WRITE_SIZE in separate --pmc passes (they cannot share one, MI355X_MICROARCH.md)
 # pass 4: SQ issue counters of the pipeline kernels
 # Raw output goes to /tmp (it exceeds the gpurun_out size cap); only the summaries are copied back.
@@ -12,8 +13,8 @@ out=$root/gpurun_out/prof_$tag
 mkdir -p "$out"
 export TMPDIR=/tmp
 cd /tmp
-K="--cpu-frames 0 --e2e-frames 0 --lookahead 0 --survey-leg 0"
-P="--cpu-frames 0 --e2e-frames 0 --lookahead 0 --survey-leg 0"
+K="--full --cpu-frames 0 --e2e-frames 0 --lookahead 0 --survey-leg 0"
+P="--full --cpu-frames 0 --e2e-frames 0 --lookahead 0 --survey-leg 0"
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_kt -- python3 $root/bench.py $K "$@" > $out/bench_under_rocprof.json 2> /tmp/p_kt.err
 cp $(ls /tmp/p_kt/*/*kernel_stats.csv | head -1) $out/kernel_stats_full.csv
 rocprofv3 --pmc FETCH_SIZE --kernel-include-regex "x264gpu" --output-format csv -d /tmp/p_rd -- python3 $root/bench.py $P "$@" > /tmp/p_rd.log 2>&1
