@@ -55,7 +55,7 @@ public:
         log2_max_frame_num = log2_max_fn;
         refs.clear(); frame_num = 0; last_idr = 0;
     }
-    // extra_slots / avoid: a session with several pictures in flight (host/encoder.cpp: Inflight) owns more slots than the DPB holds pictures and keeps the
+    // extra_slots / avoid: a session with several pictures in flight (host/encoder.cpp: inflight_issue) owns more slots than the DPB holds pictures and keeps the
     // slots its pictures in flight write or read out of the choice of a destination
     int extra_slots = 0; unsigned avoid = 0;
     int slots() const { return max_dpb + 1 + extra_slots; }

@@ -21,6 +21,8 @@
 #include <mutex>
 #include <condition_variable>
 
+#include <functional>
+
 using namespace x264host;
 
 struct x264_t {
@@ -171,9 +173,12 @@ struct x264_t {
     //      encoder or a view of it: own scratch, the shared DPB) on a stream of its own, behind the events of the pictures it references, into a slot no picture in
     //      flight reads or writes; pictures are planned, issued and handed back in coding order, so the stream is the serial session's byte for byte ----
     struct LaunchCtx { x264gpu_encoder *gpu = nullptr; void *stream = nullptr, *ev = nullptr; x264gpu_mb *d_mb = nullptr; int16_t *d_lv = nullptr; bool busy = false; };
-    struct Inflight { BPlanned pl; x264gpu_pic pic; SliceParams sp; int ctx = 0, nal_ref_idc = 0; unsigned slots_used = 0; char direct_char = '-'; };
+    // a picture of a session on the DPB model between plan and finish: what was decided for it, what the device is told, what the slice writer is told;
+    // with several pictures in flight also its launch context and the DPB slots it reads or writes
+    struct PicPlan { BPlanned pl; x264gpu_pic pic; SliceParams sp; int nal_ref_idc = 0; double qpf = 0; const float *d_offsets = nullptr; bool direct_auto_write = false; char direct_char = '-';
+                     int ctx = 0; unsigned slots_used = 0; };
     void *ev_la = nullptr;               // the default stream's position when a picture is issued: its upload, offsets and lowres vectors are complete behind it
-    std::vector<LaunchCtx> lctx; std::deque<Inflight> fl; int inflight = 1; int slot_writer[8] = { -1, -1, -1, -1, -1, -1, -1, -1 }; int last_retired_slot = -1;
+    std::vector<LaunchCtx> lctx; std::deque<PicPlan> fl; int inflight = 1; int slot_writer[8] = { -1, -1, -1, -1, -1, -1, -1, -1 }; int last_retired_slot = -1;
     std::deque<BEntry> bq;
     std::deque<BPlanned> bcoding;
     std::vector<int64_t> all_pts;        // every pts seen, in display order (the dts delay line)
@@ -568,7 +573,6 @@ static PpsParams make_pps(const x264_t *h)
     pp.weighted_pred = h->weightp > 0;
     return pp;
 }
-// appends SPS, PPS (and optionally the version SEI) to h->out, recording NAL offsets and types
 // access unit delimiter (--aud, 7.3.2.4, Table 7-5): primary_pic_type 0 = I slices only, 1 = I and P, 2 = I, P and B (what x264 writes for its three
 // slice types); first NAL of the access unit (long start code)
 static void write_aud(std::vector<uint8_t> &out, int pic_type /* 0 I, 1 P, 2 B */, bool annexb)
@@ -579,40 +583,82 @@ static void write_aud(std::vector<uint8_t> &out, int pic_type /* 0 I, 1 P, 2 B *
     append_nal(out, 0, 9, bw.bytes(), annexb, true);
 }
 
-static void emit_sets(x264_t *h, std::vector<int> &types, bool sei)
+// appends SPS, PPS (and optionally the version SEI) to `bytes`, recording NAL offsets and types
+static void write_sets(const x264_t *h, std::vector<uint8_t> &bytes, std::vector<size_t> &off, std::vector<int> &types, bool sei)
 {
     const bool annexb = h->param.b_annexb != 0;
-    h->nal_off.push_back(h->out.size()); types.push_back(7);
-    write_sps(h->out, make_sps(h), annexb);
-    h->nal_off.push_back(h->out.size()); types.push_back(8);
-    write_pps(h->out, make_pps(h), annexb);
+    off.push_back(bytes.size()); types.push_back(7);
+    write_sps(bytes, make_sps(h), annexb);
+    off.push_back(bytes.size()); types.push_back(8);
+    write_pps(bytes, make_pps(h), annexb);
     if (sei) {
-        h->nal_off.push_back(h->out.size()); types.push_back(6);
-        write_sei_version(h->out, kSeiText, annexb);
+        off.push_back(bytes.size()); types.push_back(6);
+        write_sei_version(bytes, kSeiText, annexb);
     }
+}
+
+// ---- the steps every session mode takes for a coded picture ----
+// what opens the access unit of a picture of type PIC_*: the delimiter under --aud, and in front of an IDR picture (b_repeat_headers) the parameter sets, with the
+// version SEI when the caller says so (sessions that write into h->out: until it has been sent once; GOP slots: in the stream's first GOP).  true: the sets were written
+static bool begin_access_unit(const x264_t *h, std::vector<uint8_t> &bytes, std::vector<size_t> &off, std::vector<int> &types, int pic_type, bool sei)
+{
+    const x264_param_t &p = h->param;
+    if (p.b_aud) { off.push_back(bytes.size()); types.push_back(9); write_aud(bytes, pic_type <= PIC_I ? 0 : pic_type == PIC_P ? 1 : 2, p.b_annexb != 0); }
+    if (pic_type != PIC_IDR || !p.b_repeat_headers) return false;
+    write_sets(h, bytes, off, types, sei);
+    return true;
+}
+// the slices of the picture behind what the access unit holds so far, their NAL units tagged 5 (IDR) or 1
+static void write_slices(std::vector<uint8_t> &bytes, std::vector<size_t> &off, std::vector<int> &types, const SliceParams &sp, int slices, const x264gpu_mb *mbs, const int16_t *levels,
+                         bool annexb, bool idr, SliceStats *stats, int threads, const x264gpu_level_index *index = nullptr)
+{
+    const size_t before = off.size();
+    write_picture(bytes, &off, sp, slices, mbs, levels, annexb, before == 0, stats, threads, index);
+    for (size_t i = before; i < off.size(); i++) types.push_back(idr ? 5 : 1);
+}
+// the session-constant half of a picture's SliceParams; the caller adds what differs per picture (qp, slice_type, frame_num, idr*, nal_ref_idc, num_ref — or Dpb::fill)
+static SliceParams slice_params_base(const x264_t *h)
+{
+    const x264_param_t &p = h->param;
+    SliceParams sp = {};
+    sp.mbw = h->mbw; sp.mbh = h->mbh; sp.pic_init_qp = h->pic_init_qp; sp.log2_max_frame_num = h->log2_max_frame_num; sp.log2_max_poc_lsb = h->log2_max_poc_lsb;
+    sp.pps_id = p.i_sps_id; sp.num_ref_default = p.i_frame_reference; sp.num_ref1_default = 1;
+    sp.disable_deblock_idc = p.b_deblocking_filter ? 0 : 1; sp.alpha_off_div2 = p.i_deblocking_filter_alphac0; sp.beta_off_div2 = p.i_deblocking_filter_beta;
+    sp.transform8x8_mode = p.analyse.b_transform_8x8; sp.cabac = p.b_cabac; sp.slices_plain = h->slices_plain;
+    return sp;
+}
+static int x264_type_of(int pic_type)
+{
+    return pic_type == PIC_IDR ? X264_TYPE_IDR : pic_type == PIC_I ? X264_TYPE_I : pic_type == PIC_P ? X264_TYPE_P : pic_type == PIC_BREF ? X264_TYPE_BREF : X264_TYPE_B;
+}
+// x264's dts of the k-th coded picture: the pts of display picture k - delay; the first `delay` ones are shifted back by the delay's duration
+static int64_t coded_dts(const x264_t *h, long k)
+{
+    const long delay = !h->bframes ? 0 : h->bpyramid ? 2 : 1;
+    const size_t np = h->all_pts.size();
+    if (k >= delay) return h->all_pts[(size_t)(k - delay) < np ? (size_t)(k - delay) : np - 1];
+    return h->all_pts[(size_t)k < np ? (size_t)k : np - 1] - (h->all_pts[(size_t)delay < np ? (size_t)delay : np - 1] - h->all_pts[0]);
+}
+static void fill_pic_out(x264_picture_t *pic_out, int i_type, bool keyframe, int64_t pts, int64_t dts, const x264_image_t *img)
+{
+    if (!pic_out) return;
+    x264_picture_init(pic_out);
+    pic_out->i_type = i_type; pic_out->b_keyframe = keyframe;
+    pic_out->i_pts = pts; pic_out->i_dts = dts;
+    if (img) pic_out->img = *img;
 }
 
 extern "C" {
 static bool p2_load(x264_t *h, const char *path);
 static bool p2_init(x264_t *h);
 
-x264_t *x264_encoder_open(x264_param_t *param)
-{
-    if (!param) return nullptr;
-    if (param->i_width < 16 || param->i_height < 16 || (param->i_width & 1) || (param->i_height & 1)) {
-        xlog(param, X264_LOG_ERROR, "invalid width x height (%dx%d)\n", param->i_width, param->i_height);
-        return nullptr;
-    }
-    if ((param->i_csp & X264_CSP_MASK) != X264_CSP_I420) { xlog(param, X264_LOG_ERROR, "only i420 input is supported\n"); return nullptr; }
-    if (x264gpu_device_count() < 1) { xlog(param, X264_LOG_ERROR, "no MI355X device visible (there is no CPU fallback)\n"); return nullptr; }
-    x264_t *h = new x264_t();
-    h->param = *param;
-    x264_param_t &p = h->param;
-    if (p.rc.psz_stat_in) { h->stat_in = p.rc.psz_stat_in; p.rc.psz_stat_in = &h->stat_in[0]; }     // codec.c:1386 stack buffers
-    if (p.rc.psz_stat_out) { h->stat_out = p.rc.psz_stat_out; p.rc.psz_stat_out = &h->stat_out[0]; }
-    h->mbw = (p.i_width + 15) / 16; h->mbh = (p.i_height + 15) / 16; h->nmb = h->mbw * h->mbh;
-    if (!p.i_timebase_num || !p.i_timebase_den) { p.i_timebase_num = p.i_fps_den; p.i_timebase_den = p.i_fps_num; }
+// ---- x264_encoder_open, step by step (each step logs what it changes or why it fails; a failed step leaves the teardown to x264_encoder_close) ----
+static int psy_rd_q8(const x264_param_t &p) { return p.analyse.i_subpel_refine >= 6 ? (int)(p.analyse.f_psy_rd * 256.0f + 0.5f) : 0; }      // h->mb.i_psy_rd
 
+// the toolset: what this pipeline implements of the analysis options, slices and threads (reported back via x264_encoder_parameters)
+static void open_toolset(x264_t *h)
+{
+    x264_param_t &p = h->param;
     // ---- effective parameters: what this round's pipeline implements (reported back via encoder_parameters) ----
     // B pictures: on the device in CABAC sessions, one GOP in flight (settled below, once those are known)
     p.i_bframe = clampi(p.i_bframe, 0, 16);
@@ -653,10 +699,9 @@ x264_t *x264_encoder_open(x264_param_t *param)
     p.analyse.b_psy = p.analyse.b_psy != 0;
     if (!p.analyse.b_psy) { p.analyse.f_psy_rd = 0; p.analyse.f_psy_trellis = 0; }       // x264 validate_parameters
     p.analyse.f_psy_rd = p.analyse.f_psy_rd < 0 ? 0 : p.analyse.f_psy_rd > 10 ? 10 : p.analyse.f_psy_rd;
-    const int psy_rd_q8 = p.analyse.i_subpel_refine >= 6 ? (int)(p.analyse.f_psy_rd * 256.0f + 0.5f) : 0;      // h->mb.i_psy_rd
     // psy RD raises luma quality at chroma's cost, so x264 lowers the chroma quantiser offset to compensate (encoder.c, validate / mb init)
     int eff_chroma_qp_offset = p.analyse.i_chroma_qp_offset;
-    if (psy_rd_q8) eff_chroma_qp_offset -= p.analyse.f_psy_rd < 0.25f ? 1 : 2;
+    if (psy_rd_q8(p)) eff_chroma_qp_offset -= p.analyse.f_psy_rd < 0.25f ? 1 : 2;
     eff_chroma_qp_offset = clampi(eff_chroma_qp_offset, -12, 12);
     p.analyse.i_chroma_qp_offset = eff_chroma_qp_offset;          // x264 changes the parameter in place too: the PPS carries it
     p.analyse.b_fast_pskip = p.analyse.b_fast_pskip != 0;
@@ -689,6 +734,12 @@ x264_t *x264_encoder_open(x264_param_t *param)
         h->slices = p.i_slice_count; h->slices_plain = h->slices > 1;
     } else if (!p.b_sliced_threads) p.i_slice_count = 0;
     p.i_threads = clampi(p.i_threads, 1, 256);                 // --threads G: GOPs coded in lock-step (1 = no delay)
+}
+
+// picture structure: B pictures, --weightp, and whether the session runs on the DPB model or in a batch
+static void open_modes(x264_t *h)
+{
+    x264_param_t &p = h->param;
     if (p.i_bframe) {
         // (below --subme 7 x264 analyses B slices without RD: k_mb_b.inc's NORD flow; from 7 up their RD decisions count CABAC sizes or CAVLC bits)
         // (--threads G: closed GOPs in lock-step carry B pictures when every GOP has the same picture structure and quantisers: constant quantiser)
@@ -736,6 +787,12 @@ x264_t *x264_encoder_open(x264_param_t *param)
     if (h->dpbmode && !h->bframes) { p.rc.b_mb_tree = 0; }
     if (h->weightp) xlog(&p, X264_LOG_INFO, "weightp %d: weights for fades from the lookahead (luma, and the chroma planes beside it)%s\n", h->weightp, h->weightp == X264_WEIGHTP_SMART ? ", duplicates of reference 0 on every P picture" : "");
     h->keyint = p.i_keyint_max;
+}
+
+// rate control: which method the session really runs (passes of a 2-pass encode, zones, AQ, macroblock-tree), the quantisers, profile and level, the DPB model
+static void open_quantisers(x264_t *h)
+{
+    x264_param_t &p = h->param;
     // rate control: constant QP (X264_RC_CQP, codec.c:1498-1502) and single-pass CRF without AQ / mbtree (codec.c:1504-1507, the
     // driver's default session) when one GOP is in flight; ABR and CRF under --threads > 1 map to their nominal quantiser
     int qp = p.rc.i_rc_method == X264_RC_CQP ? p.rc.i_qp_constant : p.rc.i_rc_method == X264_RC_CRF ? (int)(p.rc.f_rf_constant + 0.5f) : 26;
@@ -806,6 +863,12 @@ x264_t *x264_encoder_open(x264_param_t *param)
         p.i_level_idc = h->level_idc;
     }
 
+}
+
+// what the device encoder(s) are created with; settles the GOP-slot count, --mvrange and the pictures in flight on the way
+static x264gpu_config open_device_config(x264_t *h)
+{
+    x264_param_t &p = h->param;
     x264gpu_config cfg = {};
     // GOP-parallel factor: bounded by the device ring (keyint x G pictures) staying under 24 GB
     h->G = p.i_threads;
@@ -819,8 +882,8 @@ x264_t *x264_encoder_open(x264_param_t *param)
     cfg.width = p.i_width; cfg.height = p.i_height; cfg.streams = h->G; cfg.refs = p.i_frame_reference; cfg.slices = h->slices; cfg.slices_plain = h->slices_plain; cfg.cabac = p.b_cabac;
     cfg.qp_i = h->qp_i; cfg.qp_p = h->qp_p; cfg.me_range = p.analyse.i_me_range; cfg.subme = p.analyse.i_subpel_refine;
     cfg.deblock = p.b_deblocking_filter; cfg.deblock_alpha = p.i_deblocking_filter_alphac0; cfg.deblock_beta = p.i_deblocking_filter_beta;
-    cfg.chroma_qp_offset = eff_chroma_qp_offset;
-    cfg.rd = p.analyse.i_subpel_refine >= 8 ? 63 : p.analyse.i_subpel_refine >= 6; cfg.psy_rd_q8 = psy_rd_q8;      // 63: RD + every refinement site (x264's i_mbrd 2)
+    cfg.chroma_qp_offset = p.analyse.i_chroma_qp_offset;
+    cfg.rd = p.analyse.i_subpel_refine >= 8 ? 63 : p.analyse.i_subpel_refine >= 6; cfg.psy_rd_q8 = psy_rd_q8(p);      // 63: RD + every refinement site (x264's i_mbrd 2)
     if (p.analyse.i_subpel_refine >= 9 && p.b_deblocking_filter) cfg.rd |= 64;          // h->mb.b_deblock_rdo: whole-macroblock RD costs measured after the loop filter
     cfg.trellis = p.analyse.i_trellis == 2 ? 63 + 64 : p.analyse.i_trellis ? 63 : 0;         // every quantiser call of the final encode; + 64: of the analysis too
     cfg.psy = cfg.rd && p.analyse.b_psy;           // x264: the chroma lambda offset table follows b_psy, whatever the psy-rd strength
@@ -854,7 +917,15 @@ x264_t *x264_encoder_open(x264_param_t *param)
         if (extra >= 1) { h->inflight = extra + 1; h->dpb.extra_slots = extra; }
     }
     if (h->dpbmode) { cfg.dpb = h->dpb.max_dpb + h->dpb.extra_slots; cfg.weightb = p.analyse.b_weighted_bipred; }
-    size_t insz = (size_t)p.i_width * p.i_height * 3 / 2;
+    return cfg;
+}
+
+// the device side: the staging buffer, then the GOP slots' encoders and rings per device, or a seat in a batch group, or the session's own encoder with its launch contexts
+static bool open_device(x264_t *h)
+{
+    x264_param_t &p = h->param;
+    x264gpu_config cfg = open_device_config(h);
+    const size_t insz = (size_t)p.i_width * p.i_height * 3 / 2;
     (void)x264gpu_get_device(&h->device);
     bool ok_setup = x264gpu_malloc((void **)&h->d_in, insz) == X264GPU_OK;
     if (ok_setup && h->G > 1) {
@@ -875,7 +946,7 @@ x264_t *x264_encoder_open(x264_param_t *param)
         }
         const std::string err = ok_setup ? "" : x264gpu_last_error();
         (void)x264gpu_set_device(h->device);
-        if (!ok_setup) { xlog(&p, X264_LOG_ERROR, "GPU encoder setup failed: %s\n", err.c_str()); x264_encoder_close(h); return nullptr; }
+        if (!ok_setup) { xlog(&p, X264_LOG_ERROR, "GPU encoder setup failed: %s\n", err.c_str()); return false; }
         if (D > 1) xlog(&p, X264_LOG_INFO, "GOP slots on %d devices (%d + ... per device)\n", D, h->devs[0].nsl);
     } else if (ok_setup && h->batch_n) {
         h->batch = batch_join(cfg, h->batch_n, insz, (size_t)h->nmb, &h->batch_idx);
@@ -902,15 +973,21 @@ x264_t *x264_encoder_open(x264_param_t *param)
     }
     if (!ok_setup) {
         xlog(&p, X264_LOG_ERROR, "GPU encoder setup failed: %s\n", x264gpu_last_error());
-        x264_encoder_close(h);
-        return nullptr;
+        return false;
     }
+    return true;
+}
+
+// lookahead and slice-type objects, how many pictures are held back, the queue's device ring
+static bool open_lookahead(x264_t *h)
+{
+    x264_param_t &p = h->param;
+    const size_t insz = (size_t)p.i_width * p.i_height * 3 / 2;
     if ((p.i_scenecut_threshold > 0 && !h->dpbmode) || h->crf || h->abr || h->aq_mode >= 2) {       // (sessions on the DPB model take scene cuts from x264's own analysis below)
         if (x264gpu_lookahead_create(&h->la, p.i_width, p.i_height, 1, p.analyse.i_me_range, p.analyse.i_subpel_refine) != X264GPU_OK ||
             x264gpu_malloc((void **)&h->d_la, 4 * sizeof(int32_t)) != X264GPU_OK) {
             xlog(&p, X264_LOG_ERROR, "GPU lookahead setup failed: %s\n", x264gpu_last_error());
-            x264_encoder_close(h);
-            return nullptr;
+            return false;
         }
     }
     // lookahead queue: rc-lookahead pictures are held back when the macroblock-tree is on (x264's sync lookahead), none otherwise
@@ -945,13 +1022,12 @@ x264_t *x264_encoder_open(x264_param_t *param)
         if (x264gpu_slicetype_create(&h->st, p.i_width, p.i_height, 1, h->Q, h->bframes, p.analyse.i_me_method, p.analyse.i_subpel_refine, p.analyse.i_me_range,
                                      p.analyse.b_weighted_bipred, p.analyse.i_mv_range, h->mbtree ? 1 : 0) != X264GPU_OK) {
             xlog(&p, X264_LOG_ERROR, "GPU lookahead setup failed: %s\n", x264gpu_last_error());
-            x264_encoder_close(h);
-            return nullptr;
+            return false;
         }
         p.i_bframe_bias = clampi(p.i_bframe_bias, -90, 100);
         (void)x264gpu_slicetype_set_bframe_bias(h->st, p.i_bframe_bias);          // --b-bias also scales the B costs of slicetype_frame_cost
     }
-    h->aq_strength = cfg.aq_mode ? cfg.aq_strength : h->aq_mode >= 2 ? p.rc.f_aq_strength : 0.f;      // (modes 2 / 3: the plain strength, x264_adaptive_quant_frame scales it by the picture's mean itself)
+    h->aq_strength = h->aq_mode == X264_AQ_VARIANCE ? p.rc.f_aq_strength * 1.0397f : h->aq_mode >= 2 ? p.rc.f_aq_strength : 0.f;      // (modes 2 / 3: the plain strength, x264_adaptive_quant_frame scales it by the picture's mean itself)
     h->st_aq_costs = h->st && h->la && !h->mbtree && h->aq_strength != 0.f && (h->crf || h->abr);
     h->tree_strength = 5.0f * (1.0f - p.rc.f_qcompress);
     h->q_raw.assign((size_t)h->Q, nullptr); h->q_info.assign((size_t)h->Q, nullptr); h->q_aq.assign((size_t)h->Q, nullptr); h->q_tree.assign((size_t)h->Q, nullptr);
@@ -975,10 +1051,16 @@ x264_t *x264_encoder_open(x264_param_t *param)
         if (ok && h->mbtree) ok = x264gpu_malloc((void **)&h->d_tree, (size_t)h->nmb * sizeof(float)) == X264GPU_OK;
         if (!ok) {
             xlog(&p, X264_LOG_ERROR, "GPU lookahead queue setup failed: %s\n", x264gpu_last_error());
-            x264_encoder_close(h);
-            return nullptr;
+            return false;
         }
     }
+    return true;
+}
+
+// single-pass rate control state, the second pass' plan, the statistics file
+static bool open_ratecontrol(x264_t *h)
+{
+    x264_param_t &p = h->param;
     if (h->crf || h->abr) {
         // x264_ratecontrol_new: rate_factor_constant = base_cplx^(1 - qcomp) / qp2qscale(crf), base_cplx = mbs * (bframes ? 120 : 80)
         auto qp2qscale = [](double q) { return rc_qp2qscale(q); };
@@ -1006,7 +1088,7 @@ x264_t *x264_encoder_open(x264_param_t *param)
     }
     h->rc.fps = p.i_fps_num ? (double)p.i_fps_num / p.i_fps_den : 25.0;
     if (h->pass2) {
-        if (!p2_load(h, p.rc.psz_stat_in) || !p2_init(h)) { x264_encoder_close(h); return nullptr; }
+        if (!p2_load(h, p.rc.psz_stat_in) || !p2_init(h)) return false;
         xlog(&p, X264_LOG_INFO, "2-pass: %d pictures planned from the first pass' statistics, %.1f kbit expected before the last one\n", (int)h->p2.size(), h->p2_final_bits / 1000.0);
     }
     // (the driver's N-th pass asks for both: statistics read AND written again — codec.c:1519-1541 with its fixed updatestats — so that a further pass plans from this one's pictures)
@@ -1014,11 +1096,19 @@ x264_t *x264_encoder_open(x264_param_t *param)
     if (h->pass1 || stat_update) {
         // x264 writes <stats>.temp and renames it when the encoder closes; the first line names the options the second pass must agree with
         h->stat_file = fopen((std::string(p.rc.psz_stat_out) + ".temp").c_str(), "wb");
-        if (!h->stat_file) { xlog(&p, X264_LOG_ERROR, "ratecontrol_init: can't open stats file\n"); x264_encoder_close(h); return nullptr; }
+        if (!h->stat_file) { xlog(&p, X264_LOG_ERROR, "ratecontrol_init: can't open stats file\n"); return false; }
         fprintf(h->stat_file, "#options: %dx%d fps=%u/%u timebase=%u/%u bitdepth=8 cabac=%d ref=%d bframes=%d b_pyramid=%d b_adapt=%d weightp=%d keyint=%d rc=%s\n", p.i_width, p.i_height,
                 p.i_fps_num, p.i_fps_den, p.i_fps_den, p.i_fps_num, p.b_cabac, p.i_frame_reference, p.i_bframe, p.i_bframe_pyramid, p.i_bframe_adaptive, p.analyse.i_weighted_pred, p.i_keyint_max,
                 p.rc.i_rc_method == X264_RC_ABR ? "abr" : p.rc.i_rc_method == X264_RC_CRF ? "crf" : "cqp");
     }
+    return true;
+}
+
+// host buffers and the GOP slots' bookkeeping
+static void open_host_buffers(x264_t *h)
+{
+    x264_param_t &p = h->param;
+    const size_t insz = (size_t)p.i_width * p.i_height * 3 / 2;
     { const unsigned hw = std::thread::hardware_concurrency(); h->cavlc_threads = h->G > 1 ? 1 : cavlc_threads_default(hw >= 32 ? 16 : hw >= 16 ? 8 : hw >= 4 ? (int)hw / 2 : 1); }
     h->h_in.resize(insz);
     // (a batch session whose pictures are downloaded and coded by its helper threads keeps the records in the two deferred slots instead: 7 MB less to clear per open)
@@ -1037,6 +1127,30 @@ x264_t *x264_encoder_open(x264_param_t *param)
             xlog(&p, X264_LOG_INFO, "%d GOP slots in lock-step with B pictures (bframes %d, b-pyramid %d, constant quantiser): pictures leave in coding order, %d calls late\n", h->G, h->bframes, h->bpyramid, (h->G - 1) * h->keyint + h->bframes + 1);
         }
     }
+}
+
+x264_t *x264_encoder_open(x264_param_t *param)
+{
+    if (!param) return nullptr;
+    if (param->i_width < 16 || param->i_height < 16 || (param->i_width & 1) || (param->i_height & 1)) {
+        xlog(param, X264_LOG_ERROR, "invalid width x height (%dx%d)\n", param->i_width, param->i_height);
+        return nullptr;
+    }
+    if ((param->i_csp & X264_CSP_MASK) != X264_CSP_I420) { xlog(param, X264_LOG_ERROR, "only i420 input is supported\n"); return nullptr; }
+    if (x264gpu_device_count() < 1) { xlog(param, X264_LOG_ERROR, "no MI355X device visible (there is no CPU fallback)\n"); return nullptr; }
+    x264_t *h = new x264_t();
+    h->param = *param;
+    x264_param_t &p = h->param;
+    if (p.rc.psz_stat_in) { h->stat_in = p.rc.psz_stat_in; p.rc.psz_stat_in = &h->stat_in[0]; }     // codec.c:1386 stack buffers
+    if (p.rc.psz_stat_out) { h->stat_out = p.rc.psz_stat_out; p.rc.psz_stat_out = &h->stat_out[0]; }
+    h->mbw = (p.i_width + 15) / 16; h->mbh = (p.i_height + 15) / 16; h->nmb = h->mbw * h->mbh;
+    if (!p.i_timebase_num || !p.i_timebase_den) { p.i_timebase_num = p.i_fps_den; p.i_timebase_den = p.i_fps_num; }
+
+    open_toolset(h);
+    open_modes(h);
+    open_quantisers(h);
+    if (!open_device(h) || !open_lookahead(h) || !open_ratecontrol(h)) { x264_encoder_close(h); return nullptr; }
+    open_host_buffers(h);
     xlog(&p, X264_LOG_INFO, "MI355X hot path: %dx%d, %d MBs, CQP I:%d P:%d, keyint %d, level %d\n", p.i_width, p.i_height, h->nmb,
          h->qp_i, h->qp_p, h->keyint, h->level_idc);
     return h;
@@ -1071,7 +1185,7 @@ int x264_encoder_headers(x264_t *h, x264_nal_t **pp_nal, int *pi_nal)
     if (!h || !pp_nal || !pi_nal) return -1;
     h->out.clear(); h->nal_off.clear();
     std::vector<int> types;
-    emit_sets(h, types, true);               // nal[0]=SPS nal[1]=PPS nal[2]=SEI (output/raw.c:41-47)
+    write_sets(h, h->out, h->nal_off, types, true);               // nal[0]=SPS nal[1]=PPS nal[2]=SEI (output/raw.c:41-47)
     publish_nals(h, pp_nal, pi_nal, types);
     return (int)h->out.size();
 }
@@ -1094,6 +1208,65 @@ static void join_pool(x264_t *h)
 
 static int rc_pick_qp(x264_t *h, bool is_i, const int32_t costs[4], int frames_done, int frame);
 
+// One coding position of the slots [slot0, slot0 + nslots) on the devices: launch(dc, d) issues device d's encode call for its slots (false: it failed), the
+// records and levels of those slots then land in the download buffers not in use — on the caller's thread when there is one device, else on a host thread per
+// device (the error text is per thread: the first per device is kept).  The CAVLC pool of the position before is joined, it read the other pair.
+// owners_only: devices that own none of the slots sit the position out (GOP slots with B pictures; the I / P mode launches every device).
+// 0 and the buffers the position landed in, or -1 after a GPU failure (the session is then dead: h->failed)
+static int run_devices(x264_t *h, int slot0, int nslots, bool owners_only, const std::function<bool(x264_t::DevCtx &, int)> &launch, x264gpu_mb **hmb_out, int16_t **hlv_out)
+{
+    x264gpu_mb *hmb = h->dl ? h->h_mb2.data() : h->h_mb.data();
+    int16_t *hlv = h->dl ? h->h_lv2.data() : h->h_lv.data();
+    h->dl ^= 1;
+    const int D = (int)h->devs.size();
+    std::vector<std::string> errs((size_t)D);
+    auto run_dev = [&](int d) {
+        x264_t::DevCtx &dc = h->devs[(size_t)d];
+        bool mine = !owners_only;
+        for (int s = slot0; s < slot0 + nslots; s++) mine |= s % D == d;
+        if (!mine) return;                                     // (the stream's last, shorter GOP is coded alone: only its device runs)
+        const bool ok = (D == 1 || x264gpu_set_device(dc.dev) == X264GPU_OK) && launch(dc, d) &&
+                        x264gpu_memcpy_d2h(hmb + (size_t)dc.base * h->nmb, dc.d_mb, (size_t)dc.nsl * h->nmb * sizeof(x264gpu_mb), nullptr) == X264GPU_OK &&
+                        x264gpu_memcpy_d2h(hlv + (size_t)dc.base * h->nmb * X264GPU_MB_LEVELS, dc.d_lv, (size_t)dc.nsl * h->nmb * X264GPU_MB_LEVELS * sizeof(int16_t), nullptr) == X264GPU_OK;
+        if (!ok) errs[(size_t)d] = std::string("device ") + std::to_string(dc.dev) + ": " + x264gpu_last_error();
+    };
+    if (D == 1) run_dev(0);
+    else {
+        std::vector<std::thread> ths;
+        for (int d = 0; d < D; d++) ths.emplace_back(run_dev, d);
+        for (auto &th : ths) th.join();
+    }
+    join_pool(h);
+    for (int d = 0; d < D; d++)
+        if (!errs[(size_t)d].empty()) {
+            xlog(&h->param, X264_LOG_ERROR, "x264_encoder_encode: GPU hot path failed: %s\n", errs[(size_t)d].c_str());
+            h->failed = true;
+            return -1;
+        }
+    *hmb_out = hmb; *hlv_out = hlv;
+    return 0;
+}
+
+// starts the CAVLC pool over the slots [slot0, slot0 + nslots) of position `pos`: work(s) writes slot s' access unit; the threads overlap the GPU work of the next position
+static void start_pool(x264_t *h, int pos, int slot0, int nslots, const std::function<void(int)> &work)
+{
+    const unsigned hw = std::thread::hardware_concurrency();
+    const int nthr = (int)(hw ? (hw < (unsigned)nslots ? hw : (unsigned)nslots) : 1);
+    h->pool_t = pos; h->pool_nslots = nslots; h->pool_slot0 = slot0;
+    for (int th = 0; th < nthr; th++)
+        h->pool.emplace_back([work, th, nthr, slot0, nslots]() { for (int s = slot0 + th; s < slot0 + nslots; s += nthr) work(s); });
+}
+
+// the access unit of GOP `gop`'s picture in `cd` (a pool thread): AUD, the sets in front of an IDR picture (the SEI in the stream's first GOP only), the slices
+static void write_coded(const x264_t *h, x264_t::Coded &cd, int pic_type, long gop, SliceParams sp, const x264gpu_mb *mb, const int16_t *lv)
+{
+    cd.bytes.clear(); cd.off.clear(); cd.types.clear();
+    cd.idr = pic_type == PIC_IDR;
+    begin_access_unit(h, cd.bytes, cd.off, cd.types, pic_type, gop == 0);
+    sp.idr_pic_id = (int)(gop & 0xffff);
+    write_slices(cd.bytes, cd.off, cd.types, sp, h->slices, mb, lv, h->param.b_annexb != 0, cd.idr, nullptr, 1);
+}
+
 // GOP slots with B pictures: coding position c of `order` for the slots [slot0, slot0 + nslots) of batch `batch` — the plan from the DPB model (the
 // same for every slot), one x264gpu_encode_pictures per device that owns one of the slots, the slices written by the pool while the next position runs.
 // 0, or -1 after a GPU failure (the session is then dead, as in code_position).
@@ -1102,9 +1275,6 @@ static int code_position_b(x264_t *h, int batch, int c, int slot0, int nslots, c
     const x264_param_t &p = h->param;
     const size_t insz = (size_t)p.i_width * p.i_height * 3 / 2;
     const int G = h->G, K = h->keyint, disp = order[(size_t)c].first, type = order[(size_t)c].second;
-    x264gpu_mb *hmb = h->dl ? h->h_mb2.data() : h->h_mb.data();
-    int16_t *hlv = h->dl ? h->h_lv2.data() : h->h_lv.data();
-    h->dl ^= 1;
     // the disposable pictures coded right behind this one (x264_reference_hierarchy_reset looks at them)
     int fc[16], ff[16], nf = 0;
     for (size_t i = (size_t)c + 1; i < order.size() && nf < 16 && order[i].second == PIC_B; i++) { fc[nf] = (int)i; ff[nf] = order[i].first; nf++; }
@@ -1125,69 +1295,26 @@ static int code_position_b(x264_t *h, int batch, int c, int slot0, int nslots, c
     if (!h->zones.empty())
         for (int s = slot0; s < slot0 + nslots; s++)
             if (const x264_t::Zone *z = get_zone(h, (int)(((long)batch * G + s) * K + disp))) qps[(size_t)s] = cqp_zone(h, *z, q_type);
-    SliceParams sp = {};
-    sp.mbw = h->mbw; sp.mbh = h->mbh; sp.pic_init_qp = h->pic_init_qp; sp.log2_max_frame_num = h->log2_max_frame_num; sp.log2_max_poc_lsb = h->log2_max_poc_lsb;
-    sp.pps_id = p.i_sps_id; sp.num_ref_default = p.i_frame_reference; sp.num_ref1_default = 1;
-    sp.disable_deblock_idc = p.b_deblocking_filter ? 0 : 1; sp.alpha_off_div2 = p.i_deblocking_filter_alphac0; sp.beta_off_div2 = p.i_deblocking_filter_beta;
-    sp.transform8x8_mode = p.analyse.b_transform_8x8; sp.cabac = p.b_cabac; sp.slices_plain = h->slices_plain;
+    SliceParams sp = slice_params_base(h);
     gd.dpb.fill(sp);
     gd.dpb.commit();
     const int D = (int)h->devs.size();
-    std::vector<std::string> errs((size_t)D);
-    auto run_dev = [&](int d) {
-        x264_t::DevCtx &dc = h->devs[(size_t)d];
-        bool mine = false;
-        for (int s = slot0; s < slot0 + nslots; s++) mine |= s % D == d;
-        if (!mine) return;                                     // (the stream's last, shorter GOP is coded alone: only its device runs)
-        bool ok = D == 1 || x264gpu_set_device(dc.dev) == X264GPU_OK;
+    x264gpu_mb *hmb; int16_t *hlv;
+    auto launch = [&](x264_t::DevCtx &dc, int d) {
         std::vector<x264gpu_pic> pics((size_t)dc.nsl, pic);
         for (int l = 0; l < dc.nsl; l++) pics[(size_t)l].qp = qps[(size_t)(l * D + d)];
-        ok = ok && x264gpu_encode_pictures(dc.gpu, dc.d_ring + (size_t)disp * dc.nsl * insz, pics.data(), dc.d_mb, dc.d_lv, nullptr) == X264GPU_OK &&
-             x264gpu_memcpy_d2h(hmb + (size_t)dc.base * h->nmb, dc.d_mb, (size_t)dc.nsl * h->nmb * sizeof(x264gpu_mb), nullptr) == X264GPU_OK &&
-             x264gpu_memcpy_d2h(hlv + (size_t)dc.base * h->nmb * X264GPU_MB_LEVELS, dc.d_lv, (size_t)dc.nsl * h->nmb * X264GPU_MB_LEVELS * sizeof(int16_t), nullptr) == X264GPU_OK;
-        if (!ok) errs[(size_t)d] = std::string("device ") + std::to_string(dc.dev) + ": " + x264gpu_last_error();
+        return x264gpu_encode_pictures(dc.gpu, dc.d_ring + (size_t)disp * dc.nsl * insz, pics.data(), dc.d_mb, dc.d_lv, nullptr) == X264GPU_OK;
     };
-    if (D == 1) run_dev(0);
-    else {
-        std::vector<std::thread> ths;
-        for (int d = 0; d < D; d++) ths.emplace_back(run_dev, d);
-        for (auto &th : ths) th.join();
-    }
-    for (int d = 0; d < D; d++)
-        if (!errs[(size_t)d].empty()) {
-            xlog(&p, X264_LOG_ERROR, "x264_encoder_encode: GPU hot path failed: %s\n", errs[(size_t)d].c_str());
-            join_pool(h); h->failed = true;
-            return -1;
-        }
-    join_pool(h);
+    if (run_devices(h, slot0, nslots, true, launch, &hmb, &hlv) < 0) return -1;
     const int ref_idc = plan.nal_ref_idc;
-    auto work = [h, batch, c, disp, type, hmb, hlv, qps, D, sp, ref_idc](int s) {
-        const x264_param_t &p = h->param;
-        const int G = h->G;
+    start_pool(h, c, slot0, nslots, [h, batch, c, disp, type, hmb, hlv, qps, D, sp, ref_idc](int s) {
         const size_t row = (size_t)h->devs[(size_t)(s % D)].base + (size_t)(s / D);
         x264_t::Coded &cd = h->slotbuf[(size_t)s * h->keyint + c];
-        cd.bytes.clear(); cd.off.clear(); cd.types.clear();
-        cd.idr = type == PIC_IDR; cd.ref_idc = ref_idc; cd.disp = disp;
-        cd.i_type = type == PIC_IDR ? X264_TYPE_IDR : type == PIC_I ? X264_TYPE_I : type == PIC_P ? X264_TYPE_P : type == PIC_BREF ? X264_TYPE_BREF : X264_TYPE_B;
-        const long gop = (long)batch * G + s;
-        const bool annexb = p.b_annexb != 0;
-        if (p.b_aud) { cd.off.push_back(cd.bytes.size()); cd.types.push_back(9); write_aud(cd.bytes, type <= PIC_I ? 0 : type == PIC_P ? 1 : 2, annexb); }
-        if (cd.idr && p.b_repeat_headers) {
-            cd.off.push_back(cd.bytes.size()); cd.types.push_back(7); write_sps(cd.bytes, make_sps(h), annexb);
-            cd.off.push_back(cd.bytes.size()); cd.types.push_back(8); write_pps(cd.bytes, make_pps(h), annexb);
-            if (gop == 0) { cd.off.push_back(cd.bytes.size()); cd.types.push_back(6); write_sei_version(cd.bytes, kSeiText, annexb); }
-        }
+        cd.ref_idc = ref_idc; cd.disp = disp; cd.i_type = x264_type_of(type);
         SliceParams sps = sp;
-        sps.qp = qps[(size_t)s]; sps.idr_pic_id = (int)(gop & 0xffff);
-        const size_t before = cd.off.size();
-        write_picture(cd.bytes, &cd.off, sps, h->slices, hmb + row * h->nmb, hlv + row * h->nmb * X264GPU_MB_LEVELS, annexb, before == 0, nullptr);
-        for (size_t i = before; i < cd.off.size(); i++) cd.types.push_back(cd.idr ? 5 : 1);
-    };
-    const unsigned hw = std::thread::hardware_concurrency();
-    const int nthr = (int)(hw ? (hw < (unsigned)nslots ? hw : (unsigned)nslots) : 1);
-    h->pool_t = c; h->pool_nslots = nslots; h->pool_slot0 = slot0;
-    for (int th = 0; th < nthr; th++)
-        h->pool.emplace_back([work, th, nthr, slot0, nslots]() { for (int s = slot0 + th; s < slot0 + nslots; s += nthr) work(s); });
+        sps.qp = qps[(size_t)s];
+        write_coded(h, cd, type, (long)batch * h->G + s, sps, hmb + row * h->nmb, hlv + row * h->nmb * X264GPU_MB_LEVELS);
+    });
     return 0;
 }
 
@@ -1198,11 +1325,6 @@ static int code_position(x264_t *h, int batch, int t, int nslots_with_t)
     const x264_param_t &p = h->param;
     const size_t insz = (size_t)p.i_width * p.i_height * 3 / 2;
     const int st = t == 0 ? X264GPU_SLICE_I : X264GPU_SLICE_P, G = h->G;
-    // GPU + download of this position run while the CAVLC threads of the previous position are still coding from the
-    // other buffer pair
-    x264gpu_mb *hmb = h->dl ? h->h_mb2.data() : h->h_mb.data();
-    int16_t *hlv = h->dl ? h->h_lv2.data() : h->h_lv.data();
-    h->dl ^= 1;
     std::vector<int8_t> qps; std::vector<float> qpms;
     if (h->crf) {
         qps.assign((size_t)G, (int8_t)(t == 0 ? h->qp_i : h->qp_p)); qpms.assign((size_t)G, 0.f);
@@ -1213,70 +1335,28 @@ static int code_position(x264_t *h, int batch, int t, int nslots_with_t)
         for (int s = 0; s < nslots_with_t; s++)
             if (const x264_t::Zone *z = get_zone(h, (int)(((long)batch * G + s) * h->keyint + t))) qps[(size_t)s] = (int8_t)cqp_zone(h, *z, qps[(size_t)s]);
     }
-    // every device codes position t of its slots; one host thread per device issues the work and collects the results
+    // every device codes position t of its slots: GPU + download run while the CAVLC threads of the previous position are still coding from the other buffer pair
     const int D = (int)h->devs.size();
-    std::vector<std::string> errs((size_t)D);
-    auto run_dev = [&](int d) {
-        x264_t::DevCtx &dc = h->devs[(size_t)d];
-        bool ok = D == 1 || x264gpu_set_device(dc.dev) == X264GPU_OK;
-        if (ok && !qps.empty()) {
+    x264gpu_mb *hmb; int16_t *hlv;
+    auto launch = [&](x264_t::DevCtx &dc, int d) {
+        if (!qps.empty()) {
             std::vector<int8_t> q((size_t)dc.nsl); std::vector<float> qm((size_t)dc.nsl);
             for (int l = 0; l < dc.nsl; l++) { q[(size_t)l] = qps[(size_t)(l * D + d)]; qm[(size_t)l] = qpms[(size_t)(l * D + d)]; }
-            ok = x264gpu_encoder_set_stream_qpms(dc.gpu, q.data(), qm.data()) == X264GPU_OK;
+            if (x264gpu_encoder_set_stream_qpms(dc.gpu, q.data(), qm.data()) != X264GPU_OK) return false;
         }
-        ok = ok && x264gpu_encode_frames(dc.gpu, dc.d_ring + (size_t)t * dc.nsl * insz, st, dc.d_mb, dc.d_lv, nullptr) == X264GPU_OK &&
-             x264gpu_memcpy_d2h(hmb + (size_t)dc.base * h->nmb, dc.d_mb, (size_t)dc.nsl * h->nmb * sizeof(x264gpu_mb), nullptr) == X264GPU_OK &&
-             x264gpu_memcpy_d2h(hlv + (size_t)dc.base * h->nmb * X264GPU_MB_LEVELS, dc.d_lv, (size_t)dc.nsl * h->nmb * X264GPU_MB_LEVELS * sizeof(int16_t), nullptr) == X264GPU_OK;
-        if (!ok) errs[(size_t)d] = std::string("device ") + std::to_string(dc.dev) + ": " + x264gpu_last_error();      // the error text is per thread
+        return x264gpu_encode_frames(dc.gpu, dc.d_ring + (size_t)t * dc.nsl * insz, st, dc.d_mb, dc.d_lv, nullptr) == X264GPU_OK;
     };
-    if (D == 1) run_dev(0);
-    else {
-        std::vector<std::thread> ths;
-        for (int d = 0; d < D; d++) ths.emplace_back(run_dev, d);
-        for (auto &th : ths) th.join();
-    }
-    for (int d = 0; d < D; d++)
-        if (!errs[(size_t)d].empty()) {
-            xlog(&p, X264_LOG_ERROR, "x264_encoder_encode: GPU hot path failed: %s\n", errs[(size_t)d].c_str());
-            join_pool(h); h->failed = true;
-            return -1;
-        }
-    join_pool(h);
-    auto work = [h, batch, t, st, hmb, hlv, qps, D](int s) {
+    if (run_devices(h, 0, nslots_with_t, false, launch, &hmb, &hlv) < 0) return -1;
+    start_pool(h, t, 0, nslots_with_t, [h, batch, t, st, hmb, hlv, qps, D](int s) {
         const x264_param_t &p = h->param;
-        const int G = h->G;
         const size_t row = (size_t)h->devs[(size_t)(s % D)].base + (size_t)(s / D);       // where slot s landed in the download buffers
-        x264_t::Coded &c = h->slotbuf[(size_t)s * h->keyint + t];
-        c.bytes.clear(); c.off.clear(); c.types.clear();
-        c.idr = t == 0;
-        const long gop = (long)batch * G + s;
-        if (p.b_aud) { c.off.push_back(c.bytes.size()); c.types.push_back(9); write_aud(c.bytes, t == 0 ? 0 : 1, p.b_annexb != 0); }
-        if (c.idr && p.b_repeat_headers) {
-            const bool annexb = p.b_annexb != 0;
-            c.off.push_back(c.bytes.size()); c.types.push_back(7); write_sps(c.bytes, make_sps(h), annexb);
-            c.off.push_back(c.bytes.size()); c.types.push_back(8); write_pps(c.bytes, make_pps(h), annexb);
-            if (gop == 0) { c.off.push_back(c.bytes.size()); c.types.push_back(6); write_sei_version(c.bytes, kSeiText, annexb); }
-        }
-        SliceParams sp = {};
-        sp.mbw = h->mbw; sp.mbh = h->mbh; sp.slice_type = st; sp.qp = !qps.empty() ? (int)qps[(size_t)s] : c.idr ? h->qp_i : h->qp_p; sp.pic_init_qp = h->pic_init_qp;
-        sp.frame_num = t & ((1 << h->log2_max_frame_num) - 1); sp.log2_max_frame_num = h->log2_max_frame_num;
-        sp.idr = c.idr; sp.idr_pic_id = (int)(gop & 0xffff); sp.nal_ref_idc = c.idr ? 3 : 2; sp.pps_id = p.i_sps_id;
-        sp.num_ref_default = p.i_frame_reference;
+        const bool idr = t == 0;
+        SliceParams sp = slice_params_base(h);
+        sp.slice_type = st; sp.qp = !qps.empty() ? (int)qps[(size_t)s] : idr ? h->qp_i : h->qp_p;
+        sp.frame_num = t & ((1 << h->log2_max_frame_num) - 1); sp.idr = idr; sp.nal_ref_idc = idr ? 3 : 2;
         sp.num_ref = t < p.i_frame_reference ? (t > 0 ? t : 1) : p.i_frame_reference;
-        sp.disable_deblock_idc = p.b_deblocking_filter ? 0 : 1; sp.slices_plain = h->slices_plain;
-        sp.alpha_off_div2 = p.i_deblocking_filter_alphac0; sp.beta_off_div2 = p.i_deblocking_filter_beta;
-        sp.transform8x8_mode = p.analyse.b_transform_8x8; sp.cabac = p.b_cabac;
-        {
-            const size_t before = c.off.size();
-            write_picture(c.bytes, &c.off, sp, h->slices, hmb + row * h->nmb, hlv + row * h->nmb * X264GPU_MB_LEVELS, p.b_annexb != 0, before == 0, nullptr);
-            for (size_t i = before; i < c.off.size(); i++) c.types.push_back(c.idr ? 5 : 1);
-        }
-    };
-    const unsigned hw = std::thread::hardware_concurrency();
-    const int nthr = (int)(hw ? (hw < (unsigned)nslots_with_t ? hw : (unsigned)nslots_with_t) : 1);
-    h->pool_t = t; h->pool_nslots = nslots_with_t;
-    for (int th = 0; th < nthr; th++)
-        h->pool.emplace_back([work, th, nthr, nslots_with_t]() { for (int s = th; s < nslots_with_t; s += nthr) work(s); });
+        write_coded(h, h->slotbuf[(size_t)s * h->keyint + t], idr ? PIC_IDR : PIC_P, (long)batch * h->G + s, sp, hmb + row * h->nmb, hlv + row * h->nmb * X264GPU_MB_LEVELS);
+    });
     return 0;
 }
 
@@ -1393,23 +1473,12 @@ static int encode_gop_parallel(x264_t *h, x264_nal_t **pp_nal, int *pi_nal, x264
     h->nal_off = c.off;
     publish_nals(h, pp_nal, pi_nal, c.types);
     if (h->gopb) for (size_t i = 0; i < h->nals.size(); i++) if (c.types[i] == 1 || c.types[i] == 5) h->nals[i].i_ref_idc = c.ref_idc;
-    if (pic_out && h->gopb) {
-        // coding order: the picture's own pts; x264's dts: the k-th coded picture takes the pts of display picture k - delay (the first ones shifted back)
-        x264_picture_init(pic_out);
-        pic_out->i_type = c.i_type; pic_out->b_keyframe = c.idr;
-        const long k = h->emitted, gop_base = k - k % K, delay = !h->bframes ? 0 : h->bpyramid ? 2 : 1;
-        const size_t np = h->all_pts.size();
-        const size_t di = (size_t)(gop_base + c.disp);
-        pic_out->i_pts = h->all_pts[di < np ? di : np - 1];
-        if (k >= delay) pic_out->i_dts = h->all_pts[(size_t)(k - delay) < np ? (size_t)(k - delay) : np - 1];
-        else pic_out->i_dts = h->all_pts[(size_t)k < np ? (size_t)k : np - 1] - (h->all_pts[(size_t)delay < np ? (size_t)delay : np - 1] - h->all_pts[0]);
-    } else
-    if (pic_out) {
-        x264_picture_init(pic_out);
-        pic_out->i_type = c.idr ? X264_TYPE_IDR : X264_TYPE_P;
-        pic_out->b_keyframe = c.idr;
-        pic_out->i_pts = h->pts.front(); pic_out->i_dts = h->pts.front();
-    }
+    if (h->gopb && pic_out) {
+        // coding order: the picture's own pts (its display place in its GOP) and x264's dts
+        const long k = h->emitted, gop_base = k - k % K;
+        const size_t np = h->all_pts.size(), di = (size_t)(gop_base + c.disp);
+        fill_pic_out(pic_out, c.i_type, c.idr, h->all_pts[di < np ? di : np - 1], coded_dts(h, k), nullptr);
+    } else fill_pic_out(pic_out, c.idr ? X264_TYPE_IDR : X264_TYPE_P, c.idr, h->pts.front(), h->pts.front(), nullptr);
     h->pts.pop_front();
     h->emitted++;
     h->frame_no++;
@@ -1547,36 +1616,18 @@ static int encode_queued(x264_t *h, x264_nal_t **pp_nal, int *pi_nal, x264_pictu
     memcpy(h->last_costs, e.costs, sizeof(e.costs));
     if (idr) { h->frames_since_idr = 0; h->frame_num = 0; }
     // ---- host: headers + entropy coding ----
+    const int type = idr ? PIC_IDR : intra_pic ? PIC_I : PIC_P;
     h->out.clear(); h->nal_off.clear();
     std::vector<int> types;
-    if (p.b_aud) { h->nal_off.push_back(h->out.size()); types.push_back(9); write_aud(h->out, st != X264GPU_SLICE_P ? 0 : 1, p.b_annexb != 0); }
-    if (idr && p.b_repeat_headers) {
-        emit_sets(h, types, !h->sei_sent);
-        h->sei_sent = 1;
-    }
-    SliceParams sp = {};
-    sp.mbw = h->mbw; sp.mbh = h->mbh; sp.slice_type = st == X264GPU_SLICE_P ? X264GPU_SLICE_P : X264GPU_SLICE_I; sp.qp = qp_now; sp.pic_init_qp = h->pic_init_qp;
-    sp.frame_num = h->frame_num; sp.log2_max_frame_num = h->log2_max_frame_num;
-    sp.idr = idr; sp.idr_pic_id = h->idr_pic_id; sp.nal_ref_idc = idr ? 3 : 2; sp.pps_id = p.i_sps_id;
-    sp.num_ref_default = p.i_frame_reference;
+    if (begin_access_unit(h, h->out, h->nal_off, types, type, !h->sei_sent)) h->sei_sent = 1;
+    SliceParams sp = slice_params_base(h);
+    sp.slice_type = st == X264GPU_SLICE_P ? X264GPU_SLICE_P : X264GPU_SLICE_I; sp.qp = qp_now; sp.frame_num = h->frame_num;
+    sp.idr = idr; sp.idr_pic_id = h->idr_pic_id; sp.nal_ref_idc = idr ? 3 : 2;
     sp.num_ref = h->frames_since_idr < p.i_frame_reference ? (h->frames_since_idr > 0 ? h->frames_since_idr : 1) : p.i_frame_reference;
-    sp.disable_deblock_idc = p.b_deblocking_filter ? 0 : 1; sp.slices_plain = h->slices_plain;
-    sp.alpha_off_div2 = p.i_deblocking_filter_alphac0; sp.beta_off_div2 = p.i_deblocking_filter_beta;
-    sp.transform8x8_mode = p.analyse.b_transform_8x8; sp.cabac = p.b_cabac;
     h->last_stats.skip = 0;
-    {
-        const size_t before = h->nal_off.size();
-        write_picture(h->out, &h->nal_off, sp, h->slices, hmb, hlv, p.b_annexb != 0, before == 0, &h->last_stats, h->cavlc_threads);
-        for (size_t i = before; i < h->nal_off.size(); i++) types.push_back(idr ? 5 : 1);
-    }
+    write_slices(h->out, h->nal_off, types, sp, h->slices, hmb, hlv, p.b_annexb != 0, idr, &h->last_stats, h->cavlc_threads);
     publish_nals(h, pp_nal, pi_nal, types);
-    if (pic_out) {
-        x264_picture_init(pic_out);
-        pic_out->i_type = idr ? X264_TYPE_IDR : intra_pic ? X264_TYPE_I : X264_TYPE_P;
-        pic_out->b_keyframe = idr;
-        pic_out->i_pts = e.pts; pic_out->i_dts = e.pts;
-        pic_out->img = e.img;
-    }
+    fill_pic_out(pic_out, x264_type_of(type), idr, e.pts, e.pts, &e.img);
     if (idr) h->idr_pic_id = (h->idr_pic_id + 1) & 0xffff;
     h->frame_num = (h->frame_num + 1) & ((1 << h->log2_max_frame_num) - 1);
     if (h->abr) {
@@ -2087,8 +2138,6 @@ static bool bmode_decide(x264_t *h, bool flushing)
 
 // ---- 2-pass rate control (x264 ratecontrol.c: x264_ratecontrol_new's statistics parser, init_pass2, get_qscale / get_diff_limited_q,
 //      qscale2bits; no VBV, no zones, no macroblock-tree file: the tree is off in these sessions) ----
-static double p2_qp2qscale(double q) { return rc_qp2qscale(q); }
-static double p2_qscale2qp(double qs) { return rc_qscale2qp(qs); }
 static double p2_qscale2bits(const x264_t::Pass2Entry &e, double qscale)
 {
     if (qscale < 0.1) qscale = 0.1;
@@ -2109,7 +2158,7 @@ static bool p2_load(x264_t *h, const char *path)
         char d = '-';
         if (sscanf(line, " in:%d out:%d type:%c dur:%lld cpbdur:%lld q:%f aq:%f tex:%d mv:%d misc:%d imb:%d pmb:%d smb:%d d:%c", &e.in, &e.out, &e.type, &dur, &cpbdur, &q, &aq,
                    &tex, &mv, &misc, &imb, &pmb, &smb, &d) < 13) { fclose(f); xlog(&h->param, X264_LOG_ERROR, "statistics are damaged at line %d, parser out\n", (int)raw.size() + 1); return false; }
-        e.qp = q; e.qscale = p2_qp2qscale(q); e.tex = tex; e.mv = mv; e.misc = misc; e.icount = imb; e.dur = dur > 0 ? (double)dur : 1.0; e.kept_as_ref = e.type != 'b';
+        e.qp = q; e.qscale = rc_qp2qscale(q); e.tex = tex; e.mv = mv; e.misc = misc; e.icount = imb; e.dur = dur > 0 ? (double)dur : 1.0; e.kept_as_ref = e.type != 'b';
         raw.push_back(e);
     }
     fclose(f);
@@ -2136,7 +2185,7 @@ static bool p2_init(x264_t *h)
     const double qblur = p.rc.f_qblur, cplxblur = p.rc.f_complexity_blur, qcompress = p.rc.f_qcompress;
     const int filter_size = (int)(qblur * 4) | 1;
     const double base_cplx = nmb * (p.i_bframe ? 120 : 80);
-    const double lstep = pow(2.0, p.rc.i_qp_step / 6.0), lmin = p2_qp2qscale(p.rc.i_qp_min), lmax = p2_qp2qscale(p.rc.i_qp_max);
+    const double lstep = pow(2.0, p.rc.i_qp_step / 6.0), lmin = rc_qp2qscale(p.rc.i_qp_min), lmax = rc_qp2qscale(p.rc.i_qp_max);
     const double ipf = fabs(p.rc.f_ip_factor) > 0 ? fabs(p.rc.f_ip_factor) : 1.0, pbf = fabs(p.rc.f_pb_factor) > 0 ? fabs(p.rc.f_pb_factor) : 1.0;
     double all_const_bits = 0;
     for (auto &e : E) all_const_bits += e.misc;
@@ -2179,7 +2228,7 @@ static bool p2_init(x264_t *h)
         const int kind = p2_kind(e.type);
         const double last_p_q = last_q[1], last_non_b_q = last_non_b >= 0 ? last_q[last_non_b] : q;
         if (kind == 0) {
-            const double iq = q, pq = accum_p_norm > 0 ? p2_qp2qscale(accum_p_qp / accum_p_norm) : q;
+            const double iq = q, pq = accum_p_norm > 0 ? rc_qp2qscale(accum_p_qp / accum_p_norm) : q;
             if (accum_p_norm <= 0) q = iq;
             else if (p.rc.f_ip_factor < 0) q = iq / ipf;
             else if (accum_p_norm >= 1) q = pq / ipf;
@@ -2195,7 +2244,7 @@ static bool p2_init(x264_t *h)
         last_q[kind] = q;
         if (kind != 2) last_non_b = kind;
         if (kind == 0) { last_accum_p_norm = accum_p_norm; accum_p_norm = 0; accum_p_qp = 0; }
-        if (kind == 1) { const float mask = (float)(1 - pow((float)e.icount / (float)h->nmb, 2)); accum_p_qp          /* (a float in x264) */ = mask * (p2_qscale2qp(q) + accum_p_qp); accum_p_norm = mask * (1 + accum_p_norm); }
+        if (kind == 1) { const float mask = (float)(1 - pow((float)e.icount / (float)h->nmb, 2)); accum_p_qp          /* (a float in x264) */ = mask * (rc_qscale2qp(q) + accum_p_qp); accum_p_norm = mask * (1 + accum_p_norm); }
         return q;
     };
     double expected_bits = 1;
@@ -2238,7 +2287,7 @@ static bool p2_init(x264_t *h)
     if (fabs(expected_bits / all_available_bits - 1.0) > 0.01) {
         double avgq = 0;
         for (auto &e : E) avgq += e.new_qscale;
-        avgq = p2_qscale2qp(avgq / n);
+        avgq = rc_qscale2qp(avgq / n);
         xlog(&p, X264_LOG_WARNING, "Error: 2pass curve failed to converge\n");
         xlog(&p, X264_LOG_WARNING, "target: %.2f kbit/s, expected: %.2f kbit/s, avg QP: %.4f\n", (double)p.rc.i_bitrate, expected_bits / duration / 1000., avgq);
     }
@@ -2264,7 +2313,7 @@ static double p2_pick_qscale(x264_t *h, int frame, long coded_so_far)
         const double cur_time = (double)coded_so_far / n, w = cur_time * 100 < 0 ? 0 : cur_time * 100 > 1 ? 1 : cur_time * 100;
         q *= pow(h->p2_total_bits / h->p2_expected_sum, w);
     }
-    const double lmin = p2_qp2qscale(p.rc.i_qp_min), lmax = p2_qp2qscale(p.rc.i_qp_max);
+    const double lmin = rc_qp2qscale(p.rc.i_qp_min), lmax = rc_qp2qscale(p.rc.i_qp_max);
     return q < lmin ? lmin : q > lmax ? lmax : q;
 }
 
@@ -2276,7 +2325,7 @@ static int bmode_qp(x264_t *h, const x264_t::BPlanned &pl, const DpbPlan &plan, 
     const double pb_offset = 6.0 * log2f(fabs(p.rc.f_pb_factor) > 0 ? fabsf(p.rc.f_pb_factor) : 1.0f);          // rc->pb_offset = 6.0 * log2f( f_pb_factor )
     const bool is_i = pl.type == PIC_IDR || pl.type == PIC_I, is_b = pl.type == PIC_B || pl.type == PIC_BREF;
     if (h->pass2) {
-        double q = p2_qscale2qp(p2_pick_qscale(h, pl.e.frame, h->coded_count));
+        double q = rc_qscale2qp(p2_pick_qscale(h, pl.e.frame, h->coded_count));
         q = q < p.rc.i_qp_min ? p.rc.i_qp_min : q > p.rc.i_qp_max ? p.rc.i_qp_max : q;
         *qp_float = q;
         return clampi((int)(q + 0.5), 1, 51);
@@ -2316,6 +2365,137 @@ static int bmode_qp(x264_t *h, const x264_t::BPlanned &pl, const DpbPlan &plan, 
     return clampi((int)(q + 0.5), p.rc.i_qp_min, p.rc.i_qp_max);
 }
 
+// ---- the picture path of sessions on the DPB model: plan, launch, finish --------------------------------------------------------------
+// One picture a call (encode_bmode), its batched variant whose pictures leave a call later (bmode_defer) and several pictures in flight (inflight_issue /
+// inflight_retire) are built from the same three steps; what they do differently is an argument or a branch here, each with the mode that needs it.
+
+// plan: takes the next picture of the coding order and settles everything the device and the slice writer will be told — the DPB model's plan (the follow list
+// counts from coded_index, the picture's place in the coding order: pictures in flight have not been counted yet), the quantiser, the direct mode, the lookahead's
+// vectors and the quantiser offsets on `gpu` (the encoder that will run it: the session's, or a launch context's), what later pictures' rate control and direct
+// mode read of it by DPB slot, the slice parameters.  Dpb::commit stays with the caller (serial: after the slices, deferred: before the helper thread starts,
+// in flight: when the picture is issued).  serial: one picture at a time, so --direct auto can follow the skip counts of the picture before
+static void bmode_plan(x264_t *h, x264_t::PicPlan &f, x264gpu_encoder *gpu, long coded_index, bool serial)
+{
+    f.pl = h->bcoding.front();
+    h->bcoding.pop_front();
+    const x264_t::BPlanned &pl = f.pl;
+    // the disposable pictures coded right behind this one (x264_reference_hierarchy_reset looks at them)
+    int fc[16], ff[16], nf = 0;
+    for (size_t i = 0; i < h->bcoding.size() && nf < 16 && h->bcoding[i].type == PIC_B; i++) { fc[nf] = (int)(coded_index + 1 + (long)i); ff[nf] = h->bcoding[i].e.frame; nf++; }
+    const DpbPlan plan = h->dpb.plan(pl.type, pl.e.frame, nf, fc, ff, pl.type == PIC_P && pl.e.w.on ? &pl.e.w : nullptr);
+    f.nal_ref_idc = plan.nal_ref_idc;
+    x264gpu_pic &pic = f.pic;
+    pic = plan.pic;
+    pic.qp = bmode_qp(h, pl, plan, &f.qpf);
+    // x264_ratecontrol_mb_qp: a macroblock's quantiser is round(rc->qpm + its AQ / macroblock-tree offset) with qpm the picture's FLOAT quantiser
+    pic.qpm = near_qpm(f.qpf, pic.qp);
+    h->rc_frames++;
+    const bool is_b = pl.type == PIC_B || pl.type == PIC_BREF;
+    f.direct_auto_write = false;
+    if (is_b && h->direct_mode != 1) {
+        // x264 slice_header_init: temporal direct prediction is considered only when the co-located picture's reference 0 is this picture's reference 0;
+        // --direct auto (serial only: sessions with pictures in flight never run it): the mode whose skip probe passed more often so far
+        // (h->stat.i_direct_score), every macroblock probing both again
+        bool spatial = true;
+        if (pic.nref[0] && pic.nref[1] && h->slot_l0ref0poc[pic.slot[1][0]] == plan.list_poc[0][0]) {
+            f.direct_auto_write = serial && h->direct_mode == 3;
+            spatial = f.direct_auto_write ? h->direct_score[1] > h->direct_score[0] : false;
+        }
+        pic.direct_temporal = !spatial; pic.direct_auto = f.direct_auto_write;
+        h->dpb.set_direct(pic.direct_temporal, pic.direct_auto);
+    }
+    if (h->st) {
+        // x264_mb_predict_mv_ref16x16: the lookahead's vectors towards reference 0 of each list as search candidates, when that search ran
+        // (fenc->lowres_mvs[list][distance - 1], distances up to bframes + 1)
+        const int dist0 = pic.nref[0] ? (pic.poc - plan.list_poc[0][0]) / 2 : 0, dist1 = pic.nref[1] ? (plan.list_poc[1][0] - pic.poc) / 2 : 0;
+        const int16_t *m0 = dist0 >= 1 && dist0 <= h->bframes + 1 ? x264gpu_slicetype_lowres_mvs(h->st, pl.e.slot, 0, dist0) : nullptr;
+        const int16_t *m1 = dist1 >= 1 && dist1 <= h->bframes + 1 ? x264gpu_slicetype_lowres_mvs(h->st, pl.e.slot, 1, dist1) : nullptr;
+        x264gpu_encoder_set_lowres_mvs(gpu, m0);
+        x264gpu_encoder_set_lowres_mvs1(gpu, m1);
+    }
+    f.d_offsets = nullptr;
+    if (h->st && h->mbtree)          // P / I / B-reference pictures: what the tree left (AQ - tree); other B pictures: the AQ offsets alone (x264 f_qp_offset_aq)
+        f.d_offsets = pl.type == PIC_B ? h->q_aq[(size_t)pl.e.slot] : h->q_tree[(size_t)pl.e.slot];
+    else if (h->aq_mode >= 2 && h->aq_strength != 0.f) f.d_offsets = h->q_aq[(size_t)pl.e.slot];      // --aq-mode 2 / 3: the offsets computed when the picture arrived
+    // (the serial path names a buffer only when there is one; a launch context is always told, "none" included)
+    if (f.d_offsets || !serial) x264gpu_encoder_set_mb_qp_offsets(gpu, f.d_offsets);
+    if (plan.nal_ref_idc) { h->slot_qp_rc[pic.dst] = rc_qp_avg_rc((float)f.qpf, h->mbw, h->mbh); h->slot_ptype[pic.dst] = pl.type; }
+    if (plan.nal_ref_idc) h->slot_l0ref0poc[pic.dst] = pic.nref[0] ? plan.list_poc[0][0] : INT_MIN;
+    f.direct_char = is_b ? (pic.direct_temporal ? 't' : 's') : '-';
+    f.sp = slice_params_base(h);
+    f.sp.qp = pic.qp;
+    h->dpb.fill(f.sp);
+}
+
+// finish, on the caller's thread: the picture becomes the one the diagnostics hooks describe, its access unit is opened in h->out (AUD, sets in front of an IDR
+// picture).  idr_pic_id is read here — when the picture is handed to the slice writer, which for a picture in flight is when it retires, not when it was planned
+static void bmode_open_au(x264_t *h, x264_t::PicPlan &f, std::vector<int> &types)
+{
+    const x264_t::BPlanned &pl = f.pl;
+    h->last_direct_char = f.direct_char;
+    h->last_scenecut = pl.e.scenecut; h->last_qp = f.pic.qp; h->last_qpm = f.pic.qpm;
+    memcpy(h->last_costs, pl.e.costs, sizeof(pl.e.costs));
+    h->out.clear(); h->nal_off.clear();
+    if (begin_access_unit(h, h->out, h->nal_off, types, pl.type, !h->sei_sent)) h->sei_sent = 1;
+    f.sp.idr_pic_id = h->idr_pic_id;
+}
+// ... and the session's counters move past it
+static void bmode_count(x264_t *h, bool idr)
+{
+    h->t_b[4] += 1;
+    if (idr) h->idr_pic_id = (h->idr_pic_id + 1) & 0xffff;
+    h->coded_count++;
+    h->frame_no++;
+}
+
+// finish: the picture's NAL units from its downloaded records, pic_out, what the rate control learns from its size (x264_ratecontrol_end: 2-pass and ABR sessions,
+// which always run serially), the counters; returns the bytes of the NAL units
+static int bmode_finish(x264_t *h, x264_t::PicPlan &f, const x264gpu_mb *mbs, const int16_t *levels, x264_nal_t **pp_nal, int *pi_nal, x264_picture_t *pic_out)
+{
+    const x264_param_t &p = h->param;
+    const x264_t::BPlanned &pl = f.pl;
+    const bool idr = pl.type == PIC_IDR;
+    std::vector<int> types;
+    bmode_open_au(h, f, types);
+    h->last_stats.skip = 0;
+    write_slices(h->out, h->nal_off, types, f.sp, h->slices, mbs, levels, p.b_annexb != 0, idr, &h->last_stats, h->cavlc_threads);
+    publish_nals(h, pp_nal, pi_nal, types);
+    for (size_t i = 0; i < h->nals.size(); i++) if (types[i] == 1 || types[i] == 5) h->nals[i].i_ref_idc = f.nal_ref_idc;
+    fill_pic_out(pic_out, x264_type_of(pl.type), idr, pl.e.pts, coded_dts(h, h->coded_count), &pl.e.img);
+    if (h->pass1 || h->pass2) {
+        // x264_ratecontrol_end: the picture's line of the statistics file / the second pass' account of what was spent against the plan
+        const long total = (long)h->out.size() * 8;
+        long imb = 0, pmb = 0, smb = 0;
+        double aqsum = 0;
+        for (size_t i = 0; i < (size_t)h->nmb; i++) {
+            const x264gpu_mb &m = mbs[i];
+            if (m.type <= X264GPU_MB_I16x16) imb++; else if (m.type == X264GPU_MB_P_SKIP || m.type == X264GPU_MB_B_SKIP) smb++; else pmb++;
+            aqsum += m.qp;
+        }
+        if (h->stat_file) {
+            const char t = idr ? 'I' : pl.type == PIC_I ? 'i' : pl.type == PIC_P ? 'P' : pl.type == PIC_BREF ? 'B' : 'b';
+            const long mv = h->last_stats.mv_bits, tex = h->last_stats.tex_bits, misc = total - mv - tex;
+            fprintf(h->stat_file, "in:%d out:%ld type:%c dur:%d cpbdur:%d q:%.2f aq:%.2f tex:%ld mv:%ld misc:%ld imb:%ld pmb:%ld smb:%ld d:%c ref:;\n", pl.e.frame, h->coded_count, t, 1, 1, f.qpf,
+                    aqsum / h->nmb, tex, mv, misc, imb, pmb, smb, h->last_direct_char);
+        }
+        if (h->pass2) {
+            h->p2_total_bits += (double)total;
+            if (pl.e.frame < (int)h->p2.size()) h->p2_expected_sum += p2_qscale2bits(h->p2[(size_t)pl.e.frame], rc_qp2qscale(f.qpf));
+        }
+    }
+    if (h->abr) {
+        // x264_ratecontrol_end: what the picture took moves the rate factor of the pictures to come (a B picture's quantiser is an offset of
+        // its neighbours': its bits count divided by pbratio)
+        const double bits = (double)h->out.size() * 8.0, pb = fabs(p.rc.f_pb_factor) > 0 ? fabs(p.rc.f_pb_factor) : 1.0;
+        const bool is_b = pl.type == PIC_B || pl.type == PIC_BREF;
+        h->rc.total_bits += bits;
+        h->rc.cplxr_sum += bits * rc_qp2qscale(rc_qp_avg_rc((float)f.qpf, h->mbw, h->mbh)) / (h->rc.last_rceq * (is_b ? pb : 1.0));
+        h->rc.wanted_bits_window += h->rc.bitrate / h->rc.fps;
+    }
+    bmode_count(h, idr);
+    return (int)h->out.size();
+}
+
 // hands out a picture a helper thread finished (batch sessions with overlap): waits for the thread, publishes its NAL units; 0 when the slot is empty
 static int publish_deferred(x264_t *h, x264_t::Deferred &d, x264_nal_t **pp_nal, int *pi_nal, x264_picture_t *pic_out)
 {
@@ -2334,11 +2514,58 @@ static int publish_deferred(x264_t *h, x264_t::Deferred &d, x264_nal_t **pp_nal,
     h->last_qp = d.qp; h->last_qpm = d.qpm; h->last_scenecut = d.scenecut; memcpy(h->last_costs, d.costs, sizeof(d.costs));
     publish_nals(h, pp_nal, pi_nal, d.types);
     for (size_t i = 0; i < h->nals.size(); i++) if (d.types[i] == 1 || d.types[i] == 5) h->nals[i].i_ref_idc = d.nal_ref_idc;
-    if (pic_out) {
-        x264_picture_init(pic_out);
-        pic_out->i_type = d.i_type; pic_out->b_keyframe = d.b_keyframe; pic_out->i_pts = d.pts; pic_out->i_dts = d.dts; pic_out->img = d.img;
-    }
+    fill_pic_out(pic_out, d.i_type, d.b_keyframe, d.pts, d.dts, &d.img);
     return (int)h->out.size();
+}
+
+// finish of a batch session with overlap: everything the slice writer needs is fixed, so a helper thread downloads this stream's records and levels (round's buffer
+// pair `bbuf`, on the group's download stream) and writes the slices behind the header NAL units while the group's next round runs; the DPB moves on at once (the
+// next picture's plan needs it) and the NAL units leave with the NEXT call: returns the picture of the call before (0: none yet).
+// (No x264_ratecontrol_end and no statistics line here: x264_encoder_open admits constant-quantiser and CRF sessions into a batch only.)
+static int bmode_defer(x264_t *h, x264_t::PicPlan &f, int bbuf, x264_nal_t **pp_nal, int *pi_nal, x264_picture_t *pic_out)
+{
+    const x264_param_t &p = h->param;
+    const x264_t::BPlanned &pl = f.pl;
+    const bool idr = pl.type == PIC_IDR;
+    std::vector<int> types;
+    bmode_open_au(h, f, types);
+    x264_t::Deferred &d = h->defer[h->defer_cur];
+    if (d.th.joinable()) d.th.join();          // (handed out two calls ago: long finished)
+    d.out = h->out; d.off = h->nal_off; d.types = types; d.err.clear(); d.nal_ref_idc = f.nal_ref_idc; d.stats = SliceStats{ 0 };
+    d.mb.resize((size_t)h->nmb);
+    if (h->batch->pack) d.ix.resize((size_t)h->nmb);
+    if (!d.lv) d.lv.reset(new (std::nothrow) int16_t[(size_t)h->nmb * X264GPU_MB_LEVELS]);
+    if (!d.lv) { xlog(&p, X264_LOG_ERROR, "x264_encoder_encode: out of memory (download buffers)\n"); h->failed = true; return -1; }
+    d.i_type = x264_type_of(pl.type); d.b_keyframe = idr; d.pts = pl.e.pts; d.img = pl.e.img;
+    d.qp = f.pic.qp; d.qpm = f.pic.qpm; d.scenecut = pl.e.scenecut; memcpy(d.costs, pl.e.costs, sizeof(d.costs));
+    if (h->abr || h->pass1 || h->pass2) { xlog(&p, X264_LOG_ERROR, "x264_encoder_encode: a batched session cannot run rate control that reads the coded sizes\n"); h->failed = true; return -1; }
+    d.dts = coded_dts(h, h->coded_count);
+    BatchGroup *g = h->batch;
+    const SliceParams sp = f.sp;
+    const int bidx = h->batch_idx, slices = h->slices, threads = h->cavlc_threads, dev = h->device;
+    const bool annexb = p.b_annexb != 0;
+    long my_launched;
+    { std::lock_guard<std::mutex> lg(g->m); my_launched = g->launched; }
+    d.hurry = false;
+    d.th = std::thread([&d, g, bidx, bbuf, sp, slices, threads, annexb, idr, dev, my_launched]() {
+        x264gpu_set_device(dev);
+        x264gpu_level_index *ix = d.ix.empty() ? nullptr : d.ix.data();
+        if (batch_download(g, bidx, bbuf, d.mb.data(), d.lv.get(), d.err, ix)) return;
+        const long t0 = g->timing ? us_now() : 0;
+        {
+            // the slices are written once the group's next round is on the device (the callers need the cores to get it there), or when the picture is asked for
+            std::unique_lock<std::mutex> lk(g->m);
+            g->cv.wait_for(lk, std::chrono::seconds(30), [&] { return g->launched > my_launched || d.hurry.load() || g->closed; });
+        }
+        const long t1 = g->timing ? us_now() : 0;
+        write_slices(d.out, d.off, d.types, sp, slices, d.mb.data(), d.lv.get(), annexb, idr, &d.stats, threads, ix);
+        if (g->timing) { const long t2 = us_now(); g->t_us[2] += t1 - t0; g->t_us[3] += t2 - t1; if (my_launched >= 1 && my_launched <= 64) g->r_sl[my_launched - 1] += t2 - t1; }
+    });
+    d.valid = true;
+    h->dpb.commit();
+    bmode_count(h, idr);
+    h->defer_cur ^= 1;
+    return publish_deferred(h, h->defer[h->defer_cur], pp_nal, pi_nal, pic_out);
 }
 
 // codes the next picture in coding order; returns the bytes of its NAL units, 0 when the queue still waits for input
@@ -2351,57 +2578,22 @@ static int encode_bmode(x264_t *h, x264_nal_t **pp_nal, int *pi_nal, x264_pictur
     const bool decided = bmode_decide(h, flushing);
     BPHASE(0);
     if (!decided) return flushing ? publish_deferred(h, h->defer[h->defer_cur ^ 1].valid ? h->defer[h->defer_cur ^ 1] : h->defer[h->defer_cur], pp_nal, pi_nal, pic_out) : 0;
-    const x264_t::BPlanned pl = h->bcoding.front();
-    h->bcoding.pop_front();
-    // the disposable pictures coded right behind this one (x264_reference_hierarchy_reset looks at them)
-    int fc[16], ff[16], nf = 0;
-    for (size_t i = 0; i < h->bcoding.size() && nf < 16 && h->bcoding[i].type == PIC_B; i++) { fc[nf] = (int)(h->coded_count + 1 + (long)i); ff[nf] = h->bcoding[i].e.frame; nf++; }
-    const DpbPlan plan = h->dpb.plan(pl.type, pl.e.frame, nf, fc, ff, pl.type == PIC_P && pl.e.w.on ? &pl.e.w : nullptr);
-    x264gpu_pic pic = plan.pic;
-    double qpf = 0;
-    pic.qp = bmode_qp(h, pl, plan, &qpf);
-    // x264_ratecontrol_mb_qp: a macroblock's quantiser is round(rc->qpm + its AQ / macroblock-tree offset) with qpm the picture's FLOAT quantiser
-    pic.qpm = near_qpm(qpf, pic.qp);
-    h->rc_frames++;
-    bool direct_auto_write = false;
-    if ((pl.type == PIC_B || pl.type == PIC_BREF) && h->direct_mode != 1) {
-        // x264 slice_header_init: temporal direct prediction is considered only when the co-located picture's reference 0 is this picture's reference 0;
-        // --direct auto: the mode whose skip probe passed more often so far (h->stat.i_direct_score), every macroblock probing both again
-        bool spatial = true;
-        if (pic.nref[0] && pic.nref[1] && h->slot_l0ref0poc[pic.slot[1][0]] == plan.list_poc[0][0]) {
-            direct_auto_write = h->direct_mode == 3;
-            spatial = direct_auto_write ? h->direct_score[1] > h->direct_score[0] : false;
-        }
-        pic.direct_temporal = !spatial; pic.direct_auto = direct_auto_write;
-        h->dpb.set_direct(pic.direct_temporal, pic.direct_auto);
-    }
-    if (h->st) {
-        // x264_mb_predict_mv_ref16x16: the lookahead's vectors towards reference 0 of each list as search candidates, when that search ran
-        // (fenc->lowres_mvs[list][distance - 1], distances up to bframes + 1)
-        const int dist0 = pic.nref[0] ? (pic.poc - plan.list_poc[0][0]) / 2 : 0, dist1 = pic.nref[1] ? (plan.list_poc[1][0] - pic.poc) / 2 : 0;
-        const int16_t *m0 = dist0 >= 1 && dist0 <= h->bframes + 1 ? x264gpu_slicetype_lowres_mvs(h->st, pl.e.slot, 0, dist0) : nullptr;
-        const int16_t *m1 = dist1 >= 1 && dist1 <= h->bframes + 1 ? x264gpu_slicetype_lowres_mvs(h->st, pl.e.slot, 1, dist1) : nullptr;
-        x264gpu_encoder_set_lowres_mvs(h->gpu, m0);
-        x264gpu_encoder_set_lowres_mvs1(h->gpu, m1);
-    }
-    const float *d_offsets = nullptr;
-    if (h->st && h->mbtree)          // P / I / B-reference pictures: what the tree left (AQ - tree); other B pictures: the AQ offsets alone (x264 f_qp_offset_aq)
-        d_offsets = pl.type == PIC_B ? h->q_aq[(size_t)pl.e.slot] : h->q_tree[(size_t)pl.e.slot];
-    else if (h->aq_mode >= 2 && h->aq_strength != 0.f) d_offsets = h->q_aq[(size_t)pl.e.slot];      // --aq-mode 2 / 3: the offsets computed when the picture arrived
-    if (d_offsets) x264gpu_encoder_set_mb_qp_offsets(h->gpu, d_offsets);
+    x264_t::PicPlan f;
+    bmode_plan(h, f, h->gpu, h->coded_count, true);
+    // launch: the group's round (its results downloaded here unless a helper thread does it: deferred), or this session's encoder and two downloads on the default stream
+    const uint8_t *d_src = h->q_raw[(size_t)f.pl.e.slot];
     int bbuf = 0;
-    bool deferred = false;
+    const bool deferred = h->batch && h->batch->overlap;
     if (h->batch) {
         std::string berr;
-        deferred = h->batch->overlap;          // the download and the entropy coding of this picture run beside the group's next round (below)
-        if (batch_submit(h->batch, h->batch_idx, h->q_raw[(size_t)pl.e.slot], pic, &bbuf, berr) ||
+        if (batch_submit(h->batch, h->batch_idx, d_src, f.pic, &bbuf, berr) ||
             (!deferred && batch_download(h->batch, h->batch_idx, bbuf, h->h_mb.data(), h->h_lv.data(), berr))) {
             xlog(&p, X264_LOG_ERROR, "x264_encoder_encode: GPU hot path failed: %s\n", berr.c_str());
             h->failed = true;
             return -1;
         }
     } else
-    if (x264gpu_encode_pictures(h->gpu, h->q_raw[(size_t)pl.e.slot], &pic, h->d_mb, h->d_lv, nullptr) != X264GPU_OK || (getenv("X264GPU_HOST_TIMING") && (x264gpu_stream_sync(nullptr), BPHASE(1), false)) ||
+    if (x264gpu_encode_pictures(h->gpu, d_src, &f.pic, h->d_mb, h->d_lv, nullptr) != X264GPU_OK || (getenv("X264GPU_HOST_TIMING") && (x264gpu_stream_sync(nullptr), BPHASE(1), false)) ||
         x264gpu_memcpy_d2h(h->h_mb.data(), h->d_mb, h->h_mb.size() * sizeof(x264gpu_mb), nullptr) != X264GPU_OK ||
         x264gpu_memcpy_d2h(h->h_lv.data(), h->d_lv, h->h_lv.size() * sizeof(int16_t), nullptr) != X264GPU_OK) {
         xlog(&p, X264_LOG_ERROR, "x264_encoder_encode: GPU hot path failed: %s\n", x264gpu_last_error());
@@ -2412,157 +2604,37 @@ static int encode_bmode(x264_t *h, x264_nal_t **pp_nal, int *pi_nal, x264_pictur
     if (const char *dd = getenv("X264GPU_DUMP_RECORDS")) {          // debugging aid: the records and levels of every coded picture, and what was asked of the device
         char fn[512];
         snprintf(fn, sizeof(fn), "%s/pic%04ld.bin", dd, h->coded_count);
-        if (FILE *f = fopen(fn, "wb")) {
-            fwrite(&pic, sizeof(pic), 1, f);
-            fwrite(h->h_mb.data(), sizeof(x264gpu_mb), h->h_mb.size(), f);
-            fwrite(h->h_lv.data(), sizeof(int16_t), h->h_lv.size(), f);
+        if (FILE *fp = fopen(fn, "wb")) {
+            fwrite(&f.pic, sizeof(f.pic), 1, fp);
+            fwrite(h->h_mb.data(), sizeof(x264gpu_mb), h->h_mb.size(), fp);
+            fwrite(h->h_lv.data(), sizeof(int16_t), h->h_lv.size(), fp);
             std::vector<float> off((size_t)h->nmb, 0.f);          // ... and the per-macroblock quantiser offsets it was coded with (zeros: none handed in)
-            if (d_offsets) x264gpu_memcpy_d2h(off.data(), d_offsets, off.size() * sizeof(float), nullptr);
-            fwrite(off.data(), sizeof(float), off.size(), f);
-            fclose(f);
+            if (f.d_offsets) x264gpu_memcpy_d2h(off.data(), f.d_offsets, off.size() * sizeof(float), nullptr);
+            fwrite(off.data(), sizeof(float), off.size(), fp);
+            fclose(fp);
         }
     }
-    if (plan.nal_ref_idc) { h->slot_qp_rc[pic.dst] = rc_qp_avg_rc((float)qpf, h->mbw, h->mbh); h->slot_ptype[pic.dst] = pl.type; }
-    if (plan.nal_ref_idc) h->slot_l0ref0poc[pic.dst] = pic.nref[0] ? plan.list_poc[0][0] : INT_MIN;
-    h->last_direct_char = (pl.type == PIC_B || pl.type == PIC_BREF) ? (pic.direct_temporal ? 't' : 's') : '-';
-    if (direct_auto_write) {
+    if (f.direct_auto_write) {
         // x264_encoder_frame_end ("somewhat arbitrary time constants"): the running counts decay once they exceed a picture's worth, then take this picture's
         int sc[2] = { 0, 0 };
         if (x264gpu_encoder_direct_scores(h->gpu, sc) != X264GPU_OK) { xlog(&p, X264_LOG_ERROR, "direct auto: %s\n", x264gpu_last_error()); h->failed = true; return -1; }
         if (h->direct_score[0] + h->direct_score[1] > h->mbw * h->mbh) for (int i = 0; i < 2; i++) h->direct_score[i] = h->direct_score[i] * 9 / 10;
         for (int i = 0; i < 2; i++) h->direct_score[i] += sc[i];
     }
-    h->last_scenecut = pl.e.scenecut; h->last_qp = pic.qp; h->last_qpm = pic.qpm;
-    memcpy(h->last_costs, pl.e.costs, sizeof(pl.e.costs));
-    const bool idr = pl.type == PIC_IDR;
-    h->out.clear(); h->nal_off.clear();
-    std::vector<int> types;
-    if (p.b_aud) { h->nal_off.push_back(h->out.size()); types.push_back(9); write_aud(h->out, pl.type <= PIC_I ? 0 : pl.type == PIC_P ? 1 : 2, p.b_annexb != 0); }
-    if (idr && p.b_repeat_headers) { emit_sets(h, types, !h->sei_sent); h->sei_sent = 1; }
-    SliceParams sp = {};
-    sp.mbw = h->mbw; sp.mbh = h->mbh; sp.qp = pic.qp; sp.pic_init_qp = h->pic_init_qp; sp.log2_max_frame_num = h->log2_max_frame_num; sp.log2_max_poc_lsb = h->log2_max_poc_lsb;
-    sp.idr_pic_id = h->idr_pic_id; sp.pps_id = p.i_sps_id; sp.num_ref_default = p.i_frame_reference; sp.num_ref1_default = 1;
-    sp.disable_deblock_idc = p.b_deblocking_filter ? 0 : 1; sp.alpha_off_div2 = p.i_deblocking_filter_alphac0; sp.beta_off_div2 = p.i_deblocking_filter_beta;
-    sp.transform8x8_mode = p.analyse.b_transform_8x8; sp.cabac = p.b_cabac; sp.slices_plain = h->slices_plain;
-    h->dpb.fill(sp);
-    if (deferred) {
-        // everything the slice writer needs is fixed now: the helper thread downloads this stream's records and levels (on the group's download stream) and writes the
-        // slices behind the header NAL units; the DPB moves on at once (the next picture's plan needs it), the NAL units leave with the next call
-        x264_t::Deferred &d = h->defer[h->defer_cur];
-        if (d.th.joinable()) d.th.join();          // (handed out two calls ago: long finished)
-        d.out = h->out; d.off = h->nal_off; d.types = types; d.err.clear(); d.nal_ref_idc = plan.nal_ref_idc; d.stats = SliceStats{ 0 };
-        d.mb.resize((size_t)h->nmb);
-        if (h->batch->pack) d.ix.resize((size_t)h->nmb);
-        if (!d.lv) d.lv.reset(new (std::nothrow) int16_t[(size_t)h->nmb * X264GPU_MB_LEVELS]);
-        if (!d.lv) { xlog(&p, X264_LOG_ERROR, "x264_encoder_encode: out of memory (download buffers)\n"); h->failed = true; return -1; }
-        d.i_type = idr ? X264_TYPE_IDR : pl.type == PIC_I ? X264_TYPE_I : pl.type == PIC_P ? X264_TYPE_P : pl.type == PIC_BREF ? X264_TYPE_BREF : X264_TYPE_B;
-        d.b_keyframe = idr; d.pts = pl.e.pts; d.img = pl.e.img;
-        d.qp = pic.qp; d.qpm = pic.qpm; d.scenecut = pl.e.scenecut; memcpy(d.costs, pl.e.costs, sizeof(d.costs));
-        // (the deferred return skips x264_ratecontrol_end and the statistics line below: batched sessions are never ABR / 2-pass — x264_encoder_open admits
-        //  constant-quantiser and CRF sessions into a batch only)
-        if (h->abr || h->pass1 || h->pass2) { xlog(&p, X264_LOG_ERROR, "x264_encoder_encode: a batched session cannot run rate control that reads the coded sizes\n"); h->failed = true; return -1; }
-        {
-            const long k = h->coded_count, delay = !h->bframes ? 0 : h->bpyramid ? 2 : 1;
-            const size_t np = h->all_pts.size();
-            if (k >= delay) d.dts = h->all_pts[(size_t)(k - delay) < np ? (size_t)(k - delay) : np - 1];
-            else d.dts = h->all_pts[(size_t)k < np ? (size_t)k : np - 1] - (h->all_pts[(size_t)delay < np ? (size_t)delay : np - 1] - h->all_pts[0]);
-        }
-        BatchGroup *g = h->batch;
-        const int bidx = h->batch_idx, slices = h->slices, threads = h->cavlc_threads, dev = h->device;
-        const bool annexb = p.b_annexb != 0, first = d.off.empty();
-        long my_launched;
-        { std::lock_guard<std::mutex> lg(g->m); my_launched = g->launched; }
-        d.hurry = false;
-        d.th = std::thread([&d, g, bidx, bbuf, sp, slices, threads, annexb, first, idr, dev, my_launched]() {
-            x264gpu_set_device(dev);
-            x264gpu_level_index *ix = d.ix.empty() ? nullptr : d.ix.data();
-            if (batch_download(g, bidx, bbuf, d.mb.data(), d.lv.get(), d.err, ix)) return;
-            const long t0 = g->timing ? us_now() : 0;
-            {
-                // the slices are written once the group's next round is on the device (the callers need the cores to get it there), or when the picture is asked for
-                std::unique_lock<std::mutex> lk(g->m);
-                g->cv.wait_for(lk, std::chrono::seconds(30), [&] { return g->launched > my_launched || d.hurry.load() || g->closed; });
-            }
-            const long t1 = g->timing ? us_now() : 0;
-            const size_t before = d.off.size();
-            write_picture(d.out, &d.off, sp, slices, d.mb.data(), d.lv.get(), annexb, first, &d.stats, threads, ix);
-            if (g->timing) { const long t2 = us_now(); g->t_us[2] += t1 - t0; g->t_us[3] += t2 - t1; if (my_launched >= 1 && my_launched <= 64) g->r_sl[my_launched - 1] += t2 - t1; }
-            for (size_t i = before; i < d.off.size(); i++) d.types.push_back(idr ? 5 : 1);
-        });
-        d.valid = true;
+    int size;
+    if (deferred) size = bmode_defer(h, f, bbuf, pp_nal, pi_nal, pic_out);
+    else {
+        size = bmode_finish(h, f, h->h_mb.data(), h->h_lv.data(), pp_nal, pi_nal, pic_out);
         h->dpb.commit();
-        BPHASE(3);
-        h->t_b[4] += 1;
-        if (idr) h->idr_pic_id = (h->idr_pic_id + 1) & 0xffff;
-        h->coded_count++;
-        h->frame_no++;
-        h->defer_cur ^= 1;
-        return publish_deferred(h, h->defer[h->defer_cur], pp_nal, pi_nal, pic_out);          // the picture of the call before (0: none yet)
-    }
-    h->last_stats.skip = 0;
-    {
-        const size_t before = h->nal_off.size();
-        write_picture(h->out, &h->nal_off, sp, h->slices, h->h_mb.data(), h->h_lv.data(), p.b_annexb != 0, before == 0, &h->last_stats, h->cavlc_threads);
-        for (size_t i = before; i < h->nal_off.size(); i++) types.push_back(idr ? 5 : 1);
-    }
-    h->dpb.commit();
-    publish_nals(h, pp_nal, pi_nal, types);
-    for (size_t i = 0; i < h->nals.size(); i++) if (types[i] == 1 || types[i] == 5) h->nals[i].i_ref_idc = plan.nal_ref_idc;
-    if (pic_out) {
-        x264_picture_init(pic_out);
-        pic_out->i_type = idr ? X264_TYPE_IDR : pl.type == PIC_I ? X264_TYPE_I : pl.type == PIC_P ? X264_TYPE_P : pl.type == PIC_BREF ? X264_TYPE_BREF : X264_TYPE_B;
-        pic_out->b_keyframe = idr;
-        pic_out->i_pts = pl.e.pts;
-        // x264: the k-th coded picture's dts is the pts of display picture k - delay; the first `delay` ones are shifted back by the delay's duration
-        const long k = h->coded_count, delay = !h->bframes ? 0 : h->bpyramid ? 2 : 1;
-        const size_t np = h->all_pts.size();
-        if (k >= delay) pic_out->i_dts = h->all_pts[(size_t)(k - delay) < np ? (size_t)(k - delay) : np - 1];
-        else pic_out->i_dts = h->all_pts[(size_t)k < np ? (size_t)k : np - 1] - (h->all_pts[(size_t)delay < np ? (size_t)delay : np - 1] - h->all_pts[0]);
-        pic_out->img = pl.e.img;
-    }
-    if (h->pass1 || h->pass2) {
-        // x264_ratecontrol_end: the picture's line of the statistics file / the second pass' account of what was spent against the plan
-        const long total = (long)h->out.size() * 8;
-        long imb = 0, pmb = 0, smb = 0;
-        double aqsum = 0;
-        for (size_t i = 0; i < (size_t)h->nmb; i++) {
-            const x264gpu_mb &m = h->h_mb[i];
-            if (m.type <= X264GPU_MB_I16x16) imb++; else if (m.type == X264GPU_MB_P_SKIP || m.type == X264GPU_MB_B_SKIP) smb++; else pmb++;
-            aqsum += m.qp;
-        }
-        if (h->stat_file) {
-            const char t = idr ? 'I' : pl.type == PIC_I ? 'i' : pl.type == PIC_P ? 'P' : pl.type == PIC_BREF ? 'B' : 'b';
-            const long mv = h->last_stats.mv_bits, tex = h->last_stats.tex_bits, misc = total - mv - tex;
-            fprintf(h->stat_file, "in:%d out:%ld type:%c dur:%d cpbdur:%d q:%.2f aq:%.2f tex:%ld mv:%ld misc:%ld imb:%ld pmb:%ld smb:%ld d:%c ref:;\n", pl.e.frame, h->coded_count, t, 1, 1, qpf,
-                    aqsum / h->nmb, tex, mv, misc, imb, pmb, smb, h->last_direct_char);
-        }
-        if (h->pass2) {
-            h->p2_total_bits += (double)total;
-            if (pl.e.frame < (int)h->p2.size()) h->p2_expected_sum += p2_qscale2bits(h->p2[(size_t)pl.e.frame], p2_qp2qscale(qpf));
-        }
-    }
-    if (h->abr) {
-        // x264_ratecontrol_end: what the picture took moves the rate factor of the pictures to come (a B picture's quantiser is an offset of
-        // its neighbours': its bits count divided by pbratio)
-        const double bits = (double)h->out.size() * 8.0, pb = fabs(p.rc.f_pb_factor) > 0 ? fabs(p.rc.f_pb_factor) : 1.0;
-        const bool is_b = pl.type == PIC_B || pl.type == PIC_BREF;
-        h->rc.total_bits += bits;
-        h->rc.cplxr_sum += bits * rc_qp2qscale(rc_qp_avg_rc((float)qpf, h->mbw, h->mbh)) / (h->rc.last_rceq * (is_b ? pb : 1.0));
-        h->rc.wanted_bits_window += h->rc.bitrate / h->rc.fps;
     }
     BPHASE(3);
-    h->t_b[4] += 1;
-    if (idr) h->idr_pic_id = (h->idr_pic_id + 1) & 0xffff;
-    h->coded_count++;
-    h->frame_no++;
-    return (int)h->out.size();
+    return size;
 }
 
-// ---- several pictures of the session in flight (x264_t::Inflight) ----
+// ---- several pictures of the session in flight ----
 // issues the next picture of the coding order through a free launch context; false: nothing could be issued (no picture decided, no free context, no free slot)
 static bool inflight_issue(x264_t *h, bool flushing)
 {
-    const x264_param_t &p = h->param;
     int ci = -1;
     for (int i = 0; i < (int)h->lctx.size(); i++) if (!h->lctx[(size_t)i].busy) { ci = i; break; }
     if (ci < 0) return false;
@@ -2570,41 +2642,15 @@ static bool inflight_issue(x264_t *h, bool flushing)
     if (h->failed) return false;
     // the slots the pictures in flight write or read stay out of the choice of a destination
     unsigned avoid = 0;
-    for (const x264_t::Inflight &f : h->fl) avoid |= f.slots_used;
+    for (const x264_t::PicPlan &q : h->fl) avoid |= q.slots_used;
     h->dpb.avoid = avoid;
     if (!h->dpb.has_free_slot()) return false;
-    const x264_t::BPlanned pl = h->bcoding.front();
-    h->bcoding.pop_front();
-    int fc[16], ff[16], nf = 0;
-    const long coded_index = h->coded_count + (long)h->fl.size();          // this picture's place in the coding order
-    for (size_t i = 0; i < h->bcoding.size() && nf < 16 && h->bcoding[i].type == PIC_B; i++) { fc[nf] = (int)(coded_index + 1 + (long)i); ff[nf] = h->bcoding[i].e.frame; nf++; }
-    const DpbPlan plan = h->dpb.plan(pl.type, pl.e.frame, nf, fc, ff, pl.type == PIC_P && pl.e.w.on ? &pl.e.w : nullptr);
-    x264_t::Inflight f;
-    f.pl = pl; f.ctx = ci; f.nal_ref_idc = plan.nal_ref_idc;
-    x264gpu_pic pic = plan.pic;
-    double qpf = 0;
-    pic.qp = bmode_qp(h, pl, plan, &qpf);
-    pic.qpm = near_qpm(qpf, pic.qp);
-    h->rc_frames++;
-    if ((pl.type == PIC_B || pl.type == PIC_BREF) && h->direct_mode != 1) {
-        // x264 slice_header_init: temporal direct prediction only when the co-located picture's reference 0 is this picture's reference 0 (--direct auto runs serially)
-        const bool temporal = pic.nref[0] && pic.nref[1] && h->slot_l0ref0poc[pic.slot[1][0]] == plan.list_poc[0][0];
-        pic.direct_temporal = temporal; pic.direct_auto = 0;
-        h->dpb.set_direct(pic.direct_temporal, 0);
-    }
     x264_t::LaunchCtx &c = h->lctx[(size_t)ci];
-    if (h->st) {
-        const int dist0 = pic.nref[0] ? (pic.poc - plan.list_poc[0][0]) / 2 : 0, dist1 = pic.nref[1] ? (plan.list_poc[1][0] - pic.poc) / 2 : 0;
-        const int16_t *m0 = dist0 >= 1 && dist0 <= h->bframes + 1 ? x264gpu_slicetype_lowres_mvs(h->st, pl.e.slot, 0, dist0) : nullptr;
-        const int16_t *m1 = dist1 >= 1 && dist1 <= h->bframes + 1 ? x264gpu_slicetype_lowres_mvs(h->st, pl.e.slot, 1, dist1) : nullptr;
-        x264gpu_encoder_set_lowres_mvs(c.gpu, m0);
-        x264gpu_encoder_set_lowres_mvs1(c.gpu, m1);
-    }
-    const float *d_offsets = nullptr;
-    if (h->st && h->mbtree) d_offsets = pl.type == PIC_B ? h->q_aq[(size_t)pl.e.slot] : h->q_tree[(size_t)pl.e.slot];
-    else if (h->aq_mode >= 2 && h->aq_strength != 0.f) d_offsets = h->q_aq[(size_t)pl.e.slot];
-    x264gpu_encoder_set_mb_qp_offsets(c.gpu, d_offsets);
-    // behind the pictures in flight that write a slot this picture reads (its references; their side data lives with the slot)
+    x264_t::PicPlan f;
+    f.ctx = ci;
+    bmode_plan(h, f, c.gpu, h->coded_count + (long)h->fl.size(), false);
+    const x264gpu_pic &pic = f.pic;
+    // launch: on the context's stream, behind the pictures in flight that write a slot this picture reads (its references; their side data lives with the slot)
     f.slots_used = 1u << pic.dst;
     bool ok = true;
     for (int l = 0; l < 2 && ok; l++)
@@ -2617,22 +2663,11 @@ static bool inflight_issue(x264_t *h, bool flushing)
     // ... and behind the default stream: this picture's upload, its quantiser offsets and the lookahead's vectors were produced there
     ok = ok && x264gpu_event_record(h->ev_la, h->up_stream) == X264GPU_OK && x264gpu_stream_wait_event(c.stream, h->ev_la) == X264GPU_OK;
     if (ok && h->up_stream) ok = x264gpu_event_record(h->ev_la, nullptr) == X264GPU_OK && x264gpu_stream_wait_event(c.stream, h->ev_la) == X264GPU_OK;
-    ok = ok && x264gpu_encode_pictures(c.gpu, h->q_raw[(size_t)pl.e.slot], &pic, c.d_mb, c.d_lv, c.stream) == X264GPU_OK && x264gpu_event_record(c.ev, c.stream) == X264GPU_OK;
-    if (!ok) { xlog(&p, X264_LOG_ERROR, "x264_encoder_encode: GPU hot path failed: %s\n", x264gpu_last_error()); h->failed = true; return false; }
+    ok = ok && x264gpu_encode_pictures(c.gpu, h->q_raw[(size_t)f.pl.e.slot], &pic, c.d_mb, c.d_lv, c.stream) == X264GPU_OK && x264gpu_event_record(c.ev, c.stream) == X264GPU_OK;
+    if (!ok) { xlog(&h->param, X264_LOG_ERROR, "x264_encoder_encode: GPU hot path failed: %s\n", x264gpu_last_error()); h->failed = true; return false; }
     c.busy = true;
     h->slot_writer[pic.dst] = ci;
-    if (plan.nal_ref_idc) { h->slot_qp_rc[pic.dst] = rc_qp_avg_rc((float)qpf, h->mbw, h->mbh); h->slot_ptype[pic.dst] = pl.type; }
-    if (plan.nal_ref_idc) h->slot_l0ref0poc[pic.dst] = pic.nref[0] ? plan.list_poc[0][0] : INT_MIN;
-    f.direct_char = (pl.type == PIC_B || pl.type == PIC_BREF) ? (pic.direct_temporal ? 't' : 's') : '-';
-    f.pic = pic;
-    SliceParams sp = {};
-    sp.mbw = h->mbw; sp.mbh = h->mbh; sp.qp = pic.qp; sp.pic_init_qp = h->pic_init_qp; sp.log2_max_frame_num = h->log2_max_frame_num; sp.log2_max_poc_lsb = h->log2_max_poc_lsb;
-    sp.pps_id = p.i_sps_id; sp.num_ref_default = p.i_frame_reference; sp.num_ref1_default = 1;
-    sp.disable_deblock_idc = p.b_deblocking_filter ? 0 : 1; sp.alpha_off_div2 = p.i_deblocking_filter_alphac0; sp.beta_off_div2 = p.i_deblocking_filter_beta;
-    sp.transform8x8_mode = p.analyse.b_transform_8x8; sp.cabac = p.b_cabac; sp.slices_plain = h->slices_plain;
-    h->dpb.fill(sp);
     h->dpb.commit();
-    f.sp = sp;
     h->fl.push_back(f);
     return true;
 }
@@ -2640,55 +2675,20 @@ static bool inflight_issue(x264_t *h, bool flushing)
 // hands back the oldest picture in flight: waits for its launch context, downloads its records, writes its NAL units
 static int inflight_retire(x264_t *h, x264_nal_t **pp_nal, int *pi_nal, x264_picture_t *pic_out)
 {
-    const x264_param_t &p = h->param;
-    x264_t::Inflight f = h->fl.front();
+    x264_t::PicPlan f = h->fl.front();
     h->fl.pop_front();
     x264_t::LaunchCtx &c = h->lctx[(size_t)f.ctx];
     if (x264gpu_event_sync(c.ev) != X264GPU_OK ||
         x264gpu_memcpy_d2h(h->h_mb.data(), c.d_mb, h->h_mb.size() * sizeof(x264gpu_mb), c.stream) != X264GPU_OK ||
         x264gpu_memcpy_d2h(h->h_lv.data(), c.d_lv, h->h_lv.size() * sizeof(int16_t), c.stream) != X264GPU_OK) {
-        xlog(&p, X264_LOG_ERROR, "x264_encoder_encode: GPU hot path failed: %s\n", x264gpu_last_error());
+        xlog(&h->param, X264_LOG_ERROR, "x264_encoder_encode: GPU hot path failed: %s\n", x264gpu_last_error());
         h->failed = true;
         return -1;
     }
     c.busy = false;
     if (h->slot_writer[f.pic.dst] == f.ctx) h->slot_writer[f.pic.dst] = -1;
     h->last_retired_slot = f.pic.dst;
-    const x264_t::BPlanned &pl = f.pl;
-    h->last_direct_char = f.direct_char;
-    h->last_scenecut = pl.e.scenecut; h->last_qp = f.pic.qp; h->last_qpm = f.pic.qpm;
-    memcpy(h->last_costs, pl.e.costs, sizeof(pl.e.costs));
-    const bool idr = pl.type == PIC_IDR;
-    h->out.clear(); h->nal_off.clear();
-    std::vector<int> types;
-    if (p.b_aud) { h->nal_off.push_back(h->out.size()); types.push_back(9); write_aud(h->out, pl.type <= PIC_I ? 0 : pl.type == PIC_P ? 1 : 2, p.b_annexb != 0); }
-    if (idr && p.b_repeat_headers) { emit_sets(h, types, !h->sei_sent); h->sei_sent = 1; }
-    SliceParams sp = f.sp;
-    sp.idr_pic_id = h->idr_pic_id;
-    h->last_stats.skip = 0;
-    {
-        const size_t before = h->nal_off.size();
-        write_picture(h->out, &h->nal_off, sp, h->slices, h->h_mb.data(), h->h_lv.data(), p.b_annexb != 0, before == 0, &h->last_stats, h->cavlc_threads);
-        for (size_t i = before; i < h->nal_off.size(); i++) types.push_back(idr ? 5 : 1);
-    }
-    publish_nals(h, pp_nal, pi_nal, types);
-    for (size_t i = 0; i < h->nals.size(); i++) if (types[i] == 1 || types[i] == 5) h->nals[i].i_ref_idc = f.nal_ref_idc;
-    if (pic_out) {
-        x264_picture_init(pic_out);
-        pic_out->i_type = idr ? X264_TYPE_IDR : pl.type == PIC_I ? X264_TYPE_I : pl.type == PIC_P ? X264_TYPE_P : pl.type == PIC_BREF ? X264_TYPE_BREF : X264_TYPE_B;
-        pic_out->b_keyframe = idr;
-        pic_out->i_pts = pl.e.pts;
-        const long k = h->coded_count, delay = !h->bframes ? 0 : h->bpyramid ? 2 : 1;
-        const size_t np = h->all_pts.size();
-        if (k >= delay) pic_out->i_dts = h->all_pts[(size_t)(k - delay) < np ? (size_t)(k - delay) : np - 1];
-        else pic_out->i_dts = h->all_pts[(size_t)k < np ? (size_t)k : np - 1] - (h->all_pts[(size_t)delay < np ? (size_t)delay : np - 1] - h->all_pts[0]);
-        pic_out->img = pl.e.img;
-    }
-    h->t_b[4] += 1;
-    if (idr) h->idr_pic_id = (h->idr_pic_id + 1) & 0xffff;
-    h->coded_count++;
-    h->frame_no++;
-    return (int)h->out.size();
+    return bmode_finish(h, f, h->h_mb.data(), h->h_lv.data(), pp_nal, pi_nal, pic_out);
 }
 
 static int encode_bmode_inflight(x264_t *h, x264_nal_t **pp_nal, int *pi_nal, x264_picture_t *pic_out, bool flushing)
@@ -2862,23 +2862,46 @@ void x264_encoder_close(x264_t *h)
     delete h;
 }
 
+// what the slice-writing hooks are told of a picture, as SliceParams; the hooks without a DPB model add slice_type / frame_num / idr / num_ref, the others Dpb::fill
+static SliceParams slice_params_from_args(int mbw, int mbh, int qp, int pic_init_qp, int log2_max_frame_num, int idr_pic_id, int disable_deblock_idc, int num_ref_default,
+                                          int transform8x8_mode, int cabac)
+{
+    SliceParams sp = {};
+    sp.mbw = mbw; sp.mbh = mbh; sp.qp = qp; sp.pic_init_qp = pic_init_qp; sp.log2_max_frame_num = log2_max_frame_num; sp.idr_pic_id = idr_pic_id;
+    sp.num_ref_default = num_ref_default; sp.disable_deblock_idc = disable_deblock_idc; sp.transform8x8_mode = transform8x8_mode; sp.cabac = cabac;
+    return sp;
+}
+static void set_ip_slice(SliceParams &sp, int slice_type, int frame_num, int idr, int num_ref)
+{
+    sp.slice_type = slice_type; sp.frame_num = frame_num; sp.idr = idr; sp.nal_ref_idc = idr ? 3 : 2; sp.num_ref = num_ref;
+}
+// the bytes a hook wrote, into the caller's buffer: their count, -1 when they do not fit
+static int copy_out(const std::vector<uint8_t> &v, uint8_t *out, int cap)
+{
+    if ((int)v.size() > cap) return -1;
+    memcpy(out, v.data(), v.size());
+    return (int)v.size();
+}
+/* info[0..4] = frame_num, nal_ref_idc, n_mmco, reorder commands of list 0, of list 1 */
+static int plan_out(const DpbPlan &p, x264gpu_pic *pic_out, int *info)
+{
+    *pic_out = p.pic;
+    if (info) { info[0] = p.frame_num; info[1] = p.nal_ref_idc; info[2] = p.n_mmco; info[3] = p.reorder[0].n; info[4] = p.reorder[1].n; }
+    return 0;
+}
+
 /* test/diagnostic hooks (not part of the x264 API): entropy-code caller-supplied records, fetch the GPU recon */
 int x264host_write_slice(int mbw, int mbh, int slice_type, int qp, int pic_init_qp, int frame_num, int log2_max_frame_num,
                          int idr, int idr_pic_id, int disable_deblock_idc, int num_ref, int num_ref_default, int transform8x8_mode,
                          const x264gpu_mb *mbs, const int16_t *levels, uint8_t *out, int cap, int *skipped)
 {
-    SliceParams sp = {};
-    sp.mbw = mbw; sp.mbh = mbh; sp.slice_type = slice_type; sp.qp = qp; sp.pic_init_qp = pic_init_qp; sp.frame_num = frame_num;
-    sp.log2_max_frame_num = log2_max_frame_num; sp.idr = idr; sp.idr_pic_id = idr_pic_id; sp.nal_ref_idc = idr ? 3 : 2;
-    sp.num_ref = num_ref; sp.num_ref_default = num_ref_default;
-    sp.disable_deblock_idc = disable_deblock_idc; sp.transform8x8_mode = transform8x8_mode;
+    SliceParams sp = slice_params_from_args(mbw, mbh, qp, pic_init_qp, log2_max_frame_num, idr_pic_id, disable_deblock_idc, num_ref_default, transform8x8_mode, 0);
+    set_ip_slice(sp, slice_type, frame_num, idr, num_ref);
     std::vector<uint8_t> v;
     SliceStats stt = { 0 };
     write_slice(v, sp, mbs, levels, true, true, &stt, cavlc_threads_default(1));
     if (skipped) *skipped = stt.skip;
-    if ((int)v.size() > cap) return -1;
-    memcpy(out, v.data(), v.size());
-    return (int)v.size();
+    return copy_out(v, out, cap);
 }
 
 // a whole picture of `slices` slices through either writer (tests: multi-slice pictures)
@@ -2886,20 +2909,15 @@ int x264host_write_picture(int mbw, int mbh, int slice_type, int qp, int pic_ini
                            int idr, int idr_pic_id, int disable_deblock_idc, int num_ref, int num_ref_default, int transform8x8_mode, int cabac, int slices,
                            const x264gpu_mb *mbs, const int16_t *levels, uint8_t *out, int cap, int *skipped)
 {
-    SliceParams sp = {};
-    sp.mbw = mbw; sp.mbh = mbh; sp.slice_type = slice_type; sp.qp = qp; sp.pic_init_qp = pic_init_qp; sp.frame_num = frame_num;
-    sp.log2_max_frame_num = log2_max_frame_num; sp.idr = idr; sp.idr_pic_id = idr_pic_id; sp.nal_ref_idc = idr ? 3 : 2;
-    sp.num_ref = num_ref; sp.num_ref_default = num_ref_default;
-    sp.disable_deblock_idc = disable_deblock_idc; sp.transform8x8_mode = transform8x8_mode; sp.cabac = cabac;
+    SliceParams sp = slice_params_from_args(mbw, mbh, qp, pic_init_qp, log2_max_frame_num, idr_pic_id, disable_deblock_idc, num_ref_default, transform8x8_mode, cabac);
+    set_ip_slice(sp, slice_type, frame_num, idr, num_ref);
     sp.slices_plain = slices < 0;                 // -N: N slices as x264's --slices N codes them (filtered across), N: as its slice threads do
     if (slices < 0) slices = -slices;
     std::vector<uint8_t> v;
     SliceStats stt = { 0 };
     write_picture(v, nullptr, sp, slices, mbs, levels, true, true, &stt, 4);
     if (skipped) *skipped = stt.skip;
-    if ((int)v.size() > cap) return -1;
-    memcpy(out, v.data(), v.size());
-    return (int)v.size();
+    return copy_out(v, out, cap);
 }
 
 // the same through the CABAC writer (tests: records from the CPU checker -> bytes -> checker decoder)
@@ -2907,18 +2925,13 @@ int x264host_write_slice_cabac(int mbw, int mbh, int slice_type, int qp, int pic
                                int idr, int idr_pic_id, int disable_deblock_idc, int num_ref, int num_ref_default, int transform8x8_mode,
                                const x264gpu_mb *mbs, const int16_t *levels, uint8_t *out, int cap, int *skipped)
 {
-    SliceParams sp = {};
-    sp.mbw = mbw; sp.mbh = mbh; sp.slice_type = slice_type; sp.qp = qp; sp.pic_init_qp = pic_init_qp; sp.frame_num = frame_num;
-    sp.log2_max_frame_num = log2_max_frame_num; sp.idr = idr; sp.idr_pic_id = idr_pic_id; sp.nal_ref_idc = idr ? 3 : 2;
-    sp.num_ref = num_ref; sp.num_ref_default = num_ref_default;
-    sp.disable_deblock_idc = disable_deblock_idc; sp.transform8x8_mode = transform8x8_mode; sp.cabac = 1;
+    SliceParams sp = slice_params_from_args(mbw, mbh, qp, pic_init_qp, log2_max_frame_num, idr_pic_id, disable_deblock_idc, num_ref_default, transform8x8_mode, 1);
+    set_ip_slice(sp, slice_type, frame_num, idr, num_ref);
     std::vector<uint8_t> v;
     SliceStats stt = { 0 };
     write_slice(v, sp, mbs, levels, true, true, &stt, 1);
     if (skipped) *skipped = stt.skip;
-    if ((int)v.size() > cap) return -1;
-    memcpy(out, v.data(), v.size());
-    return (int)v.size();
+    return copy_out(v, out, cap);
 }
 
 int x264host_write_headers_cabac(int width, int height, int level_idc, int log2_max_frame_num, int pic_init_qp, int chroma_qp_offset,
@@ -2940,9 +2953,7 @@ int x264host_write_headers_cabac(int width, int height, int level_idc, int log2_
     write_sps(v, s, true);
     PpsParams pp = { 0, 0, cabac, num_ref, pic_init_qp, chroma_qp_offset, transform8x8_mode };
     write_pps(v, pp, true);
-    if ((int)v.size() > cap) return -1;
-    memcpy(out, v.data(), v.size());
-    return (int)v.size();
+    return copy_out(v, out, cap);
 }
 
 /* ---- tests: the DPB model (dpb.hpp) and a slice writer driven by it, for B-picture streams built from the CPU checker's records ---- */
@@ -2954,13 +2965,10 @@ void *x264host_dpb_new(int frame_reference, int bframes, int b_pyramid, int log2
 }
 void x264host_dpb_free(void *h) { delete (Dpb *)h; }
 int x264host_dpb_info(void *h, int *max_dpb, int *num_reorder) { Dpb *d = (Dpb *)h; *max_dpb = d->max_dpb; *num_reorder = d->num_reorder; return d->slots(); }
-/* info[0..7] = frame_num, nal_ref_idc, n_mmco, reorder commands of list 0, of list 1, ... */
 int x264host_dpb_plan(void *h, int type, int frame, int n_follow, const int *follow_coded, const int *follow_frame, x264gpu_pic *pic_out, int *info)
 {
     const DpbPlan &p = ((Dpb *)h)->plan(type, frame, n_follow, follow_coded, follow_frame);
-    *pic_out = p.pic;
-    if (info) { info[0] = p.frame_num; info[1] = p.nal_ref_idc; info[2] = p.n_mmco; info[3] = p.reorder[0].n; info[4] = p.reorder[1].n; }
-    return 0;
+    return plan_out(p, pic_out, info);
 }
 /* ... with a luma weight for reference 0 (x264_weights_analyse's result): w = { scale, denom, offset } */
 int x264host_dpb_plan_w(void *h, int type, int frame, int n_follow, const int *follow_coded, const int *follow_frame, const int *w, x264gpu_pic *pic_out, int *info)
@@ -2968,9 +2976,7 @@ int x264host_dpb_plan_w(void *h, int type, int frame, int n_follow, const int *f
     Dpb::LumaWeight lw;
     if (w) { lw.on = 1; lw.scale = w[0]; lw.denom = w[1]; lw.offset = w[2]; }
     const DpbPlan &p = ((Dpb *)h)->plan(type, frame, n_follow, follow_coded, follow_frame, w ? &lw : nullptr);
-    *pic_out = p.pic;
-    if (info) { info[0] = p.frame_num; info[1] = p.nal_ref_idc; info[2] = p.n_mmco; info[3] = p.reorder[0].n; info[4] = p.reorder[1].n; }
-    return 0;
+    return plan_out(p, pic_out, info);
 }
 /* ... and chroma weights beside it: w = { scale, denom, offset, chroma denom, Cb on, Cb scale, Cb offset, Cr on, Cr scale, Cr offset } */
 int x264host_dpb_plan_wc(void *h, int type, int frame, int n_follow, const int *follow_coded, const int *follow_frame, const int *w, x264gpu_pic *pic_out, int *info)
@@ -2979,9 +2985,7 @@ int x264host_dpb_plan_wc(void *h, int type, int frame, int n_follow, const int *
     lw.on = 1; lw.scale = w[0]; lw.denom = w[1]; lw.offset = w[2]; lw.cdenom = w[3];
     for (int c = 0; c < 2; c++) { lw.con[c] = w[4 + 3 * c]; lw.cscale[c] = w[5 + 3 * c]; lw.coffset[c] = w[6 + 3 * c]; }
     const DpbPlan &p = ((Dpb *)h)->plan(type, frame, n_follow, follow_coded, follow_frame, &lw);
-    *pic_out = p.pic;
-    if (info) { info[0] = p.frame_num; info[1] = p.nal_ref_idc; info[2] = p.n_mmco; info[3] = p.reorder[0].n; info[4] = p.reorder[1].n; }
-    return 0;
+    return plan_out(p, pic_out, info);
 }
 void x264host_dpb_commit(void *h) { ((Dpb *)h)->commit(); }
 void x264host_dpb_set_direct(void *h, int temporal, int auto_write) { ((Dpb *)h)->set_direct(temporal, auto_write); }
@@ -2989,28 +2993,22 @@ int x264host_write_slice_dpb(void *h, int mbw, int mbh, int qp, int pic_init_qp,
                              int disable_deblock_idc, int num_ref_default, int transform8x8_mode, const x264gpu_mb *mbs, const int16_t *levels,
                              uint8_t *out, int cap, int *skipped)
 {
-    SliceParams sp = {};
-    sp.mbw = mbw; sp.mbh = mbh; sp.qp = qp; sp.pic_init_qp = pic_init_qp; sp.log2_max_frame_num = log2_max_frame_num; sp.log2_max_poc_lsb = log2_max_poc_lsb;
-    sp.idr_pic_id = idr_pic_id; sp.num_ref_default = num_ref_default; sp.num_ref1_default = 1;
-    sp.disable_deblock_idc = disable_deblock_idc; sp.transform8x8_mode = transform8x8_mode; sp.cabac = 1;
+    SliceParams sp = slice_params_from_args(mbw, mbh, qp, pic_init_qp, log2_max_frame_num, idr_pic_id, disable_deblock_idc, num_ref_default, transform8x8_mode, 1);
+    sp.log2_max_poc_lsb = log2_max_poc_lsb;
     ((Dpb *)h)->fill(sp);
     std::vector<uint8_t> v;
     SliceStats stt = { 0 };
     write_slice(v, sp, mbs, levels, true, true, &stt, 1);
     if (skipped) *skipped = stt.skip;
-    if ((int)v.size() > cap) return -1;
-    memcpy(out, v.data(), v.size());
-    return (int)v.size();
+    return copy_out(v, out, cap);
 }
 // the same picture in `slices` slices (N: as x264's slice threads cut it, -N: as --slices N does)
 int x264host_write_picture_dpb(void *h, int mbw, int mbh, int qp, int pic_init_qp, int log2_max_frame_num, int log2_max_poc_lsb, int idr_pic_id,
                                int disable_deblock_idc, int num_ref_default, int transform8x8_mode, int slices, const x264gpu_mb *mbs, const int16_t *levels,
                                uint8_t *out, int cap, int *skipped)
 {
-    SliceParams sp = {};
-    sp.mbw = mbw; sp.mbh = mbh; sp.qp = qp; sp.pic_init_qp = pic_init_qp; sp.log2_max_frame_num = log2_max_frame_num; sp.log2_max_poc_lsb = log2_max_poc_lsb;
-    sp.idr_pic_id = idr_pic_id; sp.num_ref_default = num_ref_default; sp.num_ref1_default = 1;
-    sp.disable_deblock_idc = disable_deblock_idc; sp.transform8x8_mode = transform8x8_mode; sp.cabac = 1;
+    SliceParams sp = slice_params_from_args(mbw, mbh, qp, pic_init_qp, log2_max_frame_num, idr_pic_id, disable_deblock_idc, num_ref_default, transform8x8_mode, 1);
+    sp.log2_max_poc_lsb = log2_max_poc_lsb;
     sp.slices_plain = slices < 0;
     if (slices < 0) slices = -slices;
     ((Dpb *)h)->fill(sp);
@@ -3018,9 +3016,7 @@ int x264host_write_picture_dpb(void *h, int mbw, int mbh, int qp, int pic_init_q
     SliceStats stt = { 0 };
     write_picture(v, nullptr, sp, slices > 1 ? slices : 1, mbs, levels, true, true, &stt, 1);
     if (skipped) *skipped = stt.skip;
-    if ((int)v.size() > cap) return -1;
-    memcpy(out, v.data(), v.size());
-    return (int)v.size();
+    return copy_out(v, out, cap);
 }
 int x264host_write_headers_b(int width, int height, int level_idc, int log2_max_frame_num, int pic_init_qp, int chroma_qp_offset, uint32_t num_units_in_tick,
                              uint32_t time_scale, int num_ref_default, int transform8x8_mode, int cabac, int num_ref_frames, int log2_max_poc_lsb, int num_reorder,
@@ -3037,9 +3033,7 @@ int x264host_write_headers_b(int width, int height, int level_idc, int log2_max_
     PpsParams pp = { 0, 0, cabac, num_ref_default, pic_init_qp, chroma_qp_offset, transform8x8_mode };
     pp.weighted_bipred_idc = weighted_bipred_idc; pp.weighted_pred = weighted_pred;
     write_pps(v, pp, true);
-    if ((int)v.size() > cap) return -1;
-    memcpy(out, v.data(), v.size());
-    return (int)v.size();
+    return copy_out(v, out, cap);
 }
 
 /* device pointer of the encoder's input staging buffer: a tight I420 picture (Y w*h, U, V).  A picture whose plane[0]
