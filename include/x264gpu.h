@@ -329,6 +329,21 @@ int x264gpu_encoder_deblock_pictures(x264gpu_encoder *e, const uint8_t *d_i420, 
 int  x264gpu_encoder_get_recon(x264gpu_encoder *enc, int stream_idx, uint8_t *d_i420_out, void *stream);
 /* the same for the picture in DPB slot `slot` (x264gpu_encode_pictures sessions) */
 int  x264gpu_encoder_get_recon_slot(x264gpu_encoder *enc, int stream_idx, int slot, uint8_t *d_i420_out, void *stream);
+/* --psnr / --ssim ([x264-upstream] common/pixel.c pixel_ssd_wxh, pixel_ssim_wxh, ssim_end1; encoder/encoder.c encoder_frame_end), per picture pair a / b:
+ * ssd[p] = the exact sum of (a - b)^2 over plane p (Y, U, V).  SSIM, luma only: 4x4 blocks on the grid of origin (2, 2), zc = (w - 2) >> 2 by zr = (h - 2) >> 2 of
+ * them, each with s1 = sum a, s2 = sum b, ss = sum (a^2 + b^2), s12 = sum ab; a window = a 2x2 group of blocks (8x8 samples, step 4), ssim_cnt = (zc - 1) (zr - 1)
+ * of them; a window's value, in 32-bit integers and single floats: vars = ss * 64 - s1^2 - s2^2, covar = s12 * 64 - s1 s2,
+ * (float)(2 s1 s2 + 416) * (float)(2 covar + 235963) / ((float)(s1^2 + s2^2 + 416) * (float)(vars + 235963)); ssim_sum = their sum in double.
+ * Partial sums are added in a fixed order (no float atomics): the same inputs give the same bytes every run.  flags: which parts are computed, the others are 0. */
+typedef struct x264gpu_quality { uint64_t ssd[3]; double ssim_sum; uint32_t ssim_cnt, pad; } x264gpu_quality;   /* Y, U, V */
+#define X264GPU_QUALITY_PSNR 1
+#define X264GPU_QUALITY_SSIM 2
+/* primitive (tier 1): n pairs of tight I420 pictures (any alignment), d_out[n].  w, h even and >= 16, flags 1..3, else EINVAL */
+int x264gpu_picture_quality(const uint8_t *d_a, const uint8_t *d_b, int n, int w, int h, int flags, x264gpu_quality *d_out, void *stream);
+/* pipeline: per stream, the picture the LAST encode call through this launch context (encoder or view) coded, against the source that call ingested: the
+ * context's own source planes and the reconstruction in its DPB slot, compared where they lie over the visible width x height (the same device code as the
+ * primitive).  Queued on `stream` behind the encode call it needs no host synchronisation; d_out[streams].  EINVAL before any encode call */
+int x264gpu_encoder_quality(x264gpu_encoder *enc, int flags, x264gpu_quality *d_out /* [streams] */, void *stream);
 /* Per-stage device timing for bench.py (HIP events on the caller's stream, no host sync in the timed
  * region): profile_begin arms up to max_calls encode_frames calls; profile_end synchronises the stream
  * and returns, per stage, the summed milliseconds and the number of launches that ran. */

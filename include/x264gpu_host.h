@@ -53,6 +53,16 @@ int x264host_pass2_plan(x264_t *h, double *new_qscale, double *expected_bits, in
 int x264host_pictures_in_flight(x264_t *h);
 /* reconstructed picture of the last encoded frame as I420 (host memory) */
 int x264host_get_recon(x264_t *h, uint8_t *i420_out);
+/* --psnr / --ssim (analyse.b_psnr / b_ssim): the figures of the picture the last x264_encoder_encode call that returned one handed back, from the device's
+ * statistics (x264gpu_encoder_quality): psnr[4] = Y, U, V and the average over all samples, the mean SSIM window value of luma, the exact sums of squared
+ * differences; parts not asked for are 0.  -1: no picture yet, or the session runs without the flags (not asked for, GOP slots, no quality entry in the device library) */
+int x264host_last_quality(x264_t *h, double psnr[4] /* Y U V Avg */, double *ssim, uint64_t ssd[3]);
+/* the closing statistics as x264_encoder_close logs them at INFO level (one line per slice type with pictures, the SSIM line, the PSNR line), '\n' behind each;
+ * returns the length without the terminating 0 (the text is cut at cap - 1), -1 when the session runs without the flags */
+int x264host_quality_summary(x264_t *h, char *buf, int cap);
+/* x264_psnr: 100 when ssd / (255^2 n) <= 1e-10, else -10 log10 of it; x264_ssim: 100 when 1 - ssim <= 1e-10, else -10 log10(1 - ssim) */
+double x264host_psnr(double ssd, double n);
+double x264host_ssim_db(double ssim);
 
 #ifdef __cplusplus
 }

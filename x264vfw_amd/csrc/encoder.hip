@@ -11,6 +11,7 @@
 #include <stdlib.h>
 #include "k_deblock.hip.h"
 #include "cabac_layout.hip.h"
+#include "quality.hip.h"
 #include <math.h>
 #include <vector>
 #include <string.h>
@@ -63,6 +64,7 @@ struct x264gpu_encoder {
     int *sl_stat = nullptr, *sl_rerun = nullptr;     // --slices N: per (stream, slice) intra statistics of the speculative slice passes (EncK.sl_stat)
     unsigned long long *prof = nullptr;  // MB_PROF builds: phase counters of the last macroblock-loop launch
     int *wf_progress = nullptr;          // [streams][2][WFG_ROWS] row counters of the multi-workgroup wavefront kernels
+    void *qslab = nullptr;               // x264gpu_encoder_quality: the workgroup partials of the pass (allocated by the first call)
     // adaptive quantisation: per-macroblock quantisers and the per-quantiser tables (built when aq_mode != 0)
     uint8_t *mbqp = nullptr;
     const float *ext_off = nullptr;      // quantiser offsets handed in by the caller (lookahead), [streams][nmb] single floats
@@ -304,6 +306,7 @@ void x264gpu_encoder_destroy(x264gpu_encoder *e)
     (void)hipFree(e->direct_flags_base); (void)hipFree(e->dscore);
     for (int i = 0; i < 8; i++) (void)hipFree(e->mvr[i]);
     (void)hipFree(e->wf_progress);
+    (void)hipFree(e->qslab);
     (void)hipFree(e->tc);
     (void)hipFree(e->amvd);
     (void)hipFree(e->cab_out);
@@ -785,4 +788,20 @@ extern "C" int x264gpu_encoder_get_recon_slot(x264gpu_encoder *e, int stream_idx
     hipLaunchKernelGGL(k_get_recon, dim3((k.w + 255) / 256, k.h), dim3(256), 0, (hipStream_t)stream, l, c, k.rs, k.w, k.h, d_out);
     HIP_TRY(hipGetLastError());
     return X264GPU_OK;
+}
+
+// --psnr / --ssim: the picture this launch context coded last against the source it ingested for it, both where they lie (quality.hip); nothing is copied
+extern "C" int x264gpu_encoder_quality(x264gpu_encoder *e, int flags, x264gpu_quality *d_out, void *stream)
+{
+    ARG_TRY(e && d_out && flags >= 1 && flags <= 3 && e->have > 0);
+    const EncK &k = e->k;
+    ARG_TRY(k.w >= 16 && k.h >= 16 && !(k.w & 1) && !(k.h & 1));
+    if (!e->qslab) HIP_TRY(hipMalloc(&e->qslab, quality_slab_bytes(e->cfg.streams, k.w, k.h)));
+    QPlanes q;
+    q.a_y = e->fenc_y; q.a_c = e->fenc_uv; q.a_pitch_y = k.fency_bytes; q.a_pitch_c = k.fencuv_bytes; q.a_sy = q.a_sc = k.fs;
+    q.b_y = e->luma[e->last] + (size_t)PAD * k.rs + PAD; q.b_c = e->chroma[e->last] + (size_t)CPAD * k.rs + 2 * CPAD;
+    q.b_pitch_y = k.luma_bytes; q.b_pitch_c = k.cplane_bytes; q.b_sy = q.b_sc = k.rs;
+    q.a_voff = q.b_voff = 0;
+    q.w = k.w; q.h = k.h; q.step = 2;
+    return launch_quality(q, e->cfg.streams, flags, e->qslab, d_out, (hipStream_t)stream);
 }

@@ -7,6 +7,7 @@
 // pic_out->{i_type,b_keyframe,i_pts,i_dts} filled.  No CPU fallback: open fails without a GPU.
 #include "host.hpp"
 #include "dpb.hpp"
+#include "quality.hpp"
 #include <limits.h>
 #include <math.h>
 #include <stdio.h>
@@ -49,6 +50,10 @@ struct x264_t {
     std::vector<x264_nal_t> nals;
     std::vector<size_t> nal_off;
     SliceStats last_stats = { 0 };
+    // ---- --psnr / --ssim (host/quality.hpp): the session's figures; the device result of the picture coded last (one per launch context where there are several),
+    //      its host copies (two: the pipelined I / P session downloads one picture's while the one before is coded) ----
+    Quality ql;
+    x264gpu_quality *d_q = nullptr, hq[2] = {};
     // ---- lookahead-driven decisions (threads 1 only): scenecut and CRF, both fed by x264gpu_lookahead_frame_cost ----
     x264gpu_lookahead *la = nullptr;
     int32_t *d_la = nullptr;             // device: the four sums of the last picture
@@ -165,14 +170,15 @@ struct x264_t {
     struct Deferred { std::thread th; bool valid = false; std::atomic<bool> hurry{ false }; std::string err; std::vector<uint8_t> out; std::vector<size_t> off; std::vector<int> types; int nal_ref_idc = 0;
                       std::vector<x264gpu_mb> mb; std::vector<x264gpu_level_index> ix; std::unique_ptr<int16_t[]> lv; SliceStats stats = { 0 };      // (lv: never cleared — what is downloaded is what is read)
                       int i_type = 0, b_keyframe = 0; int64_t pts = 0, dts = 0; x264_image_t img;
-                      int qp = 0, scenecut = 0; float qpm = 0.f; int32_t costs[4] = { 0, 0, 0, 0 }; };      // the decision hooks' values of THIS picture (x264host_last_decision / _last_qpm)
+                      int qp = 0, scenecut = 0; float qpm = 0.f; int32_t costs[4] = { 0, 0, 0, 0 };
+                      x264gpu_quality q = {}; int q_type = 0, q_poc = 0; };      // --psnr / --ssim: the picture's statistics (downloaded with its records), slice type and POC      // the decision hooks' values of THIS picture (x264host_last_decision / _last_qpm)
     Deferred defer[2]; int defer_cur = 0;
     struct BPlanned { BEntry e; int type; };                                                                            // type: PIC_*
     // ---- several pictures of ONE session in flight (threads-1 sessions on the DPB model; x264's frame threads overlap pictures too).  The b pictures of a mini-GOP, the
     //      B reference between two finished P pictures and the next P picture share only FINISHED references: each is issued through a launch context of its own (the
     //      encoder or a view of it: own scratch, the shared DPB) on a stream of its own, behind the events of the pictures it references, into a slot no picture in
     //      flight reads or writes; pictures are planned, issued and handed back in coding order, so the stream is the serial session's byte for byte ----
-    struct LaunchCtx { x264gpu_encoder *gpu = nullptr; void *stream = nullptr, *ev = nullptr; x264gpu_mb *d_mb = nullptr; int16_t *d_lv = nullptr; bool busy = false; };
+    struct LaunchCtx { x264gpu_encoder *gpu = nullptr; void *stream = nullptr, *ev = nullptr; x264gpu_mb *d_mb = nullptr; int16_t *d_lv = nullptr; bool busy = false; x264gpu_quality *d_q = nullptr; };
     // a picture of a session on the DPB model between plan and finish: what was decided for it, what the device is told, what the slice writer is told;
     // with several pictures in flight also its launch context and the DPB slots it reads or writes
     struct PicPlan { BPlanned pl; x264gpu_pic pic; SliceParams sp; int nal_ref_idc = 0; double qpf = 0; const float *d_offsets = nullptr; bool direct_auto_write = false; char direct_char = '-';
@@ -221,6 +227,7 @@ struct BatchGroup {
     // the levels leave the device packed (x264gpu_pack_levels behind every round, in place): a member downloads its records, its index and the part of its levels that is kept
     // (~10 % at medium; dense, 2048 members x 7 MB a round were what the first rounds waited for: fresh pages of the download buffers, 15 GB a round over the link)
     bool pack = false; x264gpu_level_index *d_ix = nullptr, *d_ix2 = nullptr;
+    int qflags = 0; x264gpu_quality *d_q = nullptr, *d_q2 = nullptr;          // --psnr / --ssim of the members (all alike): one statistic per stream behind every round, two buffers as d_mb / d_mb2
     std::vector<void *> up_streams;          // the members' uploads: a handful of streams dealt round-robin (a stream per member was 0.7 ms to create and 0.6 ms to destroy, x 2048, serialised in the runtime)
     long ev_round[2] = { 0, 0 }, ev_done[2] = { 0, 0 }; bool ev_waiting[2] = { false, false }; std::string ev_err;      // per buffer pair: the round recorded behind it (1-based), the last one known complete, a member is waiting for the event
     long launched = 0;            // rounds whose kernels have been issued: the helper threads start entropy coding round k once round k + 1 is on the device (or when asked to hurry),
@@ -267,6 +274,8 @@ static void batch_destroy(BatchGroup *g)
     if (g->d_lv2) x264gpu_free(g->d_lv2);
     if (g->d_ix) x264gpu_free(g->d_ix);
     if (g->d_ix2) x264gpu_free(g->d_ix2);
+    if (g->d_q) x264gpu_free(g->d_q);
+    if (g->d_q2) x264gpu_free(g->d_q2);
     if (g->cs) x264gpu_stream_sync(g->cs);
     if (g->dl_stream) x264gpu_stream_destroy(g->dl_stream);
     for (void *st : g->up_streams) { x264gpu_stream_sync(st); x264gpu_stream_destroy(st); }
@@ -275,7 +284,7 @@ static void batch_destroy(BatchGroup *g)
     delete g;
 }
 // -> the group and the stream index of the caller, or nullptr (setup failed: last error set)
-static BatchGroup *batch_join(const x264gpu_config &cfg1, int N, size_t insz, size_t nmb, int *idx)
+static BatchGroup *batch_join(const x264gpu_config &cfg1, int N, size_t insz, size_t nmb, int qflags, int *idx)
 {
     std::lock_guard<std::mutex> lk(g_batch_mu);
     int dev = 0;
@@ -283,7 +292,7 @@ static BatchGroup *batch_join(const x264gpu_config &cfg1, int N, size_t insz, si
     for (BatchGroup *g : g_batch_groups) {
         x264gpu_config a = g->cfg, b = cfg1;
         a.streams = b.streams = 0;
-        if (g->N == N && g->device == dev && g->joined < N && !g->closed && !memcmp(&a, &b, sizeof(a))) {
+        if (g->N == N && g->device == dev && g->joined < N && !g->closed && g->qflags == qflags && !memcmp(&a, &b, sizeof(a))) {
             std::lock_guard<std::mutex> lg(g->m);
             *idx = g->joined++; g->active++; g->member[(size_t)*idx] = 1;
             g->cv.notify_all();
@@ -291,12 +300,13 @@ static BatchGroup *batch_join(const x264gpu_config &cfg1, int N, size_t insz, si
         }
     }
     BatchGroup *g = new BatchGroup();
-    g->cfg = cfg1; g->cfg.streams = N; g->N = N; g->device = dev; g->insz = insz; g->nmb = nmb;
+    g->cfg = cfg1; g->cfg.streams = N; g->N = N; g->device = dev; g->insz = insz; g->nmb = nmb; g->qflags = qflags;
     g->member.assign((size_t)N, 0); g->arrived.assign((size_t)N, 0); g->pics.resize((size_t)N);
     if (x264gpu_encoder_create(&g->gpu, &g->cfg) != X264GPU_OK ||
         x264gpu_malloc((void **)&g->d_in, (size_t)N * insz) != X264GPU_OK ||
         x264gpu_malloc((void **)&g->d_mb, (size_t)N * nmb * sizeof(x264gpu_mb)) != X264GPU_OK ||
-        x264gpu_malloc((void **)&g->d_lv, (size_t)N * nmb * X264GPU_MB_LEVELS * sizeof(int16_t)) != X264GPU_OK) { batch_destroy(g); return nullptr; }
+        x264gpu_malloc((void **)&g->d_lv, (size_t)N * nmb * X264GPU_MB_LEVELS * sizeof(int16_t)) != X264GPU_OK ||
+        (qflags && (x264gpu_malloc((void **)&g->d_q, (size_t)N * sizeof(x264gpu_quality)) != X264GPU_OK || x264gpu_malloc((void **)&g->d_q2, (size_t)N * sizeof(x264gpu_quality)) != X264GPU_OK))) { batch_destroy(g); return nullptr; }
     {
         const char *oe = getenv("X264GPU_BATCH_OVERLAP");
         if (!(oe && oe[0] == '0') && !getenv("X264GPU_DUMP_RECORDS") &&
@@ -327,6 +337,7 @@ static void batch_run_round(BatchGroup *g, std::unique_lock<std::mutex> &lk)
         }
         const bool second = g->overlap && (g->round & 1);          // the output buffers of this round (the other pair may still be downloading)
         if (!g->round_rc && x264gpu_encode_pictures(g->gpu, g->d_in, g->pics.data(), second ? g->d_mb2 : g->d_mb, second ? g->d_lv2 : g->d_lv, g->async ? g->cs : nullptr) != X264GPU_OK) { g->round_rc = -1; g->err = x264gpu_last_error(); }
+        if (!g->round_rc && g->qflags && quality_queue(g->gpu, g->qflags, second ? g->d_q2 : g->d_q, g->async ? g->cs : nullptr) != X264GPU_OK) { g->round_rc = -1; g->err = x264gpu_last_error(); }
         if (!g->round_rc && g->pack && x264gpu_pack_levels(second ? g->d_lv2 : g->d_lv, g->N, (int)g->nmb, second ? g->d_ix2 : g->d_ix, nullptr, g->cs) != X264GPU_OK) { g->round_rc = -1; g->err = x264gpu_last_error(); }
         if (!g->round_rc && g->async) {
             // queued, not awaited: the event behind the round is what its downloads wait for (batch_download)
@@ -376,7 +387,7 @@ static int batch_submit(BatchGroup *g, int s, const uint8_t *d_src, const x264gp
 }
 // stream s' records and levels of the round whose results lie in buffer pair `buf`
 // (h_ix: the group packs its levels — the member's index; h_lv then receives only the kept groups)
-static int batch_download(BatchGroup *g, int s, int buf, x264gpu_mb *h_mb, int16_t *h_lv, std::string &err, x264gpu_level_index *h_ix = nullptr)
+static int batch_download(BatchGroup *g, int s, int buf, x264gpu_mb *h_mb, int16_t *h_lv, std::string &err, x264gpu_level_index *h_ix = nullptr, x264gpu_quality *h_q = nullptr)
 {
     const x264gpu_mb *dm = buf ? g->d_mb2 : g->d_mb; const int16_t *dl = buf ? g->d_lv2 : g->d_lv;
     // (async groups: the members' downloads are dealt to the group's sixteen upload / download streams)
@@ -408,6 +419,7 @@ static int batch_download(BatchGroup *g, int s, int buf, x264gpu_mb *h_mb, int16
     const long rnd = g->async ? g->ev_round[buf ? 1 : 0] - 1 : 0;
     struct Acc { BatchGroup *g; long t0, t1, rnd; ~Acc() { if (g->timing) { const long t2 = us_now(); g->t_us[0] += t1 - t0; g->t_us[1] += t2 - t1;
         if (rnd >= 0 && rnd < 64) { g->r_dl[rnd] += t2 - t1; long f = g->r_dl_first[rnd].load(); while ((f == 0 || t2 < f) && !g->r_dl_first[rnd].compare_exchange_weak(f, t2)) {} long l = g->r_dl_last[rnd].load(); while (t2 > l && !g->r_dl_last[rnd].compare_exchange_weak(l, t2)) {} } } } } acc{ g, t0, t1, rnd };
+    if (g->qflags && h_q && x264gpu_memcpy_d2h(h_q, (buf ? g->d_q2 : g->d_q) + s, sizeof(x264gpu_quality), st) != X264GPU_OK) { err = x264gpu_last_error(); return -1; }
     if (g->pack) {
         if (!h_ix) { err = "X264GPU_BATCH: the group's levels are packed"; return -1; }
         const x264gpu_level_index *di = (buf ? g->d_ix2 : g->d_ix) + (size_t)s * g->nmb;
@@ -927,6 +939,7 @@ static bool open_device(x264_t *h)
     x264gpu_config cfg = open_device_config(h);
     const size_t insz = (size_t)p.i_width * p.i_height * 3 / 2;
     (void)x264gpu_get_device(&h->device);
+    h->ql.open(p, h->G > 1);          // --psnr / --ssim: from here on h->ql.flags says whether the session computes them
     bool ok_setup = x264gpu_malloc((void **)&h->d_in, insz) == X264GPU_OK;
     if (ok_setup && h->G > 1) {
         // GOP-parallel: the slots are dealt to the devices (X264GPU_DEVICES caps how many are used)
@@ -949,23 +962,25 @@ static bool open_device(x264_t *h)
         if (!ok_setup) { xlog(&p, X264_LOG_ERROR, "GPU encoder setup failed: %s\n", err.c_str()); return false; }
         if (D > 1) xlog(&p, X264_LOG_INFO, "GOP slots on %d devices (%d + ... per device)\n", D, h->devs[0].nsl);
     } else if (ok_setup && h->batch_n) {
-        h->batch = batch_join(cfg, h->batch_n, insz, (size_t)h->nmb, &h->batch_idx);
+        h->batch = batch_join(cfg, h->batch_n, insz, (size_t)h->nmb, h->ql.flags, &h->batch_idx);
         ok_setup = h->batch != nullptr;
         if (ok_setup && h->batch->async && !h->batch->up_streams.empty()) h->up_stream = h->batch->up_streams[(size_t)h->batch_idx % h->batch->up_streams.size()];      // (the group's; without one the uploads wait on the default stream: slower, not wrong)
         if (ok_setup) xlog(&p, X264_LOG_INFO, "X264GPU_BATCH: stream %d of a batch of %d sessions%s\n", h->batch_idx, h->batch_n, h->batch->async ? " (rounds queued: uploads overlap the device)" : "");
     } else if (ok_setup) {
         ok_setup = x264gpu_encoder_create(&h->gpu, &cfg) == X264GPU_OK &&
                    x264gpu_malloc((void **)&h->d_mb, (size_t)h->nmb * sizeof(x264gpu_mb)) == X264GPU_OK &&
-                   x264gpu_malloc((void **)&h->d_lv, (size_t)h->nmb * X264GPU_MB_LEVELS * sizeof(int16_t)) == X264GPU_OK;
+                   x264gpu_malloc((void **)&h->d_lv, (size_t)h->nmb * X264GPU_MB_LEVELS * sizeof(int16_t)) == X264GPU_OK &&
+                   (!h->ql.flags || x264gpu_malloc((void **)&h->d_q, sizeof(x264gpu_quality)) == X264GPU_OK);
         if (ok_setup && h->inflight > 1) {
             h->lctx.resize((size_t)h->inflight);
             ok_setup = x264gpu_event_create(&h->ev_la) == X264GPU_OK;
             for (int i = 0; i < h->inflight && ok_setup; i++) {
                 x264_t::LaunchCtx &c = h->lctx[(size_t)i];
-                if (i == 0) { c.gpu = h->gpu; c.d_mb = h->d_mb; c.d_lv = h->d_lv; }
+                if (i == 0) { c.gpu = h->gpu; c.d_mb = h->d_mb; c.d_lv = h->d_lv; c.d_q = h->d_q; }
                 else ok_setup = x264gpu_encoder_create_view(&c.gpu, h->gpu) == X264GPU_OK &&
                                 x264gpu_malloc((void **)&c.d_mb, (size_t)h->nmb * sizeof(x264gpu_mb)) == X264GPU_OK &&
-                                x264gpu_malloc((void **)&c.d_lv, (size_t)h->nmb * X264GPU_MB_LEVELS * sizeof(int16_t)) == X264GPU_OK;
+                                x264gpu_malloc((void **)&c.d_lv, (size_t)h->nmb * X264GPU_MB_LEVELS * sizeof(int16_t)) == X264GPU_OK &&
+                                (!h->ql.flags || x264gpu_malloc((void **)&c.d_q, sizeof(x264gpu_quality)) == X264GPU_OK);
                 ok_setup = ok_setup && x264gpu_stream_create(&c.stream) == X264GPU_OK && x264gpu_event_create(&c.ev) == X264GPU_OK;
             }
             if (ok_setup) xlog(&p, X264_LOG_INFO, "up to %d pictures of the session in flight (pictures that share only finished references; the stream is the serial one)\n", h->inflight);
@@ -1581,8 +1596,10 @@ static int gpu_stage(x264_t *h, size_t idx, int buf, bool async)
     const uint8_t *src = h->q_raw[(size_t)e.slot];
     x264gpu_mb *hmb = buf ? h->h_mb2.data() : h->h_mb.data();
     int16_t *hlv = buf ? h->h_lv2.data() : h->h_lv.data();
-    auto run = [h, src, st, hmb, hlv]() {
+    x264gpu_quality *hq = &h->hq[buf];
+    auto run = [h, src, st, hmb, hlv, hq]() {
         h->gpu_rc = x264gpu_encode_frames(h->gpu, src, st, h->d_mb, h->d_lv, nullptr) != X264GPU_OK ||
+                    (h->ql.flags && (h->ql.queue(h->gpu, h->d_q, nullptr) != X264GPU_OK || x264gpu_memcpy_d2h(hq, h->d_q, sizeof(*hq), nullptr) != X264GPU_OK)) ||
                     x264gpu_memcpy_d2h(hmb, h->d_mb, h->h_mb.size() * sizeof(x264gpu_mb), nullptr) != X264GPU_OK ||
                     x264gpu_memcpy_d2h(hlv, h->d_lv, h->h_lv.size() * sizeof(int16_t), nullptr) != X264GPU_OK ? -1 : 0;
         if (h->gpu_rc) h->gpu_err = x264gpu_last_error();          // the error text lives in this thread's buffer: keep it for the caller's log
@@ -1628,6 +1645,7 @@ static int encode_queued(x264_t *h, x264_nal_t **pp_nal, int *pi_nal, x264_pictu
     write_slices(h->out, h->nal_off, types, sp, h->slices, hmb, hlv, p.b_annexb != 0, idr, &h->last_stats, h->cavlc_threads);
     publish_nals(h, pp_nal, pi_nal, types);
     fill_pic_out(pic_out, x264_type_of(type), idr, e.pts, e.pts, &e.img);
+    if (h->ql.flags) h->ql.frame_end(p, h->hq[e.buf], st == X264GPU_SLICE_P ? 1 : 0, mean_mb_qp(hmb, (size_t)h->nmb), 2 * h->frames_since_idr, h->out.size());
     if (idr) h->idr_pic_id = (h->idr_pic_id + 1) & 0xffff;
     h->frame_num = (h->frame_num + 1) & ((1 << h->log2_max_frame_num) - 1);
     if (h->abr) {
@@ -2450,6 +2468,7 @@ static void bmode_count(x264_t *h, bool idr)
 
 // finish: the picture's NAL units from its downloaded records, pic_out, what the rate control learns from its size (x264_ratecontrol_end: 2-pass and ABR sessions,
 // which always run serially), the counters; returns the bytes of the NAL units
+static int quality_type(int pic_type) { return pic_type == PIC_IDR || pic_type == PIC_I ? 0 : pic_type == PIC_P ? 1 : 2; }
 static int bmode_finish(x264_t *h, x264_t::PicPlan &f, const x264gpu_mb *mbs, const int16_t *levels, x264_nal_t **pp_nal, int *pi_nal, x264_picture_t *pic_out)
 {
     const x264_param_t &p = h->param;
@@ -2462,6 +2481,7 @@ static int bmode_finish(x264_t *h, x264_t::PicPlan &f, const x264gpu_mb *mbs, co
     publish_nals(h, pp_nal, pi_nal, types);
     for (size_t i = 0; i < h->nals.size(); i++) if (types[i] == 1 || types[i] == 5) h->nals[i].i_ref_idc = f.nal_ref_idc;
     fill_pic_out(pic_out, x264_type_of(pl.type), idr, pl.e.pts, coded_dts(h, h->coded_count), &pl.e.img);
+    if (h->ql.flags) h->ql.frame_end(p, h->hq[0], quality_type(pl.type), mean_mb_qp(mbs, (size_t)h->nmb), f.pic.poc, h->out.size());          // (h->hq[0]: downloaded with the records)
     if (h->pass1 || h->pass2) {
         // x264_ratecontrol_end: the picture's line of the statistics file / the second pass' account of what was spent against the plan
         const long total = (long)h->out.size() * 8;
@@ -2515,6 +2535,7 @@ static int publish_deferred(x264_t *h, x264_t::Deferred &d, x264_nal_t **pp_nal,
     publish_nals(h, pp_nal, pi_nal, d.types);
     for (size_t i = 0; i < h->nals.size(); i++) if (d.types[i] == 1 || d.types[i] == 5) h->nals[i].i_ref_idc = d.nal_ref_idc;
     fill_pic_out(pic_out, d.i_type, d.b_keyframe, d.pts, d.dts, &d.img);
+    if (h->ql.flags) h->ql.frame_end(h->param, d.q, d.q_type, mean_mb_qp(d.mb.data(), d.mb.size()), d.q_poc, h->out.size());
     return (int)h->out.size();
 }
 
@@ -2538,6 +2559,7 @@ static int bmode_defer(x264_t *h, x264_t::PicPlan &f, int bbuf, x264_nal_t **pp_
     if (!d.lv) { xlog(&p, X264_LOG_ERROR, "x264_encoder_encode: out of memory (download buffers)\n"); h->failed = true; return -1; }
     d.i_type = x264_type_of(pl.type); d.b_keyframe = idr; d.pts = pl.e.pts; d.img = pl.e.img;
     d.qp = f.pic.qp; d.qpm = f.pic.qpm; d.scenecut = pl.e.scenecut; memcpy(d.costs, pl.e.costs, sizeof(d.costs));
+    d.q_type = quality_type(pl.type); d.q_poc = f.pic.poc;
     if (h->abr || h->pass1 || h->pass2) { xlog(&p, X264_LOG_ERROR, "x264_encoder_encode: a batched session cannot run rate control that reads the coded sizes\n"); h->failed = true; return -1; }
     d.dts = coded_dts(h, h->coded_count);
     BatchGroup *g = h->batch;
@@ -2550,7 +2572,7 @@ static int bmode_defer(x264_t *h, x264_t::PicPlan &f, int bbuf, x264_nal_t **pp_
     d.th = std::thread([&d, g, bidx, bbuf, sp, slices, threads, annexb, idr, dev, my_launched]() {
         x264gpu_set_device(dev);
         x264gpu_level_index *ix = d.ix.empty() ? nullptr : d.ix.data();
-        if (batch_download(g, bidx, bbuf, d.mb.data(), d.lv.get(), d.err, ix)) return;
+        if (batch_download(g, bidx, bbuf, d.mb.data(), d.lv.get(), d.err, ix, &d.q)) return;
         const long t0 = g->timing ? us_now() : 0;
         {
             // the slices are written once the group's next round is on the device (the callers need the cores to get it there), or when the picture is asked for
@@ -2587,13 +2609,14 @@ static int encode_bmode(x264_t *h, x264_nal_t **pp_nal, int *pi_nal, x264_pictur
     if (h->batch) {
         std::string berr;
         if (batch_submit(h->batch, h->batch_idx, d_src, f.pic, &bbuf, berr) ||
-            (!deferred && batch_download(h->batch, h->batch_idx, bbuf, h->h_mb.data(), h->h_lv.data(), berr))) {
+            (!deferred && batch_download(h->batch, h->batch_idx, bbuf, h->h_mb.data(), h->h_lv.data(), berr, nullptr, &h->hq[0]))) {
             xlog(&p, X264_LOG_ERROR, "x264_encoder_encode: GPU hot path failed: %s\n", berr.c_str());
             h->failed = true;
             return -1;
         }
     } else
-    if (x264gpu_encode_pictures(h->gpu, d_src, &f.pic, h->d_mb, h->d_lv, nullptr) != X264GPU_OK || (getenv("X264GPU_HOST_TIMING") && (x264gpu_stream_sync(nullptr), BPHASE(1), false)) ||
+    if (x264gpu_encode_pictures(h->gpu, d_src, &f.pic, h->d_mb, h->d_lv, nullptr) != X264GPU_OK || (h->ql.flags && h->ql.queue(h->gpu, h->d_q, nullptr) != X264GPU_OK) ||
+        (getenv("X264GPU_HOST_TIMING") && (x264gpu_stream_sync(nullptr), BPHASE(1), false)) || (h->ql.flags && x264gpu_memcpy_d2h(&h->hq[0], h->d_q, sizeof(h->hq[0]), nullptr) != X264GPU_OK) ||
         x264gpu_memcpy_d2h(h->h_mb.data(), h->d_mb, h->h_mb.size() * sizeof(x264gpu_mb), nullptr) != X264GPU_OK ||
         x264gpu_memcpy_d2h(h->h_lv.data(), h->d_lv, h->h_lv.size() * sizeof(int16_t), nullptr) != X264GPU_OK) {
         xlog(&p, X264_LOG_ERROR, "x264_encoder_encode: GPU hot path failed: %s\n", x264gpu_last_error());
@@ -2663,7 +2686,8 @@ static bool inflight_issue(x264_t *h, bool flushing)
     // ... and behind the default stream: this picture's upload, its quantiser offsets and the lookahead's vectors were produced there
     ok = ok && x264gpu_event_record(h->ev_la, h->up_stream) == X264GPU_OK && x264gpu_stream_wait_event(c.stream, h->ev_la) == X264GPU_OK;
     if (ok && h->up_stream) ok = x264gpu_event_record(h->ev_la, nullptr) == X264GPU_OK && x264gpu_stream_wait_event(c.stream, h->ev_la) == X264GPU_OK;
-    ok = ok && x264gpu_encode_pictures(c.gpu, h->q_raw[(size_t)f.pl.e.slot], &pic, c.d_mb, c.d_lv, c.stream) == X264GPU_OK && x264gpu_event_record(c.ev, c.stream) == X264GPU_OK;
+    ok = ok && x264gpu_encode_pictures(c.gpu, h->q_raw[(size_t)f.pl.e.slot], &pic, c.d_mb, c.d_lv, c.stream) == X264GPU_OK &&
+         (!h->ql.flags || h->ql.queue(c.gpu, c.d_q, c.stream) == X264GPU_OK) && x264gpu_event_record(c.ev, c.stream) == X264GPU_OK;
     if (!ok) { xlog(&h->param, X264_LOG_ERROR, "x264_encoder_encode: GPU hot path failed: %s\n", x264gpu_last_error()); h->failed = true; return false; }
     c.busy = true;
     h->slot_writer[pic.dst] = ci;
@@ -2678,7 +2702,7 @@ static int inflight_retire(x264_t *h, x264_nal_t **pp_nal, int *pi_nal, x264_pic
     x264_t::PicPlan f = h->fl.front();
     h->fl.pop_front();
     x264_t::LaunchCtx &c = h->lctx[(size_t)f.ctx];
-    if (x264gpu_event_sync(c.ev) != X264GPU_OK ||
+    if (x264gpu_event_sync(c.ev) != X264GPU_OK || (h->ql.flags && x264gpu_memcpy_d2h(&h->hq[0], c.d_q, sizeof(h->hq[0]), c.stream) != X264GPU_OK) ||
         x264gpu_memcpy_d2h(h->h_mb.data(), c.d_mb, h->h_mb.size() * sizeof(x264gpu_mb), c.stream) != X264GPU_OK ||
         x264gpu_memcpy_d2h(h->h_lv.data(), c.d_lv, h->h_lv.size() * sizeof(int16_t), c.stream) != X264GPU_OK) {
         xlog(&h->param, X264_LOG_ERROR, "x264_encoder_encode: GPU hot path failed: %s\n", x264gpu_last_error());
@@ -2825,6 +2849,7 @@ void x264_encoder_close(x264_t *h)
     if (getenv("X264GPU_HOST_TIMING") && h->t_b[4] > 0)
         fprintf(stderr, "x264gpu host timing (DPB model), ms per picture over %.0f pictures: slice-type analysis %.2f, GPU hot path %.2f, download %.2f, entropy coding %.2f\n", h->t_b[4],
                 1e3 * h->t_b[0] / h->t_b[4], 1e3 * h->t_b[1] / h->t_b[4], 1e3 * h->t_b[2] / h->t_b[4], 1e3 * h->t_b[3] / h->t_b[4]);
+    h->ql.log_summary(h->param);
     if (h->stat_file) {
         fclose(h->stat_file); h->stat_file = nullptr;
         const std::string out = h->param.rc.psz_stat_out ? h->param.rc.psz_stat_out : "";
@@ -2836,7 +2861,7 @@ void x264_encoder_close(x264_t *h)
         x264_t::LaunchCtx &c = h->lctx[i];
         if (c.stream) { x264gpu_stream_sync(c.stream); x264gpu_stream_destroy(c.stream); }
         if (c.ev) x264gpu_event_destroy(c.ev);
-        if (i > 0) { if (c.gpu) x264gpu_encoder_destroy(c.gpu); if (c.d_mb) x264gpu_free(c.d_mb); if (c.d_lv) x264gpu_free(c.d_lv); }
+        if (i > 0) { if (c.gpu) x264gpu_encoder_destroy(c.gpu); if (c.d_mb) x264gpu_free(c.d_mb); if (c.d_lv) x264gpu_free(c.d_lv); if (c.d_q) x264gpu_free(c.d_q); }
     }
     h->lctx.clear();
     if (h->ev_la) x264gpu_event_destroy(h->ev_la);
@@ -2846,6 +2871,7 @@ void x264_encoder_close(x264_t *h)
     if (h->d_in) x264gpu_free(h->d_in);
     if (h->d_mb) x264gpu_free(h->d_mb);
     if (h->d_lv) x264gpu_free(h->d_lv);
+    if (h->d_q) x264gpu_free(h->d_q);
     for (auto &dc : h->devs) {
         if (h->devs.size() > 1) (void)x264gpu_set_device(dc.dev);
         if (dc.gpu) x264gpu_encoder_destroy(dc.gpu);
@@ -3061,6 +3087,24 @@ int x264host_pass2_plan(x264_t *h, double *new_qscale, double *expected_bits, in
 float x264host_last_qpm(x264_t *h) { return h ? h->last_qpm : 0.f; }
 
 int x264host_pictures_in_flight(x264_t *h) { return h ? h->inflight : 0; }
+
+int x264host_last_quality(x264_t *h, double psnr[4], double *ssim, uint64_t ssd[3])
+{
+    if (!h || !h->ql.flags || !h->ql.have_last) return -1;
+    if (psnr) memcpy(psnr, h->ql.last_psnr, sizeof(h->ql.last_psnr));
+    if (ssim) *ssim = h->ql.last_ssim;
+    if (ssd) memcpy(ssd, h->ql.last_ssd, sizeof(h->ql.last_ssd));
+    return 0;
+}
+
+int x264host_quality_summary(x264_t *h, char *buf, int cap)
+{
+    if (!h || !h->ql.flags || !buf || cap < 1) return -1;
+    const std::string s = h->ql.summary(h->param);
+    const size_t n = s.size() < (size_t)cap - 1 ? s.size() : (size_t)cap - 1;
+    memcpy(buf, s.data(), n); buf[n] = 0;
+    return (int)n;
+}
 
 int x264host_get_recon(x264_t *h, uint8_t *i420_out)
 {

@@ -113,6 +113,10 @@ _sig("x264host_last_decision", _i, [C.c_void_p, C.POINTER(_i), C.POINTER(_i), C.
 _sig("x264host_last_qpm", C.c_float, [C.c_void_p])
 _sig("x264host_pictures_in_flight", C.c_int, [C.c_void_p])
 _sig("x264host_pass2_plan", _i, [C.c_void_p, C.c_void_p, C.c_void_p, _i])
+_sig("x264host_last_quality", _i, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint64)])
+_sig("x264host_quality_summary", _i, [C.c_void_p, C.c_char_p, _i])
+_sig("x264host_psnr", C.c_double, [C.c_double, C.c_double])
+_sig("x264host_ssim_db", C.c_double, [C.c_double])
 LEVELS = (Level * 21).in_dll(H, "x264_levels")
 
 X264_CSP_I420, X264_RC_CQP, X264_RC_CRF, X264_RC_ABR = 1, 0, 1, 2

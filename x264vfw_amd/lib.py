@@ -56,6 +56,11 @@ class Pic(C.Structure):
                 ("slot", (C.c_int8 * 8) * 2), ("wl0", W * 8), ("blind_dupe", C.c_int), ("qpm", C.c_float), ("wc0", WC * 8), ("direct_temporal", C.c_int), ("direct_auto", C.c_int)]
 
 
+class Quality(C.Structure):
+    """Mirror of struct x264gpu_quality (40 bytes)."""
+    _fields_ = [("ssd", C.c_uint64 * 3), ("ssim_sum", C.c_double), ("ssim_cnt", C.c_uint32), ("pad", C.c_uint32)]
+
+
 def make_pic(slice_type, qp, poc, dst, keep, l0=(), l1=()):
     p = Pic(slice_type=slice_type, qp=qp, poc=poc, dst=dst, keep=keep, blind_dupe=-1)
     p.nref[0], p.nref[1] = len(l0), len(l1)
@@ -112,6 +117,8 @@ _SIGS = {
     "x264gpu_encode_pictures": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "x264gpu_pack_levels": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
     "x264gpu_encoder_get_recon_slot": (_i, [_vp, _i, _i, _vp, _vp]),
+    "x264gpu_picture_quality": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "x264gpu_encoder_quality": (_i, [_vp, _i, _vp, _vp]),
     "x264gpu_encoder_stage_count": (_i, []),
     "x264gpu_encoder_stage_name": (C.c_char_p, [_i]),
     "x264gpu_encoder_profile_begin": (_i, [_vp, _i]),
