@@ -46,6 +46,7 @@ def main():
     preset = (opts.pop("preset", None) or "medium").encode()
     want_log = int(opts.pop("log", 0) or 0)
     want_plan = int(opts.pop("plan", 0) or 0)          # a second pass: also print the quantiser scales init_pass2 planned (x264host_pass2_plan)
+    want_decisions = int(opts.pop("decisions", 0) or 0)          # per output picture: [quantiser, scenecut flag, the four lookahead costs, float quantiser] (x264host_last_decision / _last_qpm)
     frames = make_frames(w, h, n, seed, scene_len, static, fade)
     p = HL.Param()
     assert H.x264_param_default_preset(C.byref(p), preset, None) == 0
@@ -73,7 +74,7 @@ def main():
     assert H.x264_picture_alloc(C.byref(pic), HL.X264_CSP_I420, w, h) == 0
     nal, nn = C.POINTER(HL.Nal)(), C.c_int()
     planes = [(w * h, 0), (w * h // 4, w * h), (w * h // 4, w * h * 5 // 4)]
-    stream, recs = b"", []
+    stream, recs, decisions = b"", [], []
     first_out = None
 
     def take(size):
@@ -81,6 +82,10 @@ def main():
         if size > 0:
             stream += C.string_at(nal[0].p_payload, size)
             recs.append((out.i_type, out.i_pts, out.i_dts, out.b_keyframe, size))
+            if want_decisions:
+                qp, sc, costs = C.c_int(), C.c_int(), (C.c_int32 * 4)()
+                assert H.x264host_last_decision(h_, C.byref(qp), C.byref(sc), costs) == 0
+                decisions.append([qp.value, sc.value, list(costs), float(H.x264host_last_qpm(h_))])
     for i, f in enumerate(frames):
         for pl, (sz, off) in enumerate(planes):
             C.memmove(pic.img.plane[pl], f[off:off + sz].ctypes.data, sz)
@@ -99,7 +104,7 @@ def main():
     print(json.dumps({"recs": recs, "bframes": eff.i_bframe, "pyramid": eff.i_bframe_pyramid, "badapt": eff.i_bframe_adaptive, "weightb": eff.analyse.b_weighted_bipred,
                       "weightp": eff.analyse.i_weighted_pred, "mbtree": eff.rc.b_mb_tree, "subme": eff.analyse.i_subpel_refine, "cabac": eff.b_cabac, "direct": eff.analyse.i_direct_mv_pred, "first_output_after": first_out, "log": log,
                       "rc_method": eff.rc.i_rc_method, "stat_read": eff.rc.b_stat_read, "stat_write": eff.rc.b_stat_write, "inter": eff.analyse.inter, "refs": eff.i_frame_reference,
-                      "me": eff.analyse.i_me_method, "trellis": eff.analyse.i_trellis, "mv_range": eff.analyse.i_mv_range, "me_range": eff.analyse.i_me_range, "plan": plan}))
+                      "me": eff.analyse.i_me_method, "trellis": eff.analyse.i_trellis, "mv_range": eff.analyse.i_mv_range, "me_range": eff.analyse.i_me_range, "plan": plan, "decisions": decisions}))
 
 
 if __name__ == "__main__":

@@ -1,5 +1,5 @@
 """CPU: the session's DECISIONS — picture types (scenecut, --b-adapt 1, keyint / min-keyint, closed GOPs) and single-pass CRF quantisers (I / P from the
-frame costs, B from its nearest references) — as host/encoder.cpp takes them on the stand-in device, against oracle/decide.py, a second restatement of
+frame costs, B from its nearest references) — as host/encoder.cpp and host/ratecontrol.cpp take them on the stand-in device, against oracle/decide.py, a second restatement of
 the same parts of libx264 written independently of the host code (numpy / plain python over the CPU checker's frame costs).  Reference consumers of
 these decisions: codec.c:1786 (every ICM_COMPRESS), config.c:1504-1514 (CRF / ABR rate control of the dialog)."""
 import ctypes as C
@@ -19,7 +19,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(HERE), "oracle"))
 import decide as D  # noqa: E402
 
 
-def host_session(tmp_path, w, h, n, seed, opts, offsets=False):
+def host_session(tmp_path, w, h, n, seed, opts, offsets=False, records=True):
     subprocess.check_call(["make", "-s", "-C", os.path.join(HERE, "stub")])
     dump = tmp_path / "dump"
     dump.mkdir(exist_ok=True)
@@ -28,6 +28,8 @@ def host_session(tmp_path, w, h, n, seed, opts, offsets=False):
                        capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     info = json.loads(r.stdout.strip().splitlines()[-1])
+    if not records:          # (sessions off the DPB model dump no picture records)
+        return info
     pics, offs = [], []
     nmb = ((w + 15) // 16) * ((h + 15) // 16)
     for k in range(n):
@@ -189,6 +191,31 @@ def test_single_pass_abr_equals_the_twin(tmp_path, opts, kw):
     for k, ((f, t, qp, qpf, _off), pic) in enumerate(zip(twin, pics)):
         assert pic.qp == qp and pic.qpm == np.float32(qpf), f"coded picture {k} (display {f}, type {t}): quantiser {pic.qp} / {pic.qpm} vs the twin's {qp} / {qpf}"
     assert len({pic.qp for pic in pics}) >= 4          # the rate control moves
+
+
+@pytest.mark.parametrize("opts,kw", [
+    (["crf=24"], dict(crf=24.0)),
+    (["bitrate=300", "keyint=40"], dict(bitrate=300, keyint=40)),
+    (["crf=24", "zones=4,9,q=31/14,20,b=0.5"], dict(crf=24.0, zones=[(4, 9, 'q', 31), (14, 20, 'b', 0.5)])),
+])
+def test_ip_session_quantisers_equal_the_twin(tmp_path, opts, kw):
+    """sessions without B pictures and without --weightp 2 run the I / P picture path, not the DPB model: their CRF / ABR quantisers (zones included) against the twin's
+    RateControl.nonb / .end, fed the lookahead costs the session saw (x264host_last_decision) and, for ABR, the sizes its pictures really had: the integer quantiser and
+    the float quantiser handed to the device (x264host_last_qpm) equal the twin's picture by picture"""
+    w, h, n, seed, scene = 176, 144, 24, 5, 12
+    info = host_session(tmp_path, w, h, n, seed, opts + ["bframes=0", "weightp=0", "no-mbtree", "rc-lookahead=0", f"scene_len={scene}", "decisions=1"], records=False)
+    assert info["bframes"] == 0 and info["weightp"] == 0 and not info["mbtree"]
+    assert [r[1] for r in info["recs"]] == list(range(n)) and len(info["decisions"]) == n          # display order, one picture a call
+    assert sum(r[0] in (1, 2) for r in info["recs"]) == 2, [r[0] for r in info["recs"]]             # the first picture and the scene change
+    rc = D.RateControl(D.Params((w + 15) // 16, (h + 15) // 16, bframes=0, **kw))
+    qps = []
+    for f, (r, (qp, _sc, costs, qpm)) in enumerate(zip(info["recs"], info["decisions"])):
+        is_i = r[0] in (1, 2)          # X264_TYPE_IDR / _I
+        want, wantf = rc.nonb(is_i, costs[0] if is_i else costs[1], f)
+        assert qp == want and np.float32(qpm) == np.float32(wantf), f"picture {f} (type {r[0]}): quantiser {qp} / {qpm} vs the twin's {want} / {wantf}"
+        rc.end(r[4] * 8.0, False, wantf)
+        qps.append(qp)
+    assert len(set(qps)) >= 3, qps          # the rate control moves
 
 
 def test_second_pass_plan_equals_the_twin(tmp_path):

@@ -519,7 +519,7 @@ def test_b_pictures_into_the_containers(gpu, tmp_path, ext):
 
 def test_two_pass_through_the_driver(gpu, tmp_path):
     """encoding type 4 of the config dialog (codec.c:1516-1533): pass 1 returns no stream and writes the statistics file, pass 2 reads it and hits the
-    requested bitrate within 5 % (x264 ratecontrol.c init_pass2 restated in host/encoder.cpp)"""
+    requested bitrate within 5 % (x264 ratecontrol.c init_pass2 restated in host/ratecontrol.cpp)"""
     w, h, nfr, kbps = 176, 144, 240, 300
     frames = synth_frames(w, h, nfr, seed=11, scene_len=53)
     stats = tmp_path / "vfw.stats"

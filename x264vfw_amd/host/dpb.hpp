@@ -20,8 +20,6 @@
 
 namespace x264host {
 
-enum { PIC_IDR = 0, PIC_I = 1, PIC_P = 2, PIC_BREF = 3, PIC_B = 4 };
-
 struct DpbPlan {
     x264gpu_pic pic;             // slice type, POC, destination slot, the reference lists as slots (qp left to the caller)
     int type;                    // PIC_*

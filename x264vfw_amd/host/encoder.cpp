@@ -8,8 +8,10 @@
 #include "host.hpp"
 #include "dpb.hpp"
 #include "quality.hpp"
+#include "ratecontrol.hpp"
 #include <limits.h>
 #include <math.h>
+#include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -58,21 +60,11 @@ struct x264_t {
     x264gpu_lookahead *la = nullptr;
     int32_t *d_la = nullptr;             // device: the four sums of the last picture
     int keyint_min = 25;
-    bool crf = false;
-    struct {                             // [x264-upstream] encoder/ratecontrol.c, the CRF branch of rate_estimate_qscale (restated from memory)
-        double rate_factor_constant = 1, qcompress = 0.6, ip_factor = 1.4, ip_offset = 0, dur_ratio = 1;
-        double cplxsum = 0, cplxcount = 0, accum_p_qp = 0, accum_p_norm = 0, lmin = 0, lmax = 0;
-        double last_qscale_for[2] = { 0, 0 };       // [0] I, [1] P
-        int last_non_b_is_i = 1;
-        // single-pass ABR (--bitrate): the 1-pass branch of rate_estimate_qscale + the bookkeeping of x264_ratecontrol_end
-        double bitrate = 0, fps = 25, cplxr_sum = 0, wanted_bits_window = 0, abr_buffer = 0, total_bits = 0, last_rceq = 1, lstep = 1.3195;
-        double qpa_last = 0;                        // quantiser of the picture whose size arrives next (ratecontrol_end)
-    } rc;
-    bool abr = false;
+    RateControl rc;                      // host/ratecontrol.hpp: which rate control the session runs, every picture's quantiser
     double t_b[5] = { 0, 0, 0, 0, 0 };          // ... sessions on the DPB model: slice-type analysis, GPU hot path, download, entropy coding, pictures
     double t_phase[6] = { 0, 0, 0, 0, 0, 0 };   // X264GPU_HOST_TIMING=1: seconds in copy-in, upload + lookahead, GPU, download, entropy coding, calls
     // ---- lookahead queue (threads 1): pictures wait here rc-lookahead deep when the macroblock-tree needs to see what follows them ----
-    struct QEntry { int64_t pts; int slot; int type; int scenecut; int32_t costs[4]; x264_image_t img; int qp; int buf; bool launched; float qpm = 0.f; };      // type: 0 P, 1 I, 2 IDR; qpm: the float quantiser handed to the device (0: none); qp / buf / launched: set by gpu_stage
+    struct QEntry { int64_t pts; int slot; int type; int scenecut; int32_t costs[4]; x264_image_t img; int qp; int buf; bool launched; float qpm = 0.f; double qpf = 0; };      // type: 0 P, 1 I, 2 IDR; qpm: the float quantiser handed to the device (0: none), qpf: the rate control's; qp / buf / launched: set by gpu_stage
     std::deque<QEntry> queue;
     int L = 0, Q = 1;                    // pictures held back; ring slots (L + 1)
     std::vector<uint8_t *> q_raw;        // device: source pictures (slot 0 is d_in when nothing is held back: zero-copy input)
@@ -89,12 +81,9 @@ struct x264_t {
     bool pipeline = false;
     std::thread gpu_thread;
     int gpu_rc = 0;                      // result of the GPU stage in flight
-    int rc_frames = 0;                   // pictures that went through rate control (frames_done of rc_pick_qp)
     int device = 0;
     std::vector<float> gop_qpm;          // ... and its float quantiser (x264 rc->qpm)
     std::vector<int8_t> gop_qp;          // GOP-parallel CRF: the quantiser of every ring picture (slot * keyint + position), decided on arrival
-    struct Zone { int start, end; bool force_qp; int qp; float bitrate_factor; };      // x264_zone_t: pictures start..end (display order) at quantiser qp, or at bitrate_factor times their bits
-    std::vector<Zone> zones;
     float last_qpm = 0.f;                // ... and its float quantiser as the device got it (x264 rc->qpm; 0 = the integer one)
     int last_qp = 0, last_scenecut = 0;  // diagnostics: quantiser and scenecut flag of the last coded picture
     int32_t last_costs[4] = { 0, 0, 0, 0 };
@@ -189,21 +178,9 @@ struct x264_t {
     std::deque<BPlanned> bcoding;
     std::vector<int64_t> all_pts;        // every pts seen, in display order (the dts delay line)
     long coded_count = 0;
-    double slot_qp_rc[8] = { 0 };        // CRF: the quantiser (float) every kept picture was given, by DPB slot (x264 f_qp_avg_rc)
-    int slot_ptype[8] = { 0 };           // ... and its picture type
     // --direct temporal / auto (x264 h->stat.i_direct_score, frame->i_poc_l0ref0): 1 spatial, 2 temporal, 3 auto; the running skip-probe counts of
     // temporal [0] / spatial [1] prediction; the POC behind reference 0 of list 0 of every kept picture (INT_MIN: it had none)
     int direct_mode = 1, direct_score[2] = { 0, 0 }, slot_l0ref0poc[8] = { 0 };
-    // 2-pass (x264 ratecontrol.c; the driver's encoding type 4, codec.c:1516-1541): pass 1 appends one line per coded picture to the statistics file;
-    // pass 2 reads them — picture types, bits split into texture / vectors / the rest, the quantiser they were coded at — and spreads the requested
-    // size over the pictures (init_pass2), then follows the plan with feedback (rate_estimate_qscale's 2-pass branch)
-    struct Pass2Entry { char type = 'P'; int in = 0, out = 0, icount = 0, kept_as_ref = 1; double qp = 0, qscale = 0, new_qscale = 0, blurred = 0, expected_bits = 0, dur = 1;
-                        long tex = 0, mv = 0, misc = 0; };
-    bool pass1 = false, pass2 = false;
-    FILE *stat_file = nullptr;
-    std::vector<Pass2Entry> p2;                       // by display index ("in:")
-    std::vector<int> p2_out;                          // coding order -> display index
-    double p2_expected_sum = 0, p2_total_bits = 0, p2_final_bits = 0, p2_abr_buffer = 0;
     char last_direct_char = '-';
 };
 
@@ -465,14 +442,7 @@ static void batch_leave(BatchGroup *g, int s)
     if (last) batch_destroy(g);
 }
 
-// [x264-upstream] encoder/ratecontrol.c qp2qscale / qscale2qp: single floats (powf / log2f), as x264 has them
-static inline double rc_qp2qscale(double qp) { return (double)(0.85f * powf(2.0f, ((float)qp - 12.0f) / 6.0f)); }
-static inline double rc_qscale2qp(double qscale) { return (double)(12.0f + 6.0f * log2f((float)qscale / 0.85f)); }
-static inline double FL(double v) { return (double)(float)v; }          // an assignment to one of x264's float variables
-// fdec->f_qp_avg_rc as x264 arrives at it: rc->qpa_rc (a float) gathers qpm * mb_width row by row (x264_ratecontrol_mb), x264_ratecontrol_end divides by the macroblock count
-static inline double rc_qp_avg_rc(float qpm, int mbw, int mbh) { float a = 0.f; for (int y = 0; y < mbh; y++) a += qpm * mbw; return (double)(a / (float)(mbw * mbh)); }
-
-static void xlog(const x264_param_t *p, int level, const char *fmt, ...)
+void x264host::xlog(const x264_param_t *p, int level, const char *fmt, ...)
 {
     if (!p->pf_log || level > p->i_log_level) return;
     va_list ap;
@@ -481,46 +451,6 @@ static void xlog(const x264_param_t *p, int level, const char *fmt, ...)
     va_end(ap);
 }
 
-static int clampi(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
-// get_zone ([x264-upstream] encoder/ratecontrol.c): the LAST zone that holds the picture (display index) wins
-static const x264_t::Zone *get_zone(const x264_t *h, int frame)
-{
-    for (size_t i = h->zones.size(); i-- > 0;) if (frame >= h->zones[i].start && frame <= h->zones[i].end) return &h->zones[i];
-    return nullptr;
-}
-// parse_zones / parse_zone: "<start>,<end>,q=<int>" or "<start>,<end>,b=<float>", zones separated by '/'.  (x264 also lets a zone carry other options after
-// the first; those reconfigure the encoder for the zone's pictures and are not implemented: said in the log, the zone keeps its quantiser part)
-static void parse_zones(x264_t *h, const char *str)
-{
-    if (!str || !*str) return;
-    std::string all(str);
-    size_t pos = 0;
-    while (pos <= all.size()) {
-        const size_t e = all.find('/', pos);
-        const std::string z = all.substr(pos, e == std::string::npos ? std::string::npos : e - pos);
-        pos = e == std::string::npos ? all.size() + 1 : e + 1;
-        if (z.empty()) continue;
-        x264_t::Zone zn = { 0, 0, false, 0, 1.f };
-        int len = 0;
-        if (sscanf(z.c_str(), "%d,%d,q=%d%n", &zn.start, &zn.end, &zn.qp, &len) >= 3) zn.force_qp = true;
-        else if (sscanf(z.c_str(), "%d,%d,b=%f%n", &zn.start, &zn.end, &zn.bitrate_factor, &len) >= 3) zn.force_qp = false;
-        else if (sscanf(z.c_str(), "%d,%d%n", &zn.start, &zn.end, &len) >= 2) zn.bitrate_factor = 1.f;
-        else { xlog(&h->param, X264_LOG_ERROR, "invalid zone: \"%s\"\n", z.c_str()); continue; }
-        if (zn.start > zn.end) { xlog(&h->param, X264_LOG_ERROR, "invalid zone: start=%d end=%d\n", zn.start, zn.end); continue; }
-        if (!zn.force_qp && zn.bitrate_factor <= 0) { xlog(&h->param, X264_LOG_ERROR, "invalid zone: bitrate_factor=%f\n", zn.bitrate_factor); continue; }
-        if ((size_t)len < z.size()) xlog(&h->param, X264_LOG_WARNING, "zone %d,%d: per-zone encoder options (\"%s\") are not implemented in the MI355X path: the zone keeps its quantiser / bitrate part only\n", zn.start, zn.end, z.c_str() + len);
-        h->zones.push_back(zn);
-    }
-}
-// x264_ratecontrol_start, constant quantiser: a zone shifts the picture's quantiser by (its qp - the P quantiser), or by -6 log2f(bitrate factor)
-static int cqp_zone(const x264_t *h, const x264_t::Zone &z, int q)
-{
-    float qf = (float)q;
-    if (z.force_qp) qf += (float)(z.qp - h->qp_p); else qf -= 6.f * log2f(z.bitrate_factor);
-    const float lo = (float)h->param.rc.i_qp_min, hi = (float)(h->param.rc.i_qp_max < 51 ? h->param.rc.i_qp_max : 51);
-    qf = qf < lo ? lo : qf > hi ? hi : qf;
-    return clampi((int)(qf + 0.5f), 0, 51);
-}
 
 // threads that entropy-code row bands of ONE slice (write_slice): X264GPU_CAVLC_THREADS overrides `dflt`
 static int cavlc_threads_default(int dflt)
@@ -661,9 +591,6 @@ static void fill_pic_out(x264_picture_t *pic_out, int i_type, bool keyframe, int
 }
 
 extern "C" {
-static bool p2_load(x264_t *h, const char *path);
-static bool p2_init(x264_t *h);
-
 // ---- x264_encoder_open, step by step (each step logs what it changes or why it fails; a failed step leaves the teardown to x264_encoder_close) ----
 static int psy_rd_q8(const x264_param_t &p) { return p.analyse.i_subpel_refine >= 6 ? (int)(p.analyse.f_psy_rd * 256.0f + 0.5f) : 0; }      // h->mb.i_psy_rd
 
@@ -805,29 +732,30 @@ static void open_modes(x264_t *h)
 static void open_quantisers(x264_t *h)
 {
     x264_param_t &p = h->param;
+    RateControl &rc = h->rc;
     // rate control: constant QP (X264_RC_CQP, codec.c:1498-1502) and single-pass CRF without AQ / mbtree (codec.c:1504-1507, the
     // driver's default session) when one GOP is in flight; ABR and CRF under --threads > 1 map to their nominal quantiser
     int qp = p.rc.i_rc_method == X264_RC_CQP ? p.rc.i_qp_constant : p.rc.i_rc_method == X264_RC_CRF ? (int)(p.rc.f_rf_constant + 0.5f) : 26;
-    h->crf = p.rc.i_rc_method == X264_RC_CRF && p.rc.f_rf_constant >= 1.0f;       // also under --threads G: its quantisers follow from the lookahead costs alone
+    rc.crf = p.rc.i_rc_method == X264_RC_CRF && p.rc.f_rf_constant >= 1.0f;       // also under --threads G: its quantisers follow from the lookahead costs alone
     // 2-pass: the second pass plans every picture's quantiser from the first pass' statistics; sessions on the DPB model (B pictures or --weightp 2)
-    h->pass2 = p.rc.b_stat_read && p.rc.i_rc_method == X264_RC_ABR && p.rc.i_bitrate > 0 && p.i_threads <= 1 && h->dpbmode && p.rc.psz_stat_in && !getenv("X264GPU_BATCH");
-    h->pass1 = p.rc.b_stat_write && !p.rc.b_stat_read && p.i_threads <= 1 && h->dpbmode && p.rc.psz_stat_out && !getenv("X264GPU_BATCH");
-    if ((p.rc.b_stat_read && !h->pass2) || (p.rc.b_stat_write && !p.rc.b_stat_read && !h->pass1)) {
+    rc.pass2 = p.rc.b_stat_read && p.rc.i_rc_method == X264_RC_ABR && p.rc.i_bitrate > 0 && p.i_threads <= 1 && h->dpbmode && p.rc.psz_stat_in && !getenv("X264GPU_BATCH");
+    rc.pass1 = p.rc.b_stat_write && !p.rc.b_stat_read && p.i_threads <= 1 && h->dpbmode && p.rc.psz_stat_out && !getenv("X264GPU_BATCH");
+    if ((p.rc.b_stat_read && !rc.pass2) || (p.rc.b_stat_write && !p.rc.b_stat_read && !rc.pass1)) {
         // a pass whose statistics cannot be honoured keeps its rate control: it runs as the single-pass session of the same method (ABR at i_bitrate
         // for the driver's multipass encodes, codec.c:1509-1527), as every pass did before 2-pass existed here — not at a constant quantiser
         xlog(&p, X264_LOG_WARNING, "2-pass statistics need threads 1 and B-frames or weightp 2 (the DPB-model path) in the MI355X path: this pass runs as a single pass without them\n");
-        if (!h->pass2) p.rc.b_stat_read = 0;
-        if (!h->pass1) p.rc.b_stat_write = 0;
+        if (!rc.pass2) p.rc.b_stat_read = 0;
+        if (!rc.pass1) p.rc.b_stat_write = 0;
     }
-    h->abr = p.rc.i_rc_method == X264_RC_ABR && p.i_threads <= 1 && p.rc.i_bitrate > 0 && !p.rc.b_stat_read;      // single pass, no VBV
-    if (p.rc.b_stat_write && p.rc.b_stat_read && !h->pass2) xlog(&p, X264_LOG_INFO, "this pass runs without the statistics: they stay as the first pass wrote them\n");
-    if (p.rc.i_rc_method != X264_RC_CQP && !h->crf && !h->abr && !h->pass2) xlog(&p, X264_LOG_WARNING, "this rate control mode is not implemented yet (ABR with --threads > 1): constant qp %d\n", qp);
+    rc.abr = p.rc.i_rc_method == X264_RC_ABR && p.i_threads <= 1 && p.rc.i_bitrate > 0 && !p.rc.b_stat_read;      // single pass, no VBV
+    if (p.rc.b_stat_write && p.rc.b_stat_read && !rc.pass2) xlog(&p, X264_LOG_INFO, "this pass runs without the statistics: they stay as the first pass wrote them\n");
+    if (p.rc.i_rc_method != X264_RC_CQP && !rc.by_cost() && !rc.pass2) xlog(&p, X264_LOG_WARNING, "this rate control mode is not implemented yet (ABR with --threads > 1): constant qp %d\n", qp);
     if (qp < 1) { xlog(&p, X264_LOG_WARNING, "lossless is not supported: qp 1\n"); qp = 1; }
-    if (!h->crf && !h->abr && !h->pass2) p.rc.i_rc_method = X264_RC_CQP;
-    if ((h->pass1 || h->pass2) && p.rc.b_mb_tree) { xlog(&p, X264_LOG_INFO, "2-pass: the macroblock-tree statistics file is not implemented in the MI355X path: mbtree 0 in both passes\n"); p.rc.b_mb_tree = 0; }
-    parse_zones(h, p.rc.psz_zones);
-    if (!h->zones.empty()) xlog(&p, X264_LOG_INFO, "%d zone%s (quantiser / bitrate factor per range of pictures)\n", (int)h->zones.size(), h->zones.size() > 1 ? "s" : "");
-    if (!h->zones.empty() && h->pass2) xlog(&p, X264_LOG_WARNING, "zones are not applied to the second pass' plan in the MI355X path (the first pass and single-pass sessions honour them)\n");
+    if (!rc.by_cost() && !rc.pass2) p.rc.i_rc_method = X264_RC_CQP;
+    if ((rc.pass1 || rc.pass2) && p.rc.b_mb_tree) { xlog(&p, X264_LOG_INFO, "2-pass: the macroblock-tree statistics file is not implemented in the MI355X path: mbtree 0 in both passes\n"); p.rc.b_mb_tree = 0; }
+    rc.parse_zones(p);
+    if (!rc.zones.empty()) xlog(&p, X264_LOG_INFO, "%d zone%s (quantiser / bitrate factor per range of pictures)\n", (int)rc.zones.size(), rc.zones.size() > 1 ? "s" : "");
+    if (!rc.zones.empty() && rc.pass2) xlog(&p, X264_LOG_WARNING, "zones are not applied to the second pass' plan in the MI355X path (the first pass and single-pass sessions honour them)\n");
     if (p.rc.i_vbv_max_bitrate > 0 || p.rc.i_vbv_buffer_size > 0) xlog(&p, X264_LOG_WARNING, "VBV (vbv-maxrate / vbv-bufsize) is not implemented in the MI355X path: unconstrained\n");
     p.rc.i_vbv_max_bitrate = 0; p.rc.i_vbv_buffer_size = 0;
     if (p.analyse.i_noise_reduction) { xlog(&p, X264_LOG_WARNING, "nr (noise reduction) is not implemented in the MI355X path: nr 0\n"); p.analyse.i_noise_reduction = 0; }
@@ -854,7 +782,7 @@ static void open_quantisers(x264_t *h)
     h->keyint_min = p.i_keyint_min;
     h->qp_p = p.rc.i_qp_constant;
     h->qp_i = clampi((int)(h->qp_p - 6.0 * log2(p.rc.f_ip_factor > 0 ? p.rc.f_ip_factor : 1.0) + 0.5), 1, 51);
-    h->pic_init_qp = h->crf || h->abr ? 26 : clampi(h->qp_p, 0, 51);          // CRF moves the slice quantiser both ways: centre the +-26 range of slice_qp_delta
+    h->pic_init_qp = rc.by_cost() ? 26 : clampi(h->qp_p, 0, 51);          // CRF moves the slice quantiser both ways: centre the +-26 range of slice_qp_delta
     h->profile_idc = p.analyse.b_transform_8x8 ? 100 : p.b_cabac ? 77 : 66;        // High for the 8x8 transform, Main for CABAC alone, else Baseline-compatible
     h->level_idc = p.i_level_idc > 0 ? p.i_level_idc : pick_level(&p, h->nmb, p.i_frame_reference);
     p.i_level_idc = h->level_idc;
@@ -920,7 +848,7 @@ static x264gpu_config open_device_config(x264_t *h)
     p.analyse.i_mv_range = clampi(p.analyse.i_mv_range, 32, 512);
     cfg.mv_range = p.analyse.i_mv_range;
     h->inflight = 1;
-    if (h->dpbmode && p.i_bframe > 0 && h->G == 1 && !h->batch_n && !h->pass1 && !h->pass2 && !h->abr && h->direct_mode != 3) {
+    if (h->dpbmode && p.i_bframe > 0 && h->G == 1 && !h->batch_n && !h->rc.reads_sizes() && h->direct_mode != 3) {
         // (--direct auto chooses a B picture's mode from the skip counts of the one before, ABR and 2-pass a picture's quantiser from the sizes of the ones before:
         //  those sessions code one picture at a time)
         const char *ie = getenv("X264GPU_INFLIGHT");
@@ -998,7 +926,7 @@ static bool open_lookahead(x264_t *h)
 {
     x264_param_t &p = h->param;
     const size_t insz = (size_t)p.i_width * p.i_height * 3 / 2;
-    if ((p.i_scenecut_threshold > 0 && !h->dpbmode) || h->crf || h->abr || h->aq_mode >= 2) {       // (sessions on the DPB model take scene cuts from x264's own analysis below)
+    if ((p.i_scenecut_threshold > 0 && !h->dpbmode) || h->rc.by_cost() || h->aq_mode >= 2) {       // (sessions on the DPB model take scene cuts from x264's own analysis below)
         if (x264gpu_lookahead_create(&h->la, p.i_width, p.i_height, 1, p.analyse.i_me_range, p.analyse.i_subpel_refine) != X264GPU_OK ||
             x264gpu_malloc((void **)&h->d_la, 4 * sizeof(int32_t)) != X264GPU_OK) {
             xlog(&p, X264_LOG_ERROR, "GPU lookahead setup failed: %s\n", x264gpu_last_error());
@@ -1011,7 +939,7 @@ static bool open_lookahead(x264_t *h)
     h->L = h->mbtree ? p.rc.i_lookahead : 0;
     // pictures are held back anyway and the quantisers do not depend on coded sizes: overlap the GPU stage of the next picture with
     // the entropy coding of this one (one more picture of delay); X264GPU_HOST_PIPELINE=0 keeps the two stages in one call
-    { const char *pe = getenv("X264GPU_HOST_PIPELINE"); h->pipeline = h->G == 1 && h->L > 0 && h->crf && !(pe && pe[0] == '0'); }
+    { const char *pe = getenv("X264GPU_HOST_PIPELINE"); h->pipeline = h->G == 1 && h->L > 0 && h->rc.crf && !(pe && pe[0] == '0'); }
     h->Q = h->L + 1 + (h->pipeline ? 1 : 0);
     if (h->dpbmode) {
         if (h->L > 60) { xlog(&p, X264_LOG_INFO, "rc-lookahead %d -> 60 in sessions with B pictures (the lookahead keeps every queued picture's half-resolution planes and searches on the device)\n", h->L); h->L = 60; p.rc.i_lookahead = 60; }
@@ -1043,7 +971,7 @@ static bool open_lookahead(x264_t *h)
         (void)x264gpu_slicetype_set_bframe_bias(h->st, p.i_bframe_bias);          // --b-bias also scales the B costs of slicetype_frame_cost
     }
     h->aq_strength = h->aq_mode == X264_AQ_VARIANCE ? p.rc.f_aq_strength * 1.0397f : h->aq_mode >= 2 ? p.rc.f_aq_strength : 0.f;      // (modes 2 / 3: the plain strength, x264_adaptive_quant_frame scales it by the picture's mean itself)
-    h->st_aq_costs = h->st && h->la && !h->mbtree && h->aq_strength != 0.f && (h->crf || h->abr);
+    h->st_aq_costs = h->st && h->la && !h->mbtree && h->aq_strength != 0.f && h->rc.by_cost();
     h->tree_strength = 5.0f * (1.0f - p.rc.f_qcompress);
     h->q_raw.assign((size_t)h->Q, nullptr); h->q_info.assign((size_t)h->Q, nullptr); h->q_aq.assign((size_t)h->Q, nullptr); h->q_tree.assign((size_t)h->Q, nullptr);
     if (h->Q == 1) h->q_raw[0] = h->d_in;            // no delay: the staging buffer is the one slot; with a delay the ring is separate,
@@ -1068,53 +996,6 @@ static bool open_lookahead(x264_t *h)
             xlog(&p, X264_LOG_ERROR, "GPU lookahead queue setup failed: %s\n", x264gpu_last_error());
             return false;
         }
-    }
-    return true;
-}
-
-// single-pass rate control state, the second pass' plan, the statistics file
-static bool open_ratecontrol(x264_t *h)
-{
-    x264_param_t &p = h->param;
-    if (h->crf || h->abr) {
-        // x264_ratecontrol_new: rate_factor_constant = base_cplx^(1 - qcomp) / qp2qscale(crf), base_cplx = mbs * (bframes ? 120 : 80)
-        auto qp2qscale = [](double q) { return rc_qp2qscale(q); };
-        h->rc.qcompress = p.rc.f_qcompress; h->rc.ip_factor = fabs(p.rc.f_ip_factor) > 0 ? fabs(p.rc.f_ip_factor) : 1.0;
-        h->rc.ip_offset = 6.0 * log2f((float)h->rc.ip_factor);          // x264_ratecontrol_init_reconfigurable: 6.0 * log2f( f_ip_factor )
-        if (p.rc.b_mb_tree) h->rc.qcompress = 1.0;                     // x264_ratecontrol_new: the tree does the complexity weighting, CRF shifts by 13.5 (1 - qcomp)
-        h->rc.rate_factor_constant = pow((double)h->nmb * (h->bframes ? 120.0 : 80.0), 1.0 - h->rc.qcompress) / qp2qscale(p.rc.f_rf_constant + (p.rc.b_mb_tree ? (1.0 - p.rc.f_qcompress) * 13.5 : 0.0));
-        h->rc.last_qscale_for[0] = h->rc.last_qscale_for[1] = qp2qscale(p.rc.f_rf_constant);
-        // x264_ratecontrol_new (b_abr = CRF and ABR alike): the running P quantiser starts with a hundredth of a picture at ABR_INIT_QP (CRF: the rate factor; ABR: 24)
-        h->rc.accum_p_norm = .01; h->rc.accum_p_qp = (h->crf ? (double)p.rc.f_rf_constant : 24.0) * h->rc.accum_p_norm;
-        h->rc.lmin = qp2qscale(p.rc.i_qp_min); h->rc.lmax = qp2qscale(p.rc.i_qp_max);
-        double dur = p.i_fps_num ? (double)p.i_fps_den / p.i_fps_num : 0.04;
-        dur = dur < 0.01 ? 0.01 : dur > 1.0 ? 1.0 : dur;              // CLIP_DURATION
-        h->rc.dur_ratio = dur / 0.04;                                  // BASE_FRAME_DURATION
-        if (h->abr) {
-            // x264_ratecontrol_new / x264_ratecontrol_init_reconfigurable, ABR without VBV
-            const double abr_init_qp = 24.0;
-            h->rc.bitrate = p.rc.i_bitrate * 1000.0; h->rc.fps = p.i_fps_num ? (double)p.i_fps_num / p.i_fps_den : 25.0;
-            h->rc.cplxr_sum = 0.01 * pow(7.0e5, h->rc.qcompress) * pow((double)h->nmb, 0.5);
-            h->rc.wanted_bits_window = h->rc.bitrate / h->rc.fps;
-            h->rc.abr_buffer = 2.0 * (p.rc.f_rate_tolerance > 0.01f ? p.rc.f_rate_tolerance : 0.01f) * h->rc.bitrate;
-            h->rc.lstep = pow(2.0, (p.rc.i_qp_step > 0 ? p.rc.i_qp_step : 4) / 6.0);
-            h->rc.last_qscale_for[0] = h->rc.last_qscale_for[1] = qp2qscale(abr_init_qp);
-        }
-    }
-    h->rc.fps = p.i_fps_num ? (double)p.i_fps_num / p.i_fps_den : 25.0;
-    if (h->pass2) {
-        if (!p2_load(h, p.rc.psz_stat_in) || !p2_init(h)) return false;
-        xlog(&p, X264_LOG_INFO, "2-pass: %d pictures planned from the first pass' statistics, %.1f kbit expected before the last one\n", (int)h->p2.size(), h->p2_final_bits / 1000.0);
-    }
-    // (the driver's N-th pass asks for both: statistics read AND written again — codec.c:1519-1541 with its fixed updatestats — so that a further pass plans from this one's pictures)
-    const bool stat_update = h->pass2 && p.rc.b_stat_write && p.rc.psz_stat_out;
-    if (h->pass1 || stat_update) {
-        // x264 writes <stats>.temp and renames it when the encoder closes; the first line names the options the second pass must agree with
-        h->stat_file = fopen((std::string(p.rc.psz_stat_out) + ".temp").c_str(), "wb");
-        if (!h->stat_file) { xlog(&p, X264_LOG_ERROR, "ratecontrol_init: can't open stats file\n"); return false; }
-        fprintf(h->stat_file, "#options: %dx%d fps=%u/%u timebase=%u/%u bitdepth=8 cabac=%d ref=%d bframes=%d b_pyramid=%d b_adapt=%d weightp=%d keyint=%d rc=%s\n", p.i_width, p.i_height,
-                p.i_fps_num, p.i_fps_den, p.i_fps_den, p.i_fps_num, p.b_cabac, p.i_frame_reference, p.i_bframe, p.i_bframe_pyramid, p.i_bframe_adaptive, p.analyse.i_weighted_pred, p.i_keyint_max,
-                p.rc.i_rc_method == X264_RC_ABR ? "abr" : p.rc.i_rc_method == X264_RC_CRF ? "crf" : "cqp");
     }
     return true;
 }
@@ -1164,7 +1045,7 @@ x264_t *x264_encoder_open(x264_param_t *param)
     open_toolset(h);
     open_modes(h);
     open_quantisers(h);
-    if (!open_device(h) || !open_lookahead(h) || !open_ratecontrol(h)) { x264_encoder_close(h); return nullptr; }
+    if (!open_device(h) || !open_lookahead(h) || !h->rc.open(p, h->mbw, h->mbh, h->bframes, h->qp_i, h->qp_p)) { x264_encoder_close(h); return nullptr; }
     open_host_buffers(h);
     xlog(&p, X264_LOG_INFO, "MI355X hot path: %dx%d, %d MBs, CQP I:%d P:%d, keyint %d, level %d\n", p.i_width, p.i_height, h->nmb,
          h->qp_i, h->qp_p, h->keyint, h->level_idc);
@@ -1220,8 +1101,6 @@ static void join_pool(x264_t *h)
     for (int s = h->pool_slot0; s < h->pool_slot0 + h->pool_nslots; s++) h->slot_have[(size_t)s * h->keyint + h->pool_t] = 1;
     h->pool_nslots = 0; h->pool_slot0 = 0;
 }
-
-static int rc_pick_qp(x264_t *h, bool is_i, const int32_t costs[4], int frames_done, int frame);
 
 // One coding position of the slots [slot0, slot0 + nslots) on the devices: launch(dc, d) issues device d's encode call for its slots (false: it failed), the
 // records and levels of those slots then land in the download buffers not in use — on the caller's thread when there is one device, else on a host thread per
@@ -1302,14 +1181,9 @@ static int code_position_b(x264_t *h, int batch, int c, int slot0, int nslots, c
         gd.dpb.set_direct(pic.direct_temporal, 0);
     }
     if (plan.nal_ref_idc) gd.l0ref0poc[pic.dst] = pic.nref[0] ? plan.list_poc[0][0] : INT_MIN;
-    // constant quantiser by picture type (x264_ratecontrol_start), a zone shifts it by the picture's display index in the stream
-    const double pb_offset = 6.0 * log2f(fabs(p.rc.f_pb_factor) > 0 ? fabsf(p.rc.f_pb_factor) : 1.0f);
-    const int qb = clampi((int)(h->qp_p + pb_offset + 0.5), 0, 51);
-    const int q_type = type <= PIC_I ? h->qp_i : type == PIC_P ? h->qp_p : type == PIC_BREF ? (qb + h->qp_p) / 2 : qb;
-    std::vector<int> qps((size_t)G, q_type);
-    if (!h->zones.empty())
-        for (int s = slot0; s < slot0 + nslots; s++)
-            if (const x264_t::Zone *z = get_zone(h, (int)(((long)batch * G + s) * K + disp))) qps[(size_t)s] = cqp_zone(h, *z, q_type);
+    // constant quantiser by picture type, a zone shifts it by the picture's display index in the stream (a slot coded along and thrown away: the type's)
+    std::vector<int> qps((size_t)G, h->rc.qp_constant[type]);
+    for (int s = slot0; s < slot0 + nslots; s++) qps[(size_t)s] = h->rc.start(type, (int)(((long)batch * G + s) * K + disp));
     SliceParams sp = slice_params_base(h);
     gd.dpb.fill(sp);
     gd.dpb.commit();
@@ -1341,14 +1215,12 @@ static int code_position(x264_t *h, int batch, int t, int nslots_with_t)
     const size_t insz = (size_t)p.i_width * p.i_height * 3 / 2;
     const int st = t == 0 ? X264GPU_SLICE_I : X264GPU_SLICE_P, G = h->G;
     std::vector<int8_t> qps; std::vector<float> qpms;
-    if (h->crf) {
-        qps.assign((size_t)G, (int8_t)(t == 0 ? h->qp_i : h->qp_p)); qpms.assign((size_t)G, 0.f);
-        for (int s = 0; s < nslots_with_t; s++) { qps[(size_t)s] = h->gop_qp[(size_t)s * h->keyint + t]; qpms[(size_t)s] = h->gop_qpm[(size_t)s * h->keyint + t]; }
-    } else if (!h->abr && !h->zones.empty()) {
-        // constant quantiser with zones: slot s of this batch holds picture (batch * G + s) * keyint + t of the stream
+    if (h->rc.crf || (!h->rc.abr && !h->rc.zones.empty())) {
+        // CRF: decided when the pictures arrived; constant quantiser with zones: slot s of this batch holds picture (batch * G + s) * keyint + t of the stream
         qps.assign((size_t)G, (int8_t)(t == 0 ? h->qp_i : h->qp_p)); qpms.assign((size_t)G, 0.f);
         for (int s = 0; s < nslots_with_t; s++)
-            if (const x264_t::Zone *z = get_zone(h, (int)(((long)batch * G + s) * h->keyint + t))) qps[(size_t)s] = (int8_t)cqp_zone(h, *z, qps[(size_t)s]);
+            if (h->rc.crf) { qps[(size_t)s] = h->gop_qp[(size_t)s * h->keyint + t]; qpms[(size_t)s] = h->gop_qpm[(size_t)s * h->keyint + t]; }
+            else qps[(size_t)s] = (int8_t)h->rc.start(t == 0 ? PIC_IDR : PIC_P, (int)(((long)batch * G + s) * h->keyint + t));
     }
     // every device codes position t of its slots: GPU + download run while the CAVLC threads of the previous position are still coding from the other buffer pair
     const int D = (int)h->devs.size();
@@ -1411,20 +1283,21 @@ static int encode_gop_parallel(x264_t *h, x264_nal_t **pp_nal, int *pi_nal, x264
         }
         // the lookahead lives on the caller's device: with several devices the picture also goes to the staging buffer there
         const uint8_t *la_src = dst;
-        if (h->crf && D > 1 && dc.dev != h->device) {
+        if (h->rc.crf && D > 1 && dc.dev != h->device) {
             if (!resident && x264gpu_memcpy_h2d(h->d_in, src, insz, nullptr) != X264GPU_OK) { xlog(&p, X264_LOG_ERROR, "x264_encoder_encode: upload failed: %s\n", x264gpu_last_error()); return -1; }
             la_src = h->d_in;
         }
-        if (h->crf) {
-            // CRF: the picture's quantiser follows from the lookahead costs and the pictures before it, all known now (rc_pick_qp)
+        if (h->rc.crf) {
+            // CRF: the picture's quantiser follows from the lookahead costs and the pictures before it, all known now (decided by its display index)
             int32_t costs[4];
             if (x264gpu_lookahead_frame_cost(h->la, la_src, i == 0, h->d_la, nullptr, nullptr) != X264GPU_OK ||
                 x264gpu_memcpy_d2h(costs, h->d_la, sizeof(costs), nullptr) != X264GPU_OK) {
                 xlog(&p, X264_LOG_ERROR, "x264_encoder_encode: lookahead failed: %s\n", x264gpu_last_error());
                 return -1;
             }
-            h->gop_qp[(size_t)s * K + t] = (int8_t)rc_pick_qp(h, t == 0, costs, (int)i, (int)i);
-            h->gop_qpm[(size_t)s * K + t] = near_qpm(h->rc.qpa_last, h->gop_qp[(size_t)s * K + t]);
+            double qpf;
+            h->gop_qp[(size_t)s * K + t] = (int8_t)h->rc.start(t == 0 ? PIC_IDR : PIC_P, (int)i, costs, nullptr, &qpf);
+            h->gop_qpm[(size_t)s * K + t] = near_qpm(qpf, h->gop_qp[(size_t)s * K + t]);
         }
         h->pts.push_back(pic_in->i_pts);
         if (h->gopb) h->all_pts.push_back(pic_in->i_pts);
@@ -1500,60 +1373,6 @@ static int encode_gop_parallel(x264_t *h, x264_nal_t **pp_nal, int *pi_nal, x264
     return (int)h->out.size();
 }
 
-// rate_estimate_qscale for the picture about to be coded (single-pass CRF / ABR): a function of the lookahead costs, the picture type and
-// the running rate-control state only (ABR adds the coded sizes through x264_ratecontrol_end), so under CRF it can run when a picture
-// ARRIVES — which is what lets GOP-parallel sessions keep CRF's quantisers.  frames_done = pictures decided before this one.
-static int rc_pick_qp(x264_t *h, bool is_i, const int32_t costs[4], int frames_done, int frame)
-{
-    const x264_param_t &p = h->param;
-    // rate_estimate_qscale: q = rceq / rate_factor; rceq = blurred_complexity^(1 - qcomp), or under macroblock-tree (which does the
-    // complexity weighting itself) the frame-duration term alone; an I picture after P pictures takes the running P quantiser /
-    // ipratio; the quantiser is qscale2qp(q) rounded, within [qpmin, qpmax]
-    auto qp2qscale = [](double q) { return rc_qp2qscale(q); };
-    auto qscale2qp = [](double qs) { return rc_qscale2qp(qs); };
-    const double satd = is_i ? costs[0] : costs[1];
-    h->rc.cplxsum = h->rc.cplxsum * 0.5 + satd / h->rc.dur_ratio;
-    h->rc.cplxcount = h->rc.cplxcount * 0.5 + 1.0;
-    double q, overflow = 1.0;
-    const double rate_factor = h->crf ? h->rc.rate_factor_constant : h->rc.wanted_bits_window / h->rc.cplxr_sum;
-    if (satd > 0) {
-        h->rc.last_rceq = h->mbtree ? pow(1.0 / h->rc.dur_ratio, 1.0 - p.rc.f_qcompress) : pow(h->rc.cplxsum / h->rc.cplxcount, 1.0 - h->rc.qcompress);
-        q = FL(h->rc.last_rceq / rate_factor);          // (rate_estimate_qscale's q is a float: every assignment rounds)
-    } else q = FL(h->rc.last_qscale_for[is_i ? 0 : 1]);
-    // get_qscale: a zone forces its quantiser or scales the picture's bits (an I picture after P pictures still takes the running P quantiser below, as in x264)
-    if (const x264_t::Zone *z = get_zone(h, frame)) q = FL(z->force_qp ? qp2qscale(z->qp) : q / z->bitrate_factor);
-    if (h->abr && satd > 0) {
-        // pull towards the target: bits so far against time so far, within an abr_buffer that grows with sqrt(time)
-        const double time_done = frames_done / h->rc.fps, wanted_bits = time_done * h->rc.bitrate;
-        if (wanted_bits > 0) {
-            const double buf = h->rc.abr_buffer * (time_done > 1.0 ? sqrt(time_done) : 1.0);
-            overflow = 1.0 + (h->rc.total_bits - wanted_bits) / buf;
-            overflow = overflow < 0.5 ? 0.5 : overflow > 2.0 ? 2.0 : overflow;
-            q = FL(q * overflow);
-        }
-    }
-    if (is_i && h->keyint > 1 && !h->rc.last_non_b_is_i) q = FL(qp2qscale(h->rc.accum_p_qp / h->rc.accum_p_norm) / h->rc.ip_factor);
-    else if (frames_done > 0) {
-        if (h->abr) {       // asymmetric clipping against the last quantiser of the same picture type (qpstep)
-            double lmin = h->rc.last_qscale_for[is_i ? 0 : 1] / h->rc.lstep, lmax = h->rc.last_qscale_for[is_i ? 0 : 1] * h->rc.lstep;
-            if (overflow > 1.1 && frames_done > 3) lmax *= h->rc.lstep;
-            else if (overflow < 0.9) lmin /= h->rc.lstep;
-            q = FL(q < lmin ? lmin : q > lmax ? lmax : q);
-        }
-    } else if (h->crf && h->rc.qcompress != 1.0) q = FL(qp2qscale(p.rc.f_rf_constant) / h->rc.ip_factor);       // very first picture: ABR_INIT_QP / ipratio
-    q = FL(q < h->rc.lmin ? h->rc.lmin : q > h->rc.lmax ? h->rc.lmax : q);
-    h->rc.last_qscale_for[is_i ? 0 : 1] = q;
-    if (frames_done == 0) h->rc.last_qscale_for[1] = q * h->rc.ip_factor;
-    double qpf = qscale2qp(q);
-    qpf = qpf < p.rc.i_qp_min ? p.rc.i_qp_min : qpf > p.rc.i_qp_max ? p.rc.i_qp_max : qpf;
-    const int qp_now = clampi((int)(qpf + 0.5), 1, 51);
-    h->rc.accum_p_qp = h->rc.accum_p_qp * 0.95 + (is_i ? qpf + h->rc.ip_offset : qpf);      // accum_p_qp_update
-    h->rc.accum_p_norm = h->rc.accum_p_norm * 0.95 + 1.0;
-    h->rc.last_non_b_is_i = is_i;
-    h->rc.qpa_last = qpf;
-    return qp_now;
-}
-
 // GPU stage of queue[idx]: macroblock-tree over the pictures queued behind it (up to the next intra picture), rate control, the hot
 // path and the download of its records / levels into host buffer pair `buf` — in a helper thread when `async` (join_gpu waits).
 static void join_gpu(x264_t *h) { if (h->gpu_thread.joinable()) h->gpu_thread.join(); }
@@ -1562,12 +1381,7 @@ static int gpu_stage(x264_t *h, size_t idx, int buf, bool async)
 {
     const x264_param_t &p = h->param;
     x264_t::QEntry &e = h->queue[idx];
-    const bool idr = e.type == 2, intra_pic = e.type == 1, is_i = idr || intra_pic;
-    int qp_now = is_i ? h->qp_i : h->qp_p;
-    if (!h->crf && !h->abr && !h->zones.empty()) {          // constant quantiser with zones: every picture names its quantiser
-        if (const x264_t::Zone *z = get_zone(h, h->rc_frames)) qp_now = cqp_zone(h, *z, qp_now);
-        if (x264gpu_encoder_set_qp(h->gpu, qp_now, qp_now) != X264GPU_OK) return -1;
-    }
+    const bool idr = e.type == 2, intra_pic = e.type == 1;
     if (h->mbtree) {
         // macroblock_tree: this picture and the P pictures behind it that (transitively) reference it; an intra picture ends the chain
         const int32_t *info[256]; const float *aq[256];
@@ -1584,13 +1398,13 @@ static int gpu_stage(x264_t *h, size_t idx, int buf, bool async)
             return -1;
         }
     }
-    if (h->crf || h->abr) {
-        qp_now = rc_pick_qp(h, is_i, e.costs, h->rc_frames, h->rc_frames);
+    // (pictures leave in the order they came: the rate control's count of them is the display index)
+    const int qp_now = h->rc.start(idr ? PIC_IDR : intra_pic ? PIC_I : PIC_P, h->rc.frames_done, e.costs, nullptr, &e.qpf);
+    if (h->rc.by_cost()) {
         // x264_ratecontrol_mb_qp adds the AQ / macroblock-tree offsets to the FLOAT quantiser (rc->qpm) before the one rounding
-        e.qpm = near_qpm(h->rc.qpa_last, qp_now);
+        e.qpm = near_qpm(e.qpf, qp_now);
         if (x264gpu_encoder_set_qp(h->gpu, qp_now, qp_now) != X264GPU_OK || x264gpu_encoder_set_qpm(h->gpu, e.qpm) != X264GPU_OK) return -1;
-    }
-    h->rc_frames++;
+    } else if (!h->rc.zones.empty() && x264gpu_encoder_set_qp(h->gpu, qp_now, qp_now) != X264GPU_OK) return -1;          // (constant quantiser: only zones move what the device has)
     e.qp = qp_now; e.buf = buf; e.launched = true;
     const int st = idr ? X264GPU_SLICE_I : intra_pic ? X264GPU_SLICE_I_NONIDR : X264GPU_SLICE_P;
     const uint8_t *src = h->q_raw[(size_t)e.slot];
@@ -1648,13 +1462,7 @@ static int encode_queued(x264_t *h, x264_nal_t **pp_nal, int *pi_nal, x264_pictu
     if (h->ql.flags) h->ql.frame_end(p, h->hq[e.buf], st == X264GPU_SLICE_P ? 1 : 0, mean_mb_qp(hmb, (size_t)h->nmb), 2 * h->frames_since_idr, h->out.size());
     if (idr) h->idr_pic_id = (h->idr_pic_id + 1) & 0xffff;
     h->frame_num = (h->frame_num + 1) & ((1 << h->log2_max_frame_num) - 1);
-    if (h->abr) {
-        // x264_ratecontrol_end: what this picture's bits say about the rate factor, and the bits the window now expects
-        const double bits = 8.0 * (double)h->out.size();
-        h->rc.total_bits += bits;
-        h->rc.cplxr_sum += bits * rc_qp2qscale(rc_qp_avg_rc((float)h->rc.qpa_last, h->mbw, h->mbh)) / h->rc.last_rceq;          // (rc->qpa_rc: the float gathered row by row)
-        h->rc.wanted_bits_window += h->rc.bitrate / h->rc.fps;
-    }
+    h->rc.end(h->out.size(), type, h->frame_no, e.qpf);          // (no statistics file off the DPB model)
     h->frames_since_idr++;
     h->frame_no++;
     h->queue.pop_front();
@@ -2045,12 +1853,13 @@ static bool st_decide(x264_t *h, bool flushing, int &j_out, int &closing_out)
     const int n = (int)h->bq.size();
     if (!flushing && n <= h->st_wait) return false;
     for (auto &e : h->bq) e.type = e.forced == 2 ? ST_IDR : e.forced == 1 ? ST_I : ST_AUTO;
-    if (h->pass2) {
+    if (h->rc.pass2) {
         // x264_ratecontrol_slice_type: the second pass codes every picture as the type the first pass gave it (the B-reference of a run is placed by
         // the same rule in both passes)
         for (auto &e : h->bq) {
-            if (e.frame >= (int)h->p2.size()) continue;
-            const char t = h->p2[(size_t)e.frame].type;
+            const RateControl::Pass2Entry *pe = h->rc.plan(e.frame);
+            if (!pe) continue;
+            const char t = pe->type;
             e.type = t == 'I' ? ST_IDR : t == 'i' ? ST_I : t == 'P' ? ST_P : ST_B;
         }
     } else
@@ -2097,7 +1906,7 @@ static bool bmode_decide(x264_t *h, bool flushing)
             h->bq[(size_t)j].w = st_weights_analyse(h, h->bq[(size_t)j], h->last_nonb, j + 1, false);
             if (h->failed) return false;
         }
-        if (h->crf || h->abr) {
+        if (h->rc.by_cost()) {
             // x264_rc_analyse_slice: the closing picture's complexity is its frame cost as the type it was given — the I cost, or the P cost
             // against the last non-B picture (distance = run length + 1), from the lookahead that decided the types
             x264_t::BEntry &c = h->bq[(size_t)j];
@@ -2154,235 +1963,6 @@ static bool bmode_decide(x264_t *h, bool flushing)
     return true;
 }
 
-// ---- 2-pass rate control (x264 ratecontrol.c: x264_ratecontrol_new's statistics parser, init_pass2, get_qscale / get_diff_limited_q,
-//      qscale2bits; no VBV, no zones, no macroblock-tree file: the tree is off in these sessions) ----
-static double p2_qscale2bits(const x264_t::Pass2Entry &e, double qscale)
-{
-    if (qscale < 0.1) qscale = 0.1;
-    return (e.tex + .1) * pow(e.qscale / qscale, 1.1) + e.mv * pow((e.qscale > 1 ? e.qscale : 1) / (qscale > 1 ? qscale : 1), 0.5) + e.misc;
-}
-static bool p2_load(x264_t *h, const char *path)
-{
-    FILE *f = fopen(path, "rb");
-    if (!f) { xlog(&h->param, X264_LOG_ERROR, "ratecontrol_init: can't open stats file\n"); return false; }
-    char line[2048];
-    std::vector<x264_t::Pass2Entry> raw;
-    while (fgets(line, sizeof(line), f)) {
-        if (line[0] == '#') continue;
-        x264_t::Pass2Entry e;
-        long long dur = 0, cpbdur = 0;
-        float q = 0, aq = 0;
-        int tex = 0, mv = 0, misc = 0, imb = 0, pmb = 0, smb = 0;
-        char d = '-';
-        if (sscanf(line, " in:%d out:%d type:%c dur:%lld cpbdur:%lld q:%f aq:%f tex:%d mv:%d misc:%d imb:%d pmb:%d smb:%d d:%c", &e.in, &e.out, &e.type, &dur, &cpbdur, &q, &aq,
-                   &tex, &mv, &misc, &imb, &pmb, &smb, &d) < 13) { fclose(f); xlog(&h->param, X264_LOG_ERROR, "statistics are damaged at line %d, parser out\n", (int)raw.size() + 1); return false; }
-        e.qp = q; e.qscale = rc_qp2qscale(q); e.tex = tex; e.mv = mv; e.misc = misc; e.icount = imb; e.dur = dur > 0 ? (double)dur : 1.0; e.kept_as_ref = e.type != 'b';
-        raw.push_back(e);
-    }
-    fclose(f);
-    if (raw.empty()) { xlog(&h->param, X264_LOG_ERROR, "empty stats file\n"); return false; }
-    h->p2.assign(raw.size(), x264_t::Pass2Entry()); h->p2_out.assign(raw.size(), 0);
-    for (const auto &e : raw) {
-        if (e.in < 0 || e.in >= (int)raw.size() || e.out < 0 || e.out >= (int)raw.size()) { xlog(&h->param, X264_LOG_ERROR, "bad frame number (%d) at stats line\n", e.in); return false; }
-        h->p2[(size_t)e.in] = e; h->p2_out[(size_t)e.out] = e.in;
-    }
-    return true;
-}
-// x264's slice type of a statistics character as the rate control groups them: 0 I, 1 P, 2 B
-static int p2_kind(char t) { return t == 'I' || t == 'i' ? 0 : t == 'P' ? 1 : 2; }
-static bool p2_init(x264_t *h)
-{
-    const x264_param_t &p = h->param;
-    std::vector<x264_t::Pass2Entry> &E = h->p2;
-    const int n = (int)E.size();
-    const double fps = h->rc.fps > 0 ? h->rc.fps : 25.0, nmb = h->nmb;
-    double duration = 0;
-    for (auto &e : E) duration += e.dur;
-    duration /= fps * E[0].dur;                               // (durations are in ticks of one picture here: constant frame rate, codec.c:1476-1480)
-    const double all_available_bits = p.rc.i_bitrate * 1000.0 * duration;
-    const double qblur = p.rc.f_qblur, cplxblur = p.rc.f_complexity_blur, qcompress = p.rc.f_qcompress;
-    const int filter_size = (int)(qblur * 4) | 1;
-    const double base_cplx = nmb * (p.i_bframe ? 120 : 80);
-    const double lstep = pow(2.0, p.rc.i_qp_step / 6.0), lmin = rc_qp2qscale(p.rc.i_qp_min), lmax = rc_qp2qscale(p.rc.i_qp_max);
-    const double ipf = fabs(p.rc.f_ip_factor) > 0 ? fabs(p.rc.f_ip_factor) : 1.0, pbf = fabs(p.rc.f_pb_factor) > 0 ? fabs(p.rc.f_pb_factor) : 1.0;
-    double all_const_bits = 0;
-    for (auto &e : E) all_const_bits += e.misc;
-    if (all_available_bits < all_const_bits) {
-        xlog(&p, X264_LOG_ERROR, "requested bitrate is too low. estimated minimum is %d kbps\n", (int)(all_const_bits * fps / (n * 1000.)));
-        return false;
-    }
-    // blur the complexities (not the quantisers: one very simple picture must not drag its neighbours down); per unit of BASE_FRAME_DURATION as x264 has it
-    const double frame_duration = (1.0 / fps < 0.01 ? 0.01 : 1.0 / fps > 1.0 ? 1.0 : 1.0 / fps) / 0.04;
-    for (int i = 0; i < n; i++) {
-        double weight_sum = 0, cplx_sum = 0, weight = 1.0;
-        for (int j = 1; j < cplxblur * 2 && j < n - i; j++) {
-            const auto &r = E[(size_t)(i + j)];
-            weight *= 1 - pow((float)r.icount / (float)h->nmb, 2);          // (x264: a float division — i_count and nmb are integers there)
-            if (weight < .0001) break;
-            const double g = weight * exp(-j * j / 200.0);
-            weight_sum += g; cplx_sum += g * (p2_qscale2bits(r, 1) - r.misc) / frame_duration;
-        }
-        weight = 1.0;
-        for (int j = 0; j <= cplxblur * 2 && j <= i; j++) {
-            const auto &r = E[(size_t)(i - j)];
-            const double g = weight * exp(-j * j / 200.0);
-            weight_sum += g; cplx_sum += g * (p2_qscale2bits(r, 1) - r.misc) / frame_duration;
-            weight *= 1 - pow((float)r.icount / (float)h->nmb, 2);          // (x264: a float division — i_count and nmb are integers there)
-            if (weight < .0001) break;
-        }
-        E[(size_t)i].blurred = (double)(float)(cplx_sum / weight_sum);          // (ratecontrol_entry_t keeps blurred_complexity as a float)
-    }
-    // the rate factor: multiplied into every picture's RCEQ value it makes the sizes add up to the request (no closed form: qscale2bits does not invert)
-    std::vector<double> qscale((size_t)n), blurred((size_t)n);
-    double last_q[3], accum_p_qp = 0, accum_p_norm = 0, last_accum_p_norm = 1;
-    int last_non_b = -1;
-    auto get_qscale = [&](const x264_t::Pass2Entry &e, double rate_factor) {
-        double q = pow(e.blurred, 1 - qcompress);
-        if (!std::isfinite(q) || e.tex + e.mv == 0) q = last_q[p2_kind(e.type)];
-        else q /= rate_factor;
-        return q;
-    };
-    auto diff_limited = [&](const x264_t::Pass2Entry &e, double q) {
-        const int kind = p2_kind(e.type);
-        const double last_p_q = last_q[1], last_non_b_q = last_non_b >= 0 ? last_q[last_non_b] : q;
-        if (kind == 0) {
-            const double iq = q, pq = accum_p_norm > 0 ? rc_qp2qscale(accum_p_qp / accum_p_norm) : q;
-            if (accum_p_norm <= 0) q = iq;
-            else if (p.rc.f_ip_factor < 0) q = iq / ipf;
-            else if (accum_p_norm >= 1) q = pq / ipf;
-            else q = accum_p_norm * pq / ipf + (1 - accum_p_norm) * iq;
-        } else if (kind == 2) {
-            if (p.rc.f_pb_factor > 0) q = last_non_b_q;
-            if (!e.kept_as_ref) q *= pbf;
-        } else if (last_non_b == 1 && e.tex == 0) q = last_p_q;
-        if (last_non_b == kind && (kind != 0 || last_accum_p_norm < 1)) {
-            const double lq = last_q[kind];
-            q = q > lq * lstep ? lq * lstep : q < lq / lstep ? lq / lstep : q;
-        }
-        last_q[kind] = q;
-        if (kind != 2) last_non_b = kind;
-        if (kind == 0) { last_accum_p_norm = accum_p_norm; accum_p_norm = 0; accum_p_qp = 0; }
-        if (kind == 1) { const float mask = (float)(1 - pow((float)e.icount / (float)h->nmb, 2)); accum_p_qp          /* (a float in x264) */ = mask * (rc_qscale2qp(q) + accum_p_qp); accum_p_norm = mask * (1 + accum_p_norm); }
-        return q;
-    };
-    double expected_bits = 1;
-    last_q[0] = last_q[1] = last_q[2] = pow(base_cplx, 1 - qcompress);
-    for (int i = 0; i < n; i++) { const double q = get_qscale(E[(size_t)i], 1.0); expected_bits += p2_qscale2bits(E[(size_t)i], q); last_q[p2_kind(E[(size_t)i].type)] = q; }
-    const double step_mult = all_available_bits / expected_bits;
-    double rate_factor = 0;
-    for (double step = 1E4 * step_mult; step > 1E-7 * step_mult; step *= 0.5) {
-        expected_bits = 0;
-        rate_factor += step;
-        last_non_b = -1; last_accum_p_norm = 1; accum_p_norm = 0; accum_p_qp = 0;
-        last_q[0] = last_q[1] = last_q[2] = pow(base_cplx, 1 - qcompress) / rate_factor;
-        for (int i = 0; i < n; i++) { qscale[(size_t)i] = get_qscale(E[(size_t)i], rate_factor); last_q[p2_kind(E[(size_t)i].type)] = qscale[(size_t)i]; }
-        for (int i = n - 1; i >= 0; i--) qscale[(size_t)i] = diff_limited(E[(size_t)i], qscale[(size_t)i]);       // fixed I / B quantisers relative to P
-        if (filter_size > 1) {                                  // smooth the curve over pictures of the same kind
-            for (int i = 0; i < n; i++) {
-                double q = 0.0, sum = 0.0;
-                for (int j = 0; j < filter_size; j++) {
-                    const int idx = i + j - filter_size / 2;
-                    const double d = idx - i, coeff = qblur == 0 ? 1.0 : exp(-d * d / (qblur * qblur));
-                    if (idx < 0 || idx >= n) continue;
-                    if (p2_kind(E[(size_t)i].type) != p2_kind(E[(size_t)idx].type)) continue;
-                    q += qscale[(size_t)idx] * coeff; sum += coeff;
-                }
-                blurred[(size_t)i] = q / sum;
-            }
-        } else blurred = qscale;
-        for (int i = 0; i < n; i++) {
-            double q = blurred[(size_t)i];
-            q = q < lmin ? lmin : q > lmax ? lmax : q;          // clip_qscale without VBV
-            E[(size_t)i].new_qscale = q;
-            expected_bits += p2_qscale2bits(E[(size_t)i], q);
-        }
-        if (expected_bits > all_available_bits) rate_factor -= step;
-    }
-    // the plan in coding order: what should have been spent when each picture starts
-    expected_bits = 0;
-    for (int k = 0; k < n; k++) { auto &e = E[(size_t)h->p2_out[(size_t)k]]; e.expected_bits = expected_bits; expected_bits += p2_qscale2bits(e, e.new_qscale); }
-    h->p2_final_bits = n > 0 ? E[(size_t)h->p2_out[(size_t)(n - 1)]].expected_bits : 0;          // x264: entry_out[num_entries - 1]->expected_bits — what should have been spent BEFORE the last picture
-    if (fabs(expected_bits / all_available_bits - 1.0) > 0.01) {
-        double avgq = 0;
-        for (auto &e : E) avgq += e.new_qscale;
-        avgq = rc_qscale2qp(avgq / n);
-        xlog(&p, X264_LOG_WARNING, "Error: 2pass curve failed to converge\n");
-        xlog(&p, X264_LOG_WARNING, "target: %.2f kbit/s, expected: %.2f kbit/s, avg QP: %.4f\n", (double)p.rc.i_bitrate, expected_bits / duration / 1000., avgq);
-    }
-    h->p2_abr_buffer = 2 * p.rc.f_rate_tolerance * p.rc.i_bitrate * 1000.0;
-    return true;
-}
-// rate_estimate_qscale, 2-pass branch: the planned quantiser of display picture `frame`, pulled by how far the coded size is from the plan
-static double p2_pick_qscale(x264_t *h, int frame, long coded_so_far)
-{
-    const x264_param_t &p = h->param;
-    const int n = (int)h->p2.size();
-    if (frame >= n) return h->p2[(size_t)(n - 1)].new_qscale;           // (x264: "2nd pass has more frames than 1st pass", then constant quantiser)
-    const x264_t::Pass2Entry &e = h->p2[(size_t)frame];
-    double abr_buffer = h->p2_abr_buffer;
-    if (n > coded_so_far) {           // adjust the buffer by the distance to the end of the video
-        const double video_pos = h->p2_final_bits > 0 ? e.expected_bits / h->p2_final_bits : 1.0, scale_factor = sqrt((1 - video_pos) * n);
-        abr_buffer *= 0.5 * (scale_factor > 0.5 ? scale_factor : 0.5);
-    }
-    const double diff = (double)((long long)h->p2_total_bits - (long long)e.expected_bits);          // (x264: int64_t diff = predicted_bits - (int64_t)rce.expected_bits)
-    double q = e.new_qscale, c = (abr_buffer - diff) / abr_buffer;
-    q /= c < .5 ? .5 : c > 2 ? 2 : c;
-    if (coded_so_far >= h->rc.fps && h->p2_expected_sum >= 1) {          // x264: h->i_frame >= rcc->fps && rcc->expected_bits_sum >= 1
-        const double cur_time = (double)coded_so_far / n, w = cur_time * 100 < 0 ? 0 : cur_time * 100 > 1 ? 1 : cur_time * 100;
-        q *= pow(h->p2_total_bits / h->p2_expected_sum, w);
-    }
-    const double lmin = rc_qp2qscale(p.rc.i_qp_min), lmax = rc_qp2qscale(p.rc.i_qp_max);
-    return q < lmin ? lmin : q > lmax ? lmax : q;
-}
-
-// rate control of one picture of a B session: constant quantisers (x264 rc->qp_constant[] with --ipratio / --pbratio) or CRF (rate_estimate_qscale:
-// I / P as without B pictures; B pictures take the distance-weighted average of their nearest references' quantisers plus the pb offset)
-static int bmode_qp(x264_t *h, const x264_t::BPlanned &pl, const DpbPlan &plan, double *qp_float)
-{
-    const x264_param_t &p = h->param;
-    const double pb_offset = 6.0 * log2f(fabs(p.rc.f_pb_factor) > 0 ? fabsf(p.rc.f_pb_factor) : 1.0f);          // rc->pb_offset = 6.0 * log2f( f_pb_factor )
-    const bool is_i = pl.type == PIC_IDR || pl.type == PIC_I, is_b = pl.type == PIC_B || pl.type == PIC_BREF;
-    if (h->pass2) {
-        double q = rc_qscale2qp(p2_pick_qscale(h, pl.e.frame, h->coded_count));
-        q = q < p.rc.i_qp_min ? p.rc.i_qp_min : q > p.rc.i_qp_max ? p.rc.i_qp_max : q;
-        *qp_float = q;
-        return clampi((int)(q + 0.5), 1, 51);
-    }
-    if (!h->crf && !h->abr) {
-        const int qb = clampi((int)(h->qp_p + pb_offset + 0.5), 0, 51);
-        int q = is_i ? h->qp_i : !is_b ? h->qp_p : pl.type == PIC_BREF ? (qb + h->qp_p) / 2 : qb;
-        if (const x264_t::Zone *z = get_zone(h, pl.e.frame)) q = cqp_zone(h, *z, q);
-        *qp_float = q;
-        return q;
-    }
-    if (!is_b) {
-        const int q = rc_pick_qp(h, is_i, pl.e.costs, h->rc_frames, pl.e.frame);
-        *qp_float = h->rc.qpa_last;
-        return q;
-    }
-    const int s0 = plan.pic.slot[0][0], s1 = plan.pic.slot[1][0];
-    const bool i0 = h->slot_ptype[s0] == PIC_IDR || h->slot_ptype[s0] == PIC_I, i1 = h->slot_ptype[s1] == PIC_IDR || h->slot_ptype[s1] == PIC_I;
-    const int dt0 = abs(plan.pic.poc - plan.list_poc[0][0]), dt1 = abs(plan.pic.poc - plan.list_poc[1][0]);
-    // rate_estimate_qscale's B branch in x264's own types: float q0, q1, q (f_qp_avg_rc of the nearest references), double offsets; the result goes
-    // through qp2qscale and x264_ratecontrol_start's qscale2qp like every quantiser
-    float q0 = (float)h->slot_qp_rc[s0], q1 = (float)h->slot_qp_rc[s1], qf;
-    if (h->slot_ptype[s0] == PIC_BREF) q0 = (float)(q0 - pb_offset / 2);
-    if (h->slot_ptype[s1] == PIC_BREF) q1 = (float)(q1 - pb_offset / 2);
-    if (i0 && i1) qf = (float)((q0 + q1) / 2 + h->rc.ip_offset);
-    else if (i0) qf = q1;
-    else if (i1) qf = q0;
-    else qf = (q0 * dt1 + q1 * dt0) / (dt0 + dt1);
-    qf = (float)(qf + (pl.type == PIC_BREF ? pb_offset / 2 : pb_offset));
-    double q = rc_qscale2qp(rc_qp2qscale(qf));
-    q = q < p.rc.i_qp_min ? p.rc.i_qp_min : q > p.rc.i_qp_max ? p.rc.i_qp_max : q;
-    // x264_ratecontrol_start: accum_p_qp_update runs for every picture type — a B picture's quantiser enters the running average an I picture
-    // after P pictures takes its quantiser from
-    h->rc.accum_p_qp = h->rc.accum_p_qp * 0.95 + q;
-    h->rc.accum_p_norm = h->rc.accum_p_norm * 0.95 + 1.0;
-    *qp_float = q;
-    return clampi((int)(q + 0.5), p.rc.i_qp_min, p.rc.i_qp_max);
-}
-
 // ---- the picture path of sessions on the DPB model: plan, launch, finish --------------------------------------------------------------
 // One picture a call (encode_bmode), its batched variant whose pictures leave a call later (bmode_defer) and several pictures in flight (inflight_issue /
 // inflight_retire) are built from the same three steps; what they do differently is an argument or a branch here, each with the mode that needs it.
@@ -2404,10 +1984,10 @@ static void bmode_plan(x264_t *h, x264_t::PicPlan &f, x264gpu_encoder *gpu, long
     f.nal_ref_idc = plan.nal_ref_idc;
     x264gpu_pic &pic = f.pic;
     pic = plan.pic;
-    pic.qp = bmode_qp(h, pl, plan, &f.qpf);
+    const RateControl::BRefs near = { { pic.slot[0][0], pic.slot[1][0] }, { abs(pic.poc - plan.list_poc[0][0]), abs(pic.poc - plan.list_poc[1][0]) } };      // (read for a B picture)
+    pic.qp = h->rc.start(pl.type, pl.e.frame, pl.e.costs, &near, &f.qpf);
     // x264_ratecontrol_mb_qp: a macroblock's quantiser is round(rc->qpm + its AQ / macroblock-tree offset) with qpm the picture's FLOAT quantiser
     pic.qpm = near_qpm(f.qpf, pic.qp);
-    h->rc_frames++;
     const bool is_b = pl.type == PIC_B || pl.type == PIC_BREF;
     f.direct_auto_write = false;
     if (is_b && h->direct_mode != 1) {
@@ -2437,7 +2017,7 @@ static void bmode_plan(x264_t *h, x264_t::PicPlan &f, x264gpu_encoder *gpu, long
     else if (h->aq_mode >= 2 && h->aq_strength != 0.f) f.d_offsets = h->q_aq[(size_t)pl.e.slot];      // --aq-mode 2 / 3: the offsets computed when the picture arrived
     // (the serial path names a buffer only when there is one; a launch context is always told, "none" included)
     if (f.d_offsets || !serial) x264gpu_encoder_set_mb_qp_offsets(gpu, f.d_offsets);
-    if (plan.nal_ref_idc) { h->slot_qp_rc[pic.dst] = rc_qp_avg_rc((float)f.qpf, h->mbw, h->mbh); h->slot_ptype[pic.dst] = pl.type; }
+    if (plan.nal_ref_idc) h->rc.kept(pic.dst, f.qpf, pl.type);
     if (plan.nal_ref_idc) h->slot_l0ref0poc[pic.dst] = pic.nref[0] ? plan.list_poc[0][0] : INT_MIN;
     f.direct_char = is_b ? (pic.direct_temporal ? 't' : 's') : '-';
     f.sp = slice_params_base(h);
@@ -2482,36 +2062,16 @@ static int bmode_finish(x264_t *h, x264_t::PicPlan &f, const x264gpu_mb *mbs, co
     for (size_t i = 0; i < h->nals.size(); i++) if (types[i] == 1 || types[i] == 5) h->nals[i].i_ref_idc = f.nal_ref_idc;
     fill_pic_out(pic_out, x264_type_of(pl.type), idr, pl.e.pts, coded_dts(h, h->coded_count), &pl.e.img);
     if (h->ql.flags) h->ql.frame_end(p, h->hq[0], quality_type(pl.type), mean_mb_qp(mbs, (size_t)h->nmb), f.pic.poc, h->out.size());          // (h->hq[0]: downloaded with the records)
-    if (h->pass1 || h->pass2) {
-        // x264_ratecontrol_end: the picture's line of the statistics file / the second pass' account of what was spent against the plan
-        const long total = (long)h->out.size() * 8;
-        long imb = 0, pmb = 0, smb = 0;
-        double aqsum = 0;
+    // x264_ratecontrol_end; a session that writes statistics or follows a plan is told what the picture's macroblocks were
+    RateControl::PicStats ps;
+    if (h->rc.pass1 || h->rc.pass2) {
         for (size_t i = 0; i < (size_t)h->nmb; i++) {
             const x264gpu_mb &m = mbs[i];
-            if (m.type <= X264GPU_MB_I16x16) imb++; else if (m.type == X264GPU_MB_P_SKIP || m.type == X264GPU_MB_B_SKIP) smb++; else pmb++;
-            aqsum += m.qp;
+            if (m.type <= X264GPU_MB_I16x16) ps.imb++; else if (m.type == X264GPU_MB_P_SKIP || m.type == X264GPU_MB_B_SKIP) ps.smb++; else ps.pmb++;
         }
-        if (h->stat_file) {
-            const char t = idr ? 'I' : pl.type == PIC_I ? 'i' : pl.type == PIC_P ? 'P' : pl.type == PIC_BREF ? 'B' : 'b';
-            const long mv = h->last_stats.mv_bits, tex = h->last_stats.tex_bits, misc = total - mv - tex;
-            fprintf(h->stat_file, "in:%d out:%ld type:%c dur:%d cpbdur:%d q:%.2f aq:%.2f tex:%ld mv:%ld misc:%ld imb:%ld pmb:%ld smb:%ld d:%c ref:;\n", pl.e.frame, h->coded_count, t, 1, 1, f.qpf,
-                    aqsum / h->nmb, tex, mv, misc, imb, pmb, smb, h->last_direct_char);
-        }
-        if (h->pass2) {
-            h->p2_total_bits += (double)total;
-            if (pl.e.frame < (int)h->p2.size()) h->p2_expected_sum += p2_qscale2bits(h->p2[(size_t)pl.e.frame], rc_qp2qscale(f.qpf));
-        }
+        ps.aq_mean = mean_mb_qp(mbs, (size_t)h->nmb); ps.mv_bits = h->last_stats.mv_bits; ps.tex_bits = h->last_stats.tex_bits; ps.direct = h->last_direct_char;
     }
-    if (h->abr) {
-        // x264_ratecontrol_end: what the picture took moves the rate factor of the pictures to come (a B picture's quantiser is an offset of
-        // its neighbours': its bits count divided by pbratio)
-        const double bits = (double)h->out.size() * 8.0, pb = fabs(p.rc.f_pb_factor) > 0 ? fabs(p.rc.f_pb_factor) : 1.0;
-        const bool is_b = pl.type == PIC_B || pl.type == PIC_BREF;
-        h->rc.total_bits += bits;
-        h->rc.cplxr_sum += bits * rc_qp2qscale(rc_qp_avg_rc((float)f.qpf, h->mbw, h->mbh)) / (h->rc.last_rceq * (is_b ? pb : 1.0));
-        h->rc.wanted_bits_window += h->rc.bitrate / h->rc.fps;
-    }
+    h->rc.end(h->out.size(), pl.type, pl.e.frame, f.qpf, &ps);
     bmode_count(h, idr);
     return (int)h->out.size();
 }
@@ -2560,7 +2120,7 @@ static int bmode_defer(x264_t *h, x264_t::PicPlan &f, int bbuf, x264_nal_t **pp_
     d.i_type = x264_type_of(pl.type); d.b_keyframe = idr; d.pts = pl.e.pts; d.img = pl.e.img;
     d.qp = f.pic.qp; d.qpm = f.pic.qpm; d.scenecut = pl.e.scenecut; memcpy(d.costs, pl.e.costs, sizeof(d.costs));
     d.q_type = quality_type(pl.type); d.q_poc = f.pic.poc;
-    if (h->abr || h->pass1 || h->pass2) { xlog(&p, X264_LOG_ERROR, "x264_encoder_encode: a batched session cannot run rate control that reads the coded sizes\n"); h->failed = true; return -1; }
+    if (h->rc.reads_sizes()) { xlog(&p, X264_LOG_ERROR, "x264_encoder_encode: a batched session cannot run rate control that reads the coded sizes\n"); h->failed = true; return -1; }
     d.dts = coded_dts(h, h->coded_count);
     BatchGroup *g = h->batch;
     const SliceParams sp = f.sp;
@@ -2850,13 +2410,7 @@ void x264_encoder_close(x264_t *h)
         fprintf(stderr, "x264gpu host timing (DPB model), ms per picture over %.0f pictures: slice-type analysis %.2f, GPU hot path %.2f, download %.2f, entropy coding %.2f\n", h->t_b[4],
                 1e3 * h->t_b[0] / h->t_b[4], 1e3 * h->t_b[1] / h->t_b[4], 1e3 * h->t_b[2] / h->t_b[4], 1e3 * h->t_b[3] / h->t_b[4]);
     h->ql.log_summary(h->param);
-    if (h->stat_file) {
-        fclose(h->stat_file); h->stat_file = nullptr;
-        const std::string out = h->param.rc.psz_stat_out ? h->param.rc.psz_stat_out : "";
-        // x264_ratecontrol_delete: a second pass that stopped short of the first one's pictures keeps the complete statistics it read
-        if (h->pass2 && h->coded_count < (long)h->p2.size()) { remove((out + ".temp").c_str()); xlog(&h->param, X264_LOG_INFO, "2-pass: %ld of %d pictures coded: the statistics file keeps the first pass' lines\n", h->coded_count, (int)h->p2.size()); }
-        else if (!out.empty() && rename((out + ".temp").c_str(), out.c_str())) xlog(&h->param, X264_LOG_ERROR, "failed to rename \"%s.temp\" to \"%s\"\n", out.c_str(), out.c_str());
-    }
+    h->rc.close();
     for (size_t i = 0; i < h->lctx.size(); i++) {
         x264_t::LaunchCtx &c = h->lctx[i];
         if (c.stream) { x264gpu_stream_sync(c.stream); x264gpu_stream_destroy(c.stream); }
@@ -3079,9 +2633,9 @@ int x264host_last_decision(x264_t *h, int *qp, int *scenecut, int32_t costs[4])
  * returns the number of pictures planned (0: not a second pass) */
 int x264host_pass2_plan(x264_t *h, double *new_qscale, double *expected_bits, int n)
 {
-    if (!h || !h->pass2) return 0;
-    for (int i = 0; i < n && i < (int)h->p2.size(); i++) { if (new_qscale) new_qscale[i] = h->p2[(size_t)i].new_qscale; if (expected_bits) expected_bits[i] = h->p2[(size_t)i].expected_bits; }
-    return (int)h->p2.size();
+    if (!h || !h->rc.pass2) return 0;
+    for (int i = 0; i < n && i < h->rc.planned(); i++) { if (new_qscale) new_qscale[i] = h->rc.plan(i)->new_qscale; if (expected_bits) expected_bits[i] = h->rc.plan(i)->expected_bits; }
+    return h->rc.planned();
 }
 /* tests: the float quantiser (x264 rc->qpm) the last coded picture's macroblock quantisers were rounded from; 0 = its integer quantiser */
 float x264host_last_qpm(x264_t *h) { return h ? h->last_qpm : 0.f; }

@@ -8,6 +8,11 @@
 
 namespace x264host {
 
+void xlog(const x264_param_t *p, int level, const char *fmt, ...);          // the session's log (pf_log at its i_log_level; encoder.cpp)
+inline int clampi(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
+
+enum { PIC_IDR = 0, PIC_I = 1, PIC_P = 2, PIC_BREF = 3, PIC_B = 4 };
+
 struct SliceParams {
     int mbw, mbh;
     int slice_type;          // X264GPU_SLICE_I / _P

@@ -32,15 +32,6 @@ double x264host_ssim_db(double ssim)
 
 namespace x264host {
 
-static void qlog(const x264_param_t &p, int level, const char *fmt, ...)
-{
-    if (!p.pf_log || level > p.i_log_level) return;
-    va_list ap;
-    va_start(ap, fmt);
-    p.pf_log(p.p_log_private, level, fmt, ap);
-    va_end(ap);
-}
-
 static void appendf(std::string &s, const char *fmt, ...)
 {
     char buf[512];
@@ -63,8 +54,8 @@ void Quality::open(const x264_param_t &p, bool gop_slots)
     w = p.i_width; h = p.i_height;
     flags = (p.analyse.b_psnr ? X264GPU_QUALITY_PSNR : 0) | (p.analyse.b_ssim ? X264GPU_QUALITY_SSIM : 0);
     if (!flags) return;
-    if (!x264gpu_encoder_quality) { qlog(p, X264_LOG_WARNING, "psnr / ssim: the device library has no quality entry\n"); flags = 0; return; }
-    if (gop_slots) { qlog(p, X264_LOG_INFO, "psnr / ssim switched off in GOP-slot sessions (--threads %d: pictures of several GOPs are coded per call)\n", p.i_threads); flags = 0; }
+    if (!x264gpu_encoder_quality) { xlog(&p, X264_LOG_WARNING, "psnr / ssim: the device library has no quality entry\n"); flags = 0; return; }
+    if (gop_slots) { xlog(&p, X264_LOG_INFO, "psnr / ssim switched off in GOP-slot sessions (--threads %d: pictures of several GOPs are coded per call)\n", p.i_threads); flags = 0; }
 }
 
 int quality_queue(x264gpu_encoder *gpu, int flags, x264gpu_quality *d_out, void *stream)
@@ -99,7 +90,7 @@ void Quality::frame_end(const x264_param_t &p, const x264gpu_quality &q, int typ
     }
     have_last = true;
     frames++;
-    qlog(p, X264_LOG_DEBUG, "%s\n", line.c_str());
+    xlog(&p, X264_LOG_DEBUG, "%s\n", line.c_str());
 }
 
 std::string Quality::summary(const x264_param_t &p) const
@@ -132,7 +123,7 @@ void Quality::log_summary(const x264_param_t &p) const
     const std::string s = summary(p);
     for (size_t at = 0; at < s.size();) {
         const size_t nl = s.find('\n', at);
-        qlog(p, X264_LOG_INFO, "%s\n", s.substr(at, nl - at).c_str());
+        xlog(&p, X264_LOG_INFO, "%s\n", s.substr(at, nl - at).c_str());
         at = nl + 1;
     }
 }
