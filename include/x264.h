@@ -105,6 +105,7 @@ typedef struct x264_level_t {          /* codec.c:1596-1599: level_idc + dpb (in
     int bitrate;
     int cpb;
     int mv_range;
+    int mincr;                         /* Table A-1 MinCR (with mbps = MaxMBPS: the largest picture the level allows, read by the VBV) */
 } x264_level_t;
 extern const x264_level_t x264_levels[];
 

@@ -310,7 +310,12 @@ int  x264gpu_encode_frames(x264gpu_encoder *enc, const uint8_t *d_i420, int slic
 /* The same with explicit picture control, one entry of `pics` (host array) per stream: B pictures, b-pyramid, per-stream quantisers.
  * The streams of a call run in LOCK-STEP: slice type, POC, destination slot, keep flag, both reference lists, explicit weights and the
  * blind duplicate must be the same in every entry (EINVAL otherwise); qp and qpm may differ per stream.  B pictures need a CABAC
- * session with RD (cfg.cabac, cfg.rd).  x264gpu_encode_frames is this call with the sliding-window DPB of an I / P stream. */
+ * session with RD (cfg.cabac, cfg.rd).  x264gpu_encode_frames is this call with the sliding-window DPB of an I / P stream.
+ * RE-ISSUE: a picture may be issued twice.  Calling again with the same `dst`, lists, POC and source before any later picture — another qp / qpm is the point —
+ * gives exactly what a first call with those arguments gives: records, levels, reconstruction, the slot's side data (vectors, co-located data, DPB meta) and
+ * everything a later picture reads of it.  A picture reads nothing of its own destination slot, and what the encoder carries from call to call besides the DPB
+ * (the load-balance history, the first guesses of the --slices passes) changes how long a call takes, never its result.  The host's VBV stands on this: a
+ * picture whose coded size would under-run the buffer is coded again at a higher quantiser (host/encoder.cpp; tests/test_gpu_vbv.py pins it on the device). */
 int  x264gpu_encode_pictures(x264gpu_encoder *enc, const uint8_t *d_i420, const x264gpu_pic *pics,
                              x264gpu_mb *d_mb, int16_t *d_levels, void *stream);
 /* The levels of a call, packed IN PLACE for the trip to the host: of every macroblock's X264GPU_MB_LEVELS levels only the groups of 16 that hold a non-zero one stay,

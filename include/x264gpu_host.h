@@ -49,6 +49,14 @@ int x264host_last_decision(x264_t *h, int *qp, int *scenecut, int32_t costs[4]);
 float x264host_last_qpm(x264_t *h);
 /* ... the second pass' plan (init_pass2): per picture of the statistics file, display order, the planned quantiser scale and the bits expected before it; returns the count */
 int x264host_pass2_plan(x264_t *h, double *new_qscale, double *expected_bits, int n);
+/* VBV sessions (--vbv-maxrate / --vbv-bufsize): the rate control's view of the picture whose NAL units the last call returned.  out[12] = the buffer fill (bits)
+ * x264_ratecontrol_start saw (header NAL units already taken off) and the fill x264_ratecontrol_end left; the float quantiser before clip_qscale (rc->qp_novbv) and
+ * the one start returned; frame_size_planned; how often the picture was coded (1: it fitted at once); the size of the filler NAL unit behind it (bytes, --nal-hrd
+ * cbr); the float quantiser of the attempt that was emitted; the bits of the header NAL units; the buffer size (bits) and rate (bits / s) the VBV runs on (under
+ * --nal-hrd: what the HRD's value << scale notation keeps of the request); frame_size_maximum.  planned_type / planned_satd (cap entries each, may be NULL): the
+ * types (0 IDR, 1 I, 2 P, 4 B) and lookahead costs of the pictures coded after it as x264's vbv_lookahead left them with an I / P picture, closed by type -1;
+ * returns how many there are (0 for B pictures and without rc-lookahead), -1 when the session runs without VBV or has not returned a picture */
+int x264host_last_vbv(x264_t *h, double out[12], int *planned_type, int *planned_satd, int cap);
 /* how many pictures of the session may be in flight on the device at once (launch contexts over the shared DPB; 1: one picture a call) */
 int x264host_pictures_in_flight(x264_t *h);
 /* reconstructed picture of the last encoded frame as I420 (host memory) */

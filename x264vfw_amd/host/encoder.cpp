@@ -61,6 +61,15 @@ struct x264_t {
     int32_t *d_la = nullptr;             // device: the four sums of the last picture
     int keyint_min = 25;
     RateControl rc;                      // host/ratecontrol.hpp: which rate control the session runs, every picture's quantiser
+    // ---- VBV (--vbv-maxrate / --vbv-bufsize; open_vbv validates them): such a session runs serially on the DPB model; a picture whose coded size would under-run the
+    //      buffer is coded again at a higher quantiser (x264 re-quantises row by row while the picture is coded: the entropy coder runs behind the device here) ----
+    bool vbv = false;
+    int minigop_b = 0;                   // B pictures of the mini-GOP being coded (x264 frame->i_bframes)
+    // x264host_last_vbv: the picture whose NAL units the last call returned
+    struct VbvInfo { double fill_before = 0, fill_after = 0, qp_novbv = 0, qp_clipped = 0, frame_size_planned = 0, qp_final = 0; long overhead_bits = 0; int attempts = 0, filler = 0; bool valid = false; RateControl::Planned planned; } last_vbv;
+    // --nal-hrd: the HRD in the VUI, buffering-period and picture-timing SEI messages (Annex C / D / E)
+    HrdParams hrd;
+    long hrd_pics_since_bp = 0;          // coded pictures since the last buffering period (cpb_removal_delay counts them, two clock ticks each)
     double t_b[5] = { 0, 0, 0, 0, 0 };          // ... sessions on the DPB model: slice-type analysis, GPU hot path, download, entropy coding, pictures
     double t_phase[6] = { 0, 0, 0, 0, 0, 0 };   // X264GPU_HOST_TIMING=1: seconds in copy-in, upload + lookahead, GPU, download, entropy coding, calls
     // ---- lookahead queue (threads 1): pictures wait here rc-lookahead deep when the macroblock-tree needs to see what follows them ----
@@ -139,6 +148,7 @@ struct x264_t {
     struct BEntry { int64_t pts; int frame; int slot; int forced; int scenecut; int32_t costs[4]; x264_image_t img;      // forced: 0 auto, 1 I, 2 IDR
                     int type = 0; int b_scenecut = 1;         // slicetype analysis: the type decided so far (ST_*), "may still be a real scene cut"
                     Dpb::LumaWeight w;                        // x264_weights_analyse's luma weight of reference 0 when the picture is coded as P (--weightp)
+                    RateControl::Planned planned;             // VBV with rc-lookahead: the types and costs of the pictures coded after this one (x264 i_planned_type / i_planned_satd)
                     float weighted_cost_delta[18] = { 0 }; }; // f_weighted_cost_delta[distance - 1]: weighted / unweighted cost where the fake analysis found a luma weight
     // x264's lookahead in its own structure (x264_slicetype_analyse: scenecut against the last non-B picture with flash detection, --b-adapt 1)
     // on the device's frame costs of arbitrary (p0, p1, b) triples; the half-resolution planes of a queued picture live in the slicetype object's
@@ -171,7 +181,7 @@ struct x264_t {
     // a picture of a session on the DPB model between plan and finish: what was decided for it, what the device is told, what the slice writer is told;
     // with several pictures in flight also its launch context and the DPB slots it reads or writes
     struct PicPlan { BPlanned pl; x264gpu_pic pic; SliceParams sp; int nal_ref_idc = 0; double qpf = 0; const float *d_offsets = nullptr; bool direct_auto_write = false; char direct_char = '-';
-                     int ctx = 0; unsigned slots_used = 0; };
+                     int ctx = 0; unsigned slots_used = 0; bool last_minigop_b = false; };
     void *ev_la = nullptr;               // the default stream's position when a picture is issued: its upload, offsets and lowres vectors are complete behind it
     std::vector<LaunchCtx> lctx; std::deque<PicPlan> fl; int inflight = 1; int slot_writer[8] = { -1, -1, -1, -1, -1, -1, -1, -1 }; int last_retired_slot = -1;
     std::deque<BEntry> bq;
@@ -505,6 +515,7 @@ static SpsParams make_sps(const x264_t *h)
     s.constraint_set0 = h->profile_idc == 66; s.constraint_set1 = h->profile_idc <= 77;
     s.mv_range = h->param.analyse.i_mv_range;
     if (h->dpbmode) { s.num_ref_frames = h->dpb.max_dpb; s.log2_max_poc_lsb = h->log2_max_poc_lsb; s.num_reorder_frames = h->dpb.num_reorder; }
+    s.hrd = h->hrd;
     return s;
 }
 static PpsParams make_pps(const x264_t *h)
@@ -542,13 +553,27 @@ static void write_sets(const x264_t *h, std::vector<uint8_t> &bytes, std::vector
 // ---- the steps every session mode takes for a coded picture ----
 // what opens the access unit of a picture of type PIC_*: the delimiter under --aud, and in front of an IDR picture (b_repeat_headers) the parameter sets, with the
 // version SEI when the caller says so (sessions that write into h->out: until it has been sent once; GOP slots: in the stream's first GOP).  true: the sets were written
-static bool begin_access_unit(const x264_t *h, std::vector<uint8_t> &bytes, std::vector<size_t> &off, std::vector<int> &types, int pic_type, bool sei)
+// Under --nal-hrd (tm: sessions with VBV on the DPB model) a keyframe also carries the buffering-period SEI behind its parameter sets, and every picture the
+// picture-timing SEI in front of its slices
+struct AuTiming { uint32_t initial_cpb_removal_delay, initial_cpb_removal_delay_offset, cpb_removal_delay, dpb_output_delay; };
+static bool begin_access_unit(const x264_t *h, std::vector<uint8_t> &bytes, std::vector<size_t> &off, std::vector<int> &types, int pic_type, bool sei, const AuTiming *tm = nullptr)
 {
     const x264_param_t &p = h->param;
-    if (p.b_aud) { off.push_back(bytes.size()); types.push_back(9); write_aud(bytes, pic_type <= PIC_I ? 0 : pic_type == PIC_P ? 1 : 2, p.b_annexb != 0); }
-    if (pic_type != PIC_IDR || !p.b_repeat_headers) return false;
-    write_sets(h, bytes, off, types, sei);
-    return true;
+    const bool annexb = p.b_annexb != 0, sets = pic_type == PIC_IDR && p.b_repeat_headers;
+    if (p.b_aud) { off.push_back(bytes.size()); types.push_back(9); write_aud(bytes, pic_type <= PIC_I ? 0 : pic_type == PIC_P ? 1 : 2, annexb); }
+    if (!tm) {
+        if (sets) write_sets(h, bytes, off, types, sei);
+        return sets;
+    }
+    if (sets) write_sets(h, bytes, off, types, false);
+    if (pic_type == PIC_IDR) {
+        off.push_back(bytes.size()); types.push_back(6);
+        write_sei_buffering_period(bytes, h->hrd, p.i_sps_id, tm->initial_cpb_removal_delay, tm->initial_cpb_removal_delay_offset, annexb, bytes.empty());
+    }
+    if (sets && sei) { off.push_back(bytes.size()); types.push_back(6); write_sei_version(bytes, kSeiText, annexb); }
+    off.push_back(bytes.size()); types.push_back(6);
+    write_sei_pic_timing(bytes, h->hrd, tm->cpb_removal_delay, tm->dpb_output_delay, annexb, bytes.empty());
+    return sets;
 }
 // the slices of the picture behind what the access unit holds so far, their NAL units tagged 5 (IDR) or 1
 static void write_slices(std::vector<uint8_t> &bytes, std::vector<size_t> &off, std::vector<int> &types, const SliceParams &sp, int slices, const x264gpu_mb *mbs, const int16_t *levels,
@@ -648,7 +673,6 @@ static void open_toolset(x264_t *h)
     if (p.b_interlaced) { xlog(&p, X264_LOG_WARNING, "interlaced coding is not implemented in the MI355X path: progressive\n"); p.b_interlaced = 0; }
     if (p.b_constrained_intra) { xlog(&p, X264_LOG_WARNING, "constrained-intra is not implemented in the MI355X path: off\n"); p.b_constrained_intra = 0; }
     if (p.b_intra_refresh) { xlog(&p, X264_LOG_WARNING, "intra-refresh is not implemented in the MI355X path: off\n"); p.b_intra_refresh = 0; }
-    if (p.i_nal_hrd) { xlog(&p, X264_LOG_WARNING, "nal-hrd needs VBV, which is not implemented in the MI355X path: none\n"); p.i_nal_hrd = 0; }
     // --sliced-threads / --tune zerolatency: i_threads is the number of slices per picture (x264 validate_parameters: at most one per four
     // macroblock rows; auto = as many as that allows, where x264 would count host cores) and there is one GOP in flight
     h->slices = 1;
@@ -673,6 +697,51 @@ static void open_toolset(x264_t *h)
         h->slices = p.i_slice_count; h->slices_plain = h->slices > 1;
     } else if (!p.b_sliced_threads) p.i_slice_count = 0;
     p.i_threads = clampi(p.i_threads, 1, 256);                 // --threads G: GOPs coded in lock-step (1 = no delay)
+}
+
+// VBV: x264 validate_parameters' rules for --vbv-maxrate / --vbv-bufsize / --vbv-init / --nal-hrd, and which sessions run it here (single-pass CRF / ABR, one
+// picture at a time on the DPB model).  Leaves the effective values in the parameters and h->vbv; runs before the picture structure is settled
+static void open_vbv(x264_t *h)
+{
+    x264_param_t &p = h->param;
+    h->vbv = false;
+    if (p.rc.i_vbv_max_bitrate > 0 || p.rc.i_vbv_buffer_size > 0) {
+        // (sessions that end up at a constant quantiser: open_quantisers maps CRF below 1 and ABR without a bitrate to it)
+        const bool cqp = p.rc.i_rc_method == X264_RC_CQP || (p.rc.i_rc_method == X264_RC_CRF && p.rc.f_rf_constant < 1.0f) || (p.rc.i_rc_method == X264_RC_ABR && p.rc.i_bitrate <= 0);
+        const char *be = getenv("X264GPU_BATCH");
+        const char *why = p.i_threads > 1 ? "threads 1 (GOP slots are coded in lock-step, before the sizes of the pictures in front of them are known)" :
+                          be && atoi(be) >= 2 ? "a session of its own (X264GPU_BATCH codes the sessions of a group in lock-step)" :
+                          p.rc.b_stat_read ? "a single pass (the second pass' VBV plan, x264's vbv_pass2, is not implemented)" : nullptr;
+        if (cqp) xlog(&p, X264_LOG_WARNING, "VBV is incompatible with constant QP, ignored.\n");
+        else if (why) xlog(&p, X264_LOG_WARNING, "VBV (vbv-maxrate / vbv-bufsize) needs %s in the MI355X path: unconstrained\n", why);
+        else {
+            const bool is_abr = p.rc.i_rc_method == X264_RC_ABR;
+            if (p.rc.i_vbv_buffer_size > 0 && p.rc.i_vbv_max_bitrate <= 0) {
+                if (is_abr) { xlog(&p, X264_LOG_WARNING, "VBV maxrate unspecified, assuming CBR\n"); p.rc.i_vbv_max_bitrate = p.rc.i_bitrate; }
+                else { xlog(&p, X264_LOG_WARNING, "VBV bufsize set but maxrate unspecified, ignored\n"); p.rc.i_vbv_buffer_size = 0; }
+            } else if (p.rc.i_vbv_max_bitrate > 0 && p.rc.i_vbv_buffer_size <= 0) { xlog(&p, X264_LOG_WARNING, "VBV maxrate specified, but no bufsize, ignored\n"); p.rc.i_vbv_max_bitrate = 0; }
+            if (p.rc.i_vbv_max_bitrate > 0 && p.rc.i_vbv_buffer_size > 0) {
+                if (is_abr && p.rc.i_vbv_max_bitrate < p.rc.i_bitrate) { xlog(&p, X264_LOG_WARNING, "max bitrate less than average bitrate, assuming CBR\n"); p.rc.i_bitrate = p.rc.i_vbv_max_bitrate; }
+                // x264_ratecontrol_init_reconfigurable: at least one picture's worth of buffer; --vbv-init above 1 is kbit, and the buffer starts with at least one picture's arrival
+                const double fps = p.i_fps_num ? (double)p.i_fps_num / p.i_fps_den : 25.0;
+                if (p.rc.i_vbv_buffer_size < (int)(p.rc.i_vbv_max_bitrate / fps)) {
+                    p.rc.i_vbv_buffer_size = (int)(p.rc.i_vbv_max_bitrate / fps);
+                    xlog(&p, X264_LOG_WARNING, "VBV buffer size cannot be smaller than one frame, using %d kbit\n", p.rc.i_vbv_buffer_size);
+                }
+                auto clipf = [](float v, float lo, float hi) { return v < lo ? lo : v > hi ? hi : v; };
+                if (p.rc.f_vbv_buffer_init > 1.f) p.rc.f_vbv_buffer_init = clipf(p.rc.f_vbv_buffer_init / p.rc.i_vbv_buffer_size, 0.f, 1.f);
+                const float one = (float)((p.rc.i_vbv_max_bitrate * 1000.0 / fps) / (p.rc.i_vbv_buffer_size * 1000.0));
+                p.rc.f_vbv_buffer_init = clipf(p.rc.f_vbv_buffer_init > one ? p.rc.f_vbv_buffer_init : one, 0.f, 1.f);
+                h->vbv = true;
+            }
+        }
+    }
+    if (!h->vbv) { p.rc.i_vbv_max_bitrate = 0; p.rc.i_vbv_buffer_size = 0; }
+    p.i_nal_hrd = clampi(p.i_nal_hrd, X264_NAL_HRD_NONE, X264_NAL_HRD_CBR);
+    if (p.i_nal_hrd && !h->vbv) { xlog(&p, X264_LOG_WARNING, "NAL HRD parameters require VBV parameters\n"); p.i_nal_hrd = X264_NAL_HRD_NONE; }
+    if (p.i_nal_hrd == X264_NAL_HRD_CBR && (p.rc.i_rc_method != X264_RC_ABR || p.rc.i_vbv_max_bitrate != p.rc.i_bitrate)) {
+        xlog(&p, X264_LOG_WARNING, "CBR HRD requires constant bitrate\n"); p.i_nal_hrd = X264_NAL_HRD_VBR;
+    }
 }
 
 // picture structure: B pictures, --weightp, and whether the session runs on the DPB model or in a batch
@@ -711,7 +780,7 @@ static void open_modes(x264_t *h)
     }
     if (p.analyse.i_weighted_pred == X264_WEIGHTP_SMART && p.i_frame_reference < 2) p.analyse.i_weighted_pred = X264_WEIGHTP_NONE;      // a duplicate needs two references (x264: never placed)
     h->weightp = p.analyse.i_weighted_pred;
-    h->dpbmode = h->bframes > 0 || h->weightp == X264_WEIGHTP_SMART;
+    h->dpbmode = h->bframes > 0 || h->weightp == X264_WEIGHTP_SMART || h->vbv;          // (VBV: the path that codes one picture at a time and can code it again)
     if (const char *be = getenv("X264GPU_BATCH")) {
         // cross-session batcher: this session joins (or starts) a group of N sessions coded in lock-step, if its picture structure is fixed
         const int bn = atoi(be);
@@ -756,8 +825,11 @@ static void open_quantisers(x264_t *h)
     rc.parse_zones(p);
     if (!rc.zones.empty()) xlog(&p, X264_LOG_INFO, "%d zone%s (quantiser / bitrate factor per range of pictures)\n", (int)rc.zones.size(), rc.zones.size() > 1 ? "s" : "");
     if (!rc.zones.empty() && rc.pass2) xlog(&p, X264_LOG_WARNING, "zones are not applied to the second pass' plan in the MI355X path (the first pass and single-pass sessions honour them)\n");
-    if (p.rc.i_vbv_max_bitrate > 0 || p.rc.i_vbv_buffer_size > 0) xlog(&p, X264_LOG_WARNING, "VBV (vbv-maxrate / vbv-bufsize) is not implemented in the MI355X path: unconstrained\n");
-    p.rc.i_vbv_max_bitrate = 0; p.rc.i_vbv_buffer_size = 0;
+    if (h->vbv && (!rc.by_cost() || rc.pass2)) {          // (open_vbv admitted a session whose rate control fell back since)
+        xlog(&p, X264_LOG_WARNING, "VBV is incompatible with constant QP, ignored.\n");
+        h->vbv = false; p.rc.i_vbv_max_bitrate = 0; p.rc.i_vbv_buffer_size = 0; p.i_nal_hrd = X264_NAL_HRD_NONE;
+    }
+    rc.vbv = h->vbv; rc.filler = h->vbv && p.i_nal_hrd == X264_NAL_HRD_CBR;
     if (p.analyse.i_noise_reduction) { xlog(&p, X264_LOG_WARNING, "nr (noise reduction) is not implemented in the MI355X path: nr 0\n"); p.analyse.i_noise_reduction = 0; }
     if (p.i_slice_max_size > 0 || p.i_slice_max_mbs > 0) { xlog(&p, X264_LOG_WARNING, "slice-max-size / slice-max-mbs are not implemented in the MI355X path (slices are cut by --slices N or slice threads only)\n"); p.i_slice_max_size = p.i_slice_max_mbs = 0; }
     if (p.b_fake_interlaced || p.b_pic_struct) { xlog(&p, X264_LOG_WARNING, "fake-interlaced / pic-struct are not implemented in the MI355X path: off\n"); p.b_fake_interlaced = p.b_pic_struct = 0; }
@@ -768,7 +840,9 @@ static void open_quantisers(x264_t *h)
     if (p.rc.i_rc_method == X264_RC_CQP || p.rc.i_lookahead <= 0) p.rc.b_mb_tree = 0;
     if (p.rc.b_mb_tree && p.i_threads > 1) { xlog(&p, X264_LOG_INFO, "mbtree needs threads 1 (GOPs in lock-step are coded before what follows them is seen): mbtree 0\n"); p.rc.b_mb_tree = 0; }
     p.rc.b_mb_tree = p.rc.b_mb_tree != 0;
-    p.rc.i_lookahead = p.rc.b_mb_tree ? clampi(p.rc.i_lookahead, 1, p.i_keyint_max < 250 ? (p.i_keyint_max > 1 ? p.i_keyint_max : 1) : 250) : 0;
+    // (VBV plans over the lookahead too, with or without the tree: x264's vbv_lookahead; rc-lookahead 0 leaves it the reactive algorithm)
+    { const int cap = p.i_keyint_max < 250 ? (p.i_keyint_max > 1 ? p.i_keyint_max : 1) : 250;
+      p.rc.i_lookahead = p.rc.b_mb_tree ? clampi(p.rc.i_lookahead, 1, cap) : h->vbv ? clampi(p.rc.i_lookahead, 0, cap) : 0; }
     p.rc.i_aq_mode = clampi(p.rc.i_aq_mode, 0, 3);
     if (p.rc.i_aq_mode > X264_AQ_VARIANCE && (!h->dpbmode || getenv("X264GPU_BATCH"))) {
         xlog(&p, X264_LOG_WARNING, "aq-mode %d needs B-frames or weightp 2 (the DPB-model path, one session a device encoder) in the MI355X path: aq-mode 1\n", p.rc.i_aq_mode); p.rc.i_aq_mode = X264_AQ_VARIANCE;
@@ -802,7 +876,27 @@ static void open_quantisers(x264_t *h)
         h->level_idc = p.i_level_idc > 0 ? p.i_level_idc : pick_level(&p, h->nmb, h->dpb.max_dpb);
         p.i_level_idc = h->level_idc;
     }
-
+    if (h->vbv && p.i_nal_hrd) {
+        // x264_ratecontrol_init_reconfigurable, "Init HRD": rate and size in the value / scale notation (the VBV then runs on what the notation keeps of them), the
+        // lengths of the delay fields from the longest delays the session can produce (a buffering period is at most keyint pictures long, "arbitrary" MAX_DURATION 0.5 s
+        // a picture — and never shorter than the two ticks a picture that constant-frame-rate pictures really take)
+        HrdParams &hr = h->hrd;
+        const int rate = p.rc.i_vbv_max_bitrate * 1000, size = p.rc.i_vbv_buffer_size * 1000;
+        hr.present = 1; hr.cbr = p.i_nal_hrd == X264_NAL_HRD_CBR;
+        hr.bit_rate_scale = clampi(__builtin_ctz((unsigned)rate) - 6, 0, 15); hr.bit_rate_value = rate >> (hr.bit_rate_scale + 6); hr.bit_rate_unscaled = hr.bit_rate_value << (hr.bit_rate_scale + 6);
+        hr.cpb_size_scale = clampi(__builtin_ctz((unsigned)size) - 4, 0, 15); hr.cpb_size_value = size >> (hr.cpb_size_scale + 4); hr.cpb_size_unscaled = hr.cpb_size_value << (hr.cpb_size_scale + 4);
+        const double ticks = 0.5 * (double)(p.i_timebase_den * 2) / p.i_timebase_num;
+        double max_cpb = p.i_keyint_max * ticks; if (max_cpb < 2.0 * p.i_keyint_max) max_cpb = 2.0 * p.i_keyint_max;
+        double max_dpb = h->dpb.max_dpb * ticks; if (max_dpb < 2.0 * (h->dpb.num_reorder + h->bframes + 2)) max_dpb = 2.0 * (h->dpb.num_reorder + h->bframes + 2);
+        const int max_cpb_output_delay = max_cpb < (double)INT_MAX ? (int)max_cpb : INT_MAX, max_dpb_output_delay = max_dpb < (double)INT_MAX ? (int)max_dpb : INT_MAX;
+        const int max_delay = (int)(90000.0 * (double)hr.cpb_size_unscaled / hr.bit_rate_unscaled + 0.5);
+        auto bits = [](int v) { return v > 0 ? 32 - __builtin_clz((unsigned)v) : 0; };
+        hr.initial_cpb_removal_delay_length = 2 + clampi(bits(max_delay), 4, 22);
+        hr.cpb_removal_delay_length = clampi(bits(max_cpb_output_delay), 4, 31);
+        hr.dpb_output_delay_length = clampi(bits(max_dpb_output_delay), 4, 31);
+        rc.hrd_rate = hr.bit_rate_unscaled; rc.hrd_size = hr.cpb_size_unscaled;
+        if (hr.bit_rate_value < 1 || hr.cpb_size_value < 1) { xlog(&p, X264_LOG_WARNING, "nal-hrd: rate or size too small for the HRD's notation: none\n"); hr = HrdParams(); p.i_nal_hrd = X264_NAL_HRD_NONE; rc.hrd_rate = rc.hrd_size = 0; rc.filler = false; }
+    }
 }
 
 // what the device encoder(s) are created with; settles the GOP-slot count, --mvrange and the pictures in flight on the way
@@ -936,7 +1030,7 @@ static bool open_lookahead(x264_t *h)
     // lookahead queue: rc-lookahead pictures are held back when the macroblock-tree is on (x264's sync lookahead), none otherwise
     h->mbtree = p.rc.b_mb_tree && h->la != nullptr;
     h->weightp_fake = !h->weightp && h->mbtree && p.analyse.b_psy && h->dpbmode;          // x264 validate_parameters: X264_WEIGHTP_FAKE (sessions on the DPB model: the others' tree has no weight analysis)
-    h->L = h->mbtree ? p.rc.i_lookahead : 0;
+    h->L = h->mbtree || h->vbv ? p.rc.i_lookahead : 0;
     // pictures are held back anyway and the quantisers do not depend on coded sizes: overlap the GPU stage of the next picture with
     // the entropy coding of this one (one more picture of delay); X264GPU_HOST_PIPELINE=0 keeps the two stages in one call
     { const char *pe = getenv("X264GPU_HOST_PIPELINE"); h->pipeline = h->G == 1 && h->L > 0 && h->rc.crf && !(pe && pe[0] == '0'); }
@@ -960,10 +1054,19 @@ static bool open_lookahead(x264_t *h)
     h->badapt = h->bframes ? p.i_bframe_adaptive : 0;
     // (sessions with a fixed picture structure — no scenecut, b-adapt 0, no mbtree — run without the lookahead object: no fade weights and no
     // lookahead vectors as search candidates there; that is also what makes the sessions of a batch equal to the same sessions run alone)
-    if (h->dpbmode && (h->badapt || p.i_scenecut_threshold > 0 || h->mbtree)) {
+    h->rc.vbv_lookahead = h->vbv && h->L > 0;
+    if (h->vbv) {
+        p.rc.i_lookahead = h->L;
+        xlog(&p, X264_LOG_INFO, "VBV: maxrate %d kbit/s, bufsize %d kbit, init %.3f%s; %s; x264's row-level re-quantisation is replaced by picture re-encode: a picture that would under-run the buffer is coded again at a higher quantiser\n",
+             p.rc.i_vbv_max_bitrate, p.rc.i_vbv_buffer_size, (double)p.rc.f_vbv_buffer_init, p.i_nal_hrd == X264_NAL_HRD_CBR ? ", nal-hrd cbr" : p.i_nal_hrd ? ", nal-hrd vbr" : "",
+             h->L > 0 ? "quantisers planned over the lookahead" : "rc-lookahead 0: the reactive algorithm");
+        if (p.b_vfr_input) xlog(&p, X264_LOG_INFO, "VBV: variable frame rate durations are not implemented in the MI355X path: every picture stays in the buffer for 1 / fps\n");
+        if (p.rc.f_rf_constant_max > 0) xlog(&p, X264_LOG_WARNING, "crf-max is not implemented in the MI355X path: ignored\n");
+    }
+    if (h->dpbmode && (h->badapt || p.i_scenecut_threshold > 0 || h->mbtree || h->rc.vbv_lookahead)) {
         // x264's own lookahead structure: frame costs of (p0, p1, b) triples on the half-resolution planes (x264_slicetype_analyse)
         if (x264gpu_slicetype_create(&h->st, p.i_width, p.i_height, 1, h->Q, h->bframes, p.analyse.i_me_method, p.analyse.i_subpel_refine, p.analyse.i_me_range,
-                                     p.analyse.b_weighted_bipred, p.analyse.i_mv_range, h->mbtree ? 1 : 0) != X264GPU_OK) {
+                                     p.analyse.b_weighted_bipred, p.analyse.i_mv_range, h->mbtree || h->vbv ? 1 : 0) != X264GPU_OK) {
             xlog(&p, X264_LOG_ERROR, "GPU lookahead setup failed: %s\n", x264gpu_last_error());
             return false;
         }
@@ -1043,6 +1146,7 @@ x264_t *x264_encoder_open(x264_param_t *param)
     if (!p.i_timebase_num || !p.i_timebase_den) { p.i_timebase_num = p.i_fps_den; p.i_timebase_den = p.i_fps_num; }
 
     open_toolset(h);
+    open_vbv(h);
     open_modes(h);
     open_quantisers(h);
     if (!open_device(h) || !open_lookahead(h) || !h->rc.open(p, h->mbw, h->mbh, h->bframes, h->qp_i, h->qp_p)) { x264_encoder_close(h); return nullptr; }
@@ -1742,6 +1846,46 @@ static void st_path(StFrames &F, int length, char (*best_paths)[ST_PATH_MAX + 1]
     best_paths[length % 17][length] = 0;
 }
 
+// x264's vbv_lookahead: the pictures of the window in coding order (each non-B picture, then the B pictures in front of it) with the types the analysis gave them
+// and their frame costs (vbv_frame_cost: the AQ-weighted ones in AQ sessions), left with the picture that is coded next — the first non-B picture of the window,
+// or (keyframe) frames[0] itself, a keyframe that has just been decided.  The window's last picture is not part of the plan, as in x264
+static int st_vbv_frame_cost(StFrames &F, int p0, int p1, int b)
+{
+    x264_t *h = F.h;
+    int32_t cost = st_cost(F, p0, p1, b);
+    if (!h->failed && h->aq_strength != 0.f && (h->mbtree || h->st_aq_costs) &&
+        x264gpu_slicetype_cost_aq(h->st, F.f[(size_t)b]->slot, b - p0, p1 - b, &cost, nullptr) != X264GPU_OK) {
+        xlog(&h->param, X264_LOG_ERROR, "lookahead frame cost failed: %s\n", x264gpu_last_error());
+        h->failed = true;
+    }
+    return cost;
+}
+static void st_vbv_lookahead(StFrames &F, int num_frames, bool keyframe)
+{
+    auto isb = [&](int i) { const int t = F.f[(size_t)i]->type; return t == ST_B || t == ST_BREF; };
+    int last_nonb = 0, cur_nonb = 1, idx = 0;
+    while (cur_nonb < num_frames && isb(cur_nonb)) cur_nonb++;
+    const int next_nonb = keyframe ? last_nonb : cur_nonb;
+    RateControl::Planned &pl = F.f[(size_t)next_nonb]->planned;
+    while (cur_nonb < num_frames && idx < RateControl::PLAN_MAX && !F.h->failed) {
+        if (next_nonb != cur_nonb) {          // the P / I picture (its cost as the type it was given; not next_nonb's own)
+            const int t = F.f[(size_t)cur_nonb]->type;
+            const bool is_i = t == ST_I || t == ST_IDR;
+            pl.satd[idx] = st_vbv_frame_cost(F, is_i ? cur_nonb : last_nonb, cur_nonb, cur_nonb);
+            pl.type[idx] = t == ST_IDR ? PIC_IDR : t == ST_I ? PIC_I : PIC_P;
+            idx++;
+        }
+        for (int i = last_nonb + 1; i < cur_nonb && idx < RateControl::PLAN_MAX; i++, idx++) {          // the B pictures, coded behind it
+            pl.satd[idx] = st_vbv_frame_cost(F, last_nonb, cur_nonb, i);
+            pl.type[idx] = PIC_B;
+        }
+        last_nonb = cur_nonb;
+        cur_nonb++;
+        while (cur_nonb <= num_frames && isb(cur_nonb)) cur_nonb++;
+    }
+    pl.type[idx] = RateControl::PLAN_END;
+}
+
 static void st_analyse(x264_t *h, StFrames &F, int framecnt, bool keyframe = false)
 {
     const x264_param_t &p = h->param;
@@ -1842,6 +1986,8 @@ static void st_analyse(x264_t *h, StFrames &F, int framecnt, bool keyframe = fal
             if (type(j) == ST_IDR) { last_keyframe = F.f[(size_t)j]->frame; if (j > 1 && (type(j - 1) == ST_B || type(j - 1) == ST_BREF)) type(j - 1) = ST_P; }
         }
     }
+    if (h->rc.vbv_lookahead) st_vbv_lookahead(F, num_frames, keyframe);
+    if (h->failed) return;
     // the pictures behind the first mini-GOP are decided again when their turn comes
     for (int j = reset_start; j <= framecnt; j++) type(j) = forced(j);
 }
@@ -1863,7 +2009,7 @@ static bool st_decide(x264_t *h, bool flushing, int &j_out, int &closing_out)
             e.type = t == 'I' ? ST_IDR : t == 'i' ? ST_I : t == 'P' ? ST_P : ST_B;
         }
     } else
-    if (h->have_last_nonb && ((h->bframes && h->badapt) || p.i_scenecut_threshold || h->mbtree)) {
+    if (h->have_last_nonb && ((h->bframes && h->badapt) || p.i_scenecut_threshold || h->mbtree || h->rc.vbv_lookahead)) {
         StFrames F;
         F.h = h;
         F.f.push_back(&h->last_nonb);
@@ -1929,9 +2075,9 @@ static bool bmode_decide(x264_t *h, bool flushing)
         if (bref >= 0) h->bcoding.push_back({ h->bq[(size_t)bref], PIC_BREF });
         for (int i = 0; i < j; i++) if (i != bref) h->bcoding.push_back({ h->bq[(size_t)i], PIC_B });
         h->bq.erase(h->bq.begin(), h->bq.begin() + j + 1);
-        if (h->mbtree && (closing == PIC_IDR || closing == PIC_I)) {
-            // x264 lookahead_slicetype_decide: "for MB-tree, we have to perform propagation analysis on I-frames too" — the analysis again
-            // with the keyframe as frames[0]; it decides nothing, its tree reaches the keyframe itself
+        if ((h->mbtree || h->rc.vbv_lookahead) && (closing == PIC_IDR || closing == PIC_I)) {
+            // x264 lookahead_slicetype_decide: "for MB-tree and VBV lookahead, we have to perform propagation analysis on I-frames too" — the analysis again
+            // with the keyframe as frames[0]; it decides nothing, its tree reaches the keyframe itself, its plan is the keyframe's
             StFrames F;
             F.h = h;
             F.f.push_back(&h->last_nonb);
@@ -1940,8 +2086,9 @@ static bool bmode_decide(x264_t *h, bool flushing)
             for (int i = 0; i < framecnt; i++) F.f.push_back(&h->bq[(size_t)i]);
             h->last_nonb.type = closing == PIC_IDR ? ST_IDR : ST_I;
             if (framecnt > 0) st_analyse(h, F, framecnt, true);
-            else st_macroblock_tree(h, F, 0, true);
+            else if (h->mbtree) st_macroblock_tree(h, F, 0, true);
             if (h->failed) return false;
+            h->bcoding.front().e.planned = h->last_nonb.planned;          // (the closing picture was queued before its plan was made)
         }
         return true;
     }
@@ -1961,6 +2108,32 @@ static bool bmode_decide(x264_t *h, bool flushing)
     for (int i = 0; i < j; i++) if (i != bref) h->bcoding.push_back({ h->bq[(size_t)i], PIC_B });
     h->bq.erase(h->bq.begin(), h->bq.begin() + j + 1);
     return true;
+}
+
+// the bits of the NAL units a picture's access unit opens with (VBV: x264_ratecontrol_start's overhead)
+// --nal-hrd: the delays a picture's SEI messages carry, from the buffer's state in front of it (Annex C: removal times are cpb_removal_delay clock ticks behind
+// the last buffering-period picture's, two ticks a picture; a picture is output dpb_output_delay ticks after its removal, which puts the output times in display
+// order two ticks apart: 2 x (display index - coding index + the reorder depth))
+static bool au_timing(const x264_t *h, const x264_t::BPlanned &pl, AuTiming &tm)
+{
+    if (!h->hrd.present) return false;
+    const double rate = h->hrd.bit_rate_unscaled, size = h->hrd.cpb_size_unscaled;
+    const double fill = h->rc.buffer_fill_final < 0 ? 0 : h->rc.buffer_fill_final > size ? size : h->rc.buffer_fill_final;
+    tm.initial_cpb_removal_delay = (uint32_t)floor(90000.0 * fill / rate);
+    tm.initial_cpb_removal_delay_offset = (uint32_t)floor(90000.0 * size / rate) - tm.initial_cpb_removal_delay;
+    tm.cpb_removal_delay = (uint32_t)(2 * h->hrd_pics_since_bp);
+    const long delay = 2 * ((long)pl.e.frame - h->coded_count + h->dpb.num_reorder);
+    tm.dpb_output_delay = (uint32_t)(delay > 0 ? delay : 0);
+    return true;
+}
+// the bits of the NAL units a picture's access unit opens with (VBV: x264_ratecontrol_start's overhead)
+static long au_overhead_bits(const x264_t *h, const x264_t::BPlanned &pl)
+{
+    std::vector<uint8_t> bytes; std::vector<size_t> off; std::vector<int> types;
+    AuTiming tm;
+    const bool timed = au_timing(h, pl, tm);
+    begin_access_unit(h, bytes, off, types, pl.type, !h->sei_sent, timed ? &tm : nullptr);
+    return (long)bytes.size() * 8;
 }
 
 // ---- the picture path of sessions on the DPB model: plan, launch, finish --------------------------------------------------------------
@@ -1985,10 +2158,22 @@ static void bmode_plan(x264_t *h, x264_t::PicPlan &f, x264gpu_encoder *gpu, long
     x264gpu_pic &pic = f.pic;
     pic = plan.pic;
     const RateControl::BRefs near = { { pic.slot[0][0], pic.slot[1][0] }, { abs(pic.poc - plan.list_poc[0][0]), abs(pic.poc - plan.list_poc[1][0]) } };      // (read for a B picture)
+    const bool is_b = pl.type == PIC_B || pl.type == PIC_BREF;
+    if (h->vbv) {
+        // x264 frame->i_bframes / b_last_minigop_bframe (every picture of a mini-GOP knows how many B pictures it holds), and the header NAL units the
+        // access unit opens with (x264_ratecontrol_start's overhead)
+        if (!is_b) h->minigop_b = (int)h->bcoding.size();          // (what is left of the mini-GOP in the coding queue: its B pictures)
+        f.last_minigop_b = is_b && h->bcoding.empty();
+        h->rc.vbv_picture(&pl.e.planned, h->minigop_b, f.last_minigop_b, au_overhead_bits(h, pl));
+    }
     pic.qp = h->rc.start(pl.type, pl.e.frame, pl.e.costs, &near, &f.qpf);
+    if (h->vbv) {
+        x264_t::VbvInfo &v = h->last_vbv;
+        v.valid = true; v.fill_before = h->rc.buffer_fill; v.qp_novbv = h->rc.qp_novbv; v.qp_clipped = f.qpf; v.frame_size_planned = h->rc.frame_size_planned;
+        v.planned = pl.e.planned; v.attempts = 1; v.filler = 0; v.overhead_bits = au_overhead_bits(h, pl);
+    }
     // x264_ratecontrol_mb_qp: a macroblock's quantiser is round(rc->qpm + its AQ / macroblock-tree offset) with qpm the picture's FLOAT quantiser
     pic.qpm = near_qpm(f.qpf, pic.qp);
-    const bool is_b = pl.type == PIC_B || pl.type == PIC_BREF;
     f.direct_auto_write = false;
     if (is_b && h->direct_mode != 1) {
         // x264 slice_header_init: temporal direct prediction is considered only when the co-located picture's reference 0 is this picture's reference 0;
@@ -2027,15 +2212,18 @@ static void bmode_plan(x264_t *h, x264_t::PicPlan &f, x264gpu_encoder *gpu, long
 
 // finish, on the caller's thread: the picture becomes the one the diagnostics hooks describe, its access unit is opened in h->out (AUD, sets in front of an IDR
 // picture).  idr_pic_id is read here — when the picture is handed to the slice writer, which for a picture in flight is when it retires, not when it was planned
-static void bmode_open_au(x264_t *h, x264_t::PicPlan &f, std::vector<int> &types)
+static bool bmode_open_au(x264_t *h, x264_t::PicPlan &f, std::vector<int> &types)
 {
     const x264_t::BPlanned &pl = f.pl;
     h->last_direct_char = f.direct_char;
     h->last_scenecut = pl.e.scenecut; h->last_qp = f.pic.qp; h->last_qpm = f.pic.qpm;
     memcpy(h->last_costs, pl.e.costs, sizeof(pl.e.costs));
     h->out.clear(); h->nal_off.clear();
-    if (begin_access_unit(h, h->out, h->nal_off, types, pl.type, !h->sei_sent)) h->sei_sent = 1;
+    AuTiming tm;
+    const bool timed = au_timing(h, pl, tm);
+    const bool sets = begin_access_unit(h, h->out, h->nal_off, types, pl.type, !h->sei_sent, timed ? &tm : nullptr);          // (true: the caller marks the version SEI sent once the access unit is final)
     f.sp.idr_pic_id = h->idr_pic_id;
+    return sets;
 }
 // ... and the session's counters move past it
 static void bmode_count(x264_t *h, bool idr)
@@ -2049,19 +2237,23 @@ static void bmode_count(x264_t *h, bool idr)
 // finish: the picture's NAL units from its downloaded records, pic_out, what the rate control learns from its size (x264_ratecontrol_end: 2-pass and ABR sessions,
 // which always run serially), the counters; returns the bytes of the NAL units
 static int quality_type(int pic_type) { return pic_type == PIC_IDR || pic_type == PIC_I ? 0 : pic_type == PIC_P ? 1 : 2; }
-static int bmode_finish(x264_t *h, x264_t::PicPlan &f, const x264gpu_mb *mbs, const int16_t *levels, x264_nal_t **pp_nal, int *pi_nal, x264_picture_t *pic_out)
+// finish, first half: the access unit in h->out — what opens it, then the picture's slices from its downloaded records.  May run again for the same picture (a VBV
+// session codes a picture again when it does not fit): nothing of the session moves here.  true: the parameter sets were written
+static bool bmode_write_au(x264_t *h, x264_t::PicPlan &f, std::vector<int> &types, const x264gpu_mb *mbs, const int16_t *levels)
+{
+    types.clear();
+    const bool sets = bmode_open_au(h, f, types);
+    h->last_stats.skip = 0;
+    write_slices(h->out, h->nal_off, types, f.sp, h->slices, mbs, levels, h->param.b_annexb != 0, f.pl.type == PIC_IDR, &h->last_stats, h->cavlc_threads);
+    return sets;
+}
+// ... second half: the written access unit is the picture's
+static int bmode_finish_written(x264_t *h, x264_t::PicPlan &f, std::vector<int> &types, bool sets, const x264gpu_mb *mbs, x264_nal_t **pp_nal, int *pi_nal, x264_picture_t *pic_out)
 {
     const x264_param_t &p = h->param;
     const x264_t::BPlanned &pl = f.pl;
     const bool idr = pl.type == PIC_IDR;
-    std::vector<int> types;
-    bmode_open_au(h, f, types);
-    h->last_stats.skip = 0;
-    write_slices(h->out, h->nal_off, types, f.sp, h->slices, mbs, levels, p.b_annexb != 0, idr, &h->last_stats, h->cavlc_threads);
-    publish_nals(h, pp_nal, pi_nal, types);
-    for (size_t i = 0; i < h->nals.size(); i++) if (types[i] == 1 || types[i] == 5) h->nals[i].i_ref_idc = f.nal_ref_idc;
-    fill_pic_out(pic_out, x264_type_of(pl.type), idr, pl.e.pts, coded_dts(h, h->coded_count), &pl.e.img);
-    if (h->ql.flags) h->ql.frame_end(p, h->hq[0], quality_type(pl.type), mean_mb_qp(mbs, (size_t)h->nmb), f.pic.poc, h->out.size());          // (h->hq[0]: downloaded with the records)
+    if (sets) h->sei_sent = 1;
     // x264_ratecontrol_end; a session that writes statistics or follows a plan is told what the picture's macroblocks were
     RateControl::PicStats ps;
     if (h->rc.pass1 || h->rc.pass2) {
@@ -2071,9 +2263,21 @@ static int bmode_finish(x264_t *h, x264_t::PicPlan &f, const x264gpu_mb *mbs, co
         }
         ps.aq_mean = mean_mb_qp(mbs, (size_t)h->nmb); ps.mv_bits = h->last_stats.mv_bits; ps.tex_bits = h->last_stats.tex_bits; ps.direct = h->last_direct_char;
     }
-    h->rc.end(h->out.size(), pl.type, pl.e.frame, f.qpf, &ps);
+    const int filler = h->rc.end(h->out.size(), pl.type, pl.e.frame, f.qpf, &ps);
+    if (filler > 0) { h->nal_off.push_back(h->out.size()); types.push_back(12); write_filler(h->out, filler - h->rc.filler_overhead(), p.b_annexb != 0); }          // --nal-hrd cbr: what the buffer cannot hold
+    if (h->vbv) { h->last_vbv.fill_after = h->rc.buffer_fill_final; h->last_vbv.filler = filler; h->last_vbv.qp_final = f.qpf; h->hrd_pics_since_bp = idr ? 1 : h->hrd_pics_since_bp + 1; }
+    publish_nals(h, pp_nal, pi_nal, types);
+    for (size_t i = 0; i < h->nals.size(); i++) if (types[i] == 1 || types[i] == 5) h->nals[i].i_ref_idc = f.nal_ref_idc;
+    fill_pic_out(pic_out, x264_type_of(pl.type), idr, pl.e.pts, coded_dts(h, h->coded_count), &pl.e.img);
+    if (h->ql.flags) h->ql.frame_end(p, h->hq[0], quality_type(pl.type), mean_mb_qp(mbs, (size_t)h->nmb), f.pic.poc, h->out.size());          // (h->hq[0]: downloaded with the records)
     bmode_count(h, idr);
     return (int)h->out.size();
+}
+static int bmode_finish(x264_t *h, x264_t::PicPlan &f, const x264gpu_mb *mbs, const int16_t *levels, x264_nal_t **pp_nal, int *pi_nal, x264_picture_t *pic_out)
+{
+    std::vector<int> types;
+    const bool sets = bmode_write_au(h, f, types, mbs, levels);
+    return bmode_finish_written(h, f, types, sets, mbs, pp_nal, pi_nal, pic_out);
 }
 
 // hands out a picture a helper thread finished (batch sessions with overlap): waits for the thread, publishes its NAL units; 0 when the slot is empty
@@ -2109,7 +2313,7 @@ static int bmode_defer(x264_t *h, x264_t::PicPlan &f, int bbuf, x264_nal_t **pp_
     const x264_t::BPlanned &pl = f.pl;
     const bool idr = pl.type == PIC_IDR;
     std::vector<int> types;
-    bmode_open_au(h, f, types);
+    if (bmode_open_au(h, f, types)) h->sei_sent = 1;
     x264_t::Deferred &d = h->defer[h->defer_cur];
     if (d.th.joinable()) d.th.join();          // (handed out two calls ago: long finished)
     d.out = h->out; d.off = h->nal_off; d.types = types; d.err.clear(); d.nal_ref_idc = f.nal_ref_idc; d.stats = SliceStats{ 0 };
@@ -2162,6 +2366,7 @@ static int encode_bmode(x264_t *h, x264_nal_t **pp_nal, int *pi_nal, x264_pictur
     if (!decided) return flushing ? publish_deferred(h, h->defer[h->defer_cur ^ 1].valid ? h->defer[h->defer_cur ^ 1] : h->defer[h->defer_cur], pp_nal, pi_nal, pic_out) : 0;
     x264_t::PicPlan f;
     bmode_plan(h, f, h->gpu, h->coded_count, true);
+    std::vector<int> vbv_types; bool vbv_sets = false, vbv_written = false;          // VBV: the access unit is written (and the picture coded again) before it is finished
     // launch: the group's round (its results downloaded here unless a helper thread does it: deferred), or this session's encoder and two downloads on the default stream
     const uint8_t *d_src = h->q_raw[(size_t)f.pl.e.slot];
     int bbuf = 0;
@@ -2175,13 +2380,33 @@ static int encode_bmode(x264_t *h, x264_nal_t **pp_nal, int *pi_nal, x264_pictur
             return -1;
         }
     } else
-    if (x264gpu_encode_pictures(h->gpu, d_src, &f.pic, h->d_mb, h->d_lv, nullptr) != X264GPU_OK || (h->ql.flags && h->ql.queue(h->gpu, h->d_q, nullptr) != X264GPU_OK) ||
-        (getenv("X264GPU_HOST_TIMING") && (x264gpu_stream_sync(nullptr), BPHASE(1), false)) || (h->ql.flags && x264gpu_memcpy_d2h(&h->hq[0], h->d_q, sizeof(h->hq[0]), nullptr) != X264GPU_OK) ||
-        x264gpu_memcpy_d2h(h->h_mb.data(), h->d_mb, h->h_mb.size() * sizeof(x264gpu_mb), nullptr) != X264GPU_OK ||
-        x264gpu_memcpy_d2h(h->h_lv.data(), h->d_lv, h->h_lv.size() * sizeof(int16_t), nullptr) != X264GPU_OK) {
-        xlog(&p, X264_LOG_ERROR, "x264_encoder_encode: GPU hot path failed: %s\n", x264gpu_last_error());
-        h->failed = true;
-        return -1;
+    for (;;) {
+        if (x264gpu_encode_pictures(h->gpu, d_src, &f.pic, h->d_mb, h->d_lv, nullptr) != X264GPU_OK || (h->ql.flags && h->ql.queue(h->gpu, h->d_q, nullptr) != X264GPU_OK) ||
+            (getenv("X264GPU_HOST_TIMING") && (x264gpu_stream_sync(nullptr), BPHASE(1), false)) || (h->ql.flags && x264gpu_memcpy_d2h(&h->hq[0], h->d_q, sizeof(h->hq[0]), nullptr) != X264GPU_OK) ||
+            x264gpu_memcpy_d2h(h->h_mb.data(), h->d_mb, h->h_mb.size() * sizeof(x264gpu_mb), nullptr) != X264GPU_OK ||
+            x264gpu_memcpy_d2h(h->h_lv.data(), h->d_lv, h->h_lv.size() * sizeof(int16_t), nullptr) != X264GPU_OK) {
+            xlog(&p, X264_LOG_ERROR, "x264_encoder_encode: GPU hot path failed: %s\n", x264gpu_last_error());
+            h->failed = true;
+            return -1;
+        }
+        if (!h->vbv) break;
+        // the VBV's re-encode guard: the picture's exact size is known once its slices are written; one that would under-run the buffer (x264_ratecontrol_end's
+        // "VBV underflow") is issued again — same x264gpu_pic, destination slot and source, which the device contract allows before any later picture — at a
+        // quantiser raised by what its size asks for: bits fall roughly as 1 / qscale, and qscale doubles every 6.  The rate control's running state stays as
+        // start() left it; everything that describes the picture afterwards describes the attempt that is emitted
+        BPHASE(2);
+        vbv_sets = bmode_write_au(h, f, vbv_types, h->h_mb.data(), h->h_lv.data());
+        vbv_written = true;
+        BPHASE(3);
+        const double slice_bits = (double)h->out.size() * 8 - (double)h->last_vbv.overhead_bits, room = h->rc.buffer_fill;
+        const int qp_max = h->rc.qp_ceiling();
+        if (slice_bits <= room || f.pic.qp >= qp_max) break;
+        const int step = room > 0 ? (int)ceil(6.0 * log2(slice_bits / (0.9 * room))) : qp_max;
+        const int qp_new = clampi(f.pic.qp + (step > 1 ? step : 1), 1, qp_max);
+        xlog(&p, X264_LOG_DEBUG, "VBV: frame %d took %.0f bits at qp %d with %.0f bits in the buffer: coded again at qp %d\n", f.pl.e.frame, slice_bits, f.pic.qp, room, qp_new);
+        f.pic.qp = qp_new; f.pic.qpm = (float)qp_new; f.qpf = qp_new; f.sp.qp = qp_new;
+        if (f.nal_ref_idc) h->rc.kept(f.pic.dst, f.qpf, f.pl.type);
+        h->last_vbv.attempts++;
     }
     BPHASE(2);
     if (const char *dd = getenv("X264GPU_DUMP_RECORDS")) {          // debugging aid: the records and levels of every coded picture, and what was asked of the device
@@ -2207,7 +2432,7 @@ static int encode_bmode(x264_t *h, x264_nal_t **pp_nal, int *pi_nal, x264_pictur
     int size;
     if (deferred) size = bmode_defer(h, f, bbuf, pp_nal, pi_nal, pic_out);
     else {
-        size = bmode_finish(h, f, h->h_mb.data(), h->h_lv.data(), pp_nal, pi_nal, pic_out);
+        size = vbv_written ? bmode_finish_written(h, f, vbv_types, vbv_sets, h->h_mb.data(), pp_nal, pi_nal, pic_out) : bmode_finish(h, f, h->h_mb.data(), h->h_lv.data(), pp_nal, pi_nal, pic_out);
         h->dpb.commit();
     }
     BPHASE(3);
@@ -2631,6 +2856,23 @@ int x264host_last_decision(x264_t *h, int *qp, int *scenecut, int32_t costs[4])
 
 /* tests: the second pass' plan — the quantiser scale init_pass2 gave every picture of the statistics file (display order), and what should have been spent before each;
  * returns the number of pictures planned (0: not a second pass) */
+int x264host_last_vbv(x264_t *h, double out[12], int *planned_type, int *planned_satd, int cap)
+{
+    if (!h || !h->vbv || !h->last_vbv.valid) return -1;
+    const x264_t::VbvInfo &v = h->last_vbv;
+    if (out) {
+        const double o[12] = { v.fill_before, v.fill_after, v.qp_novbv, v.qp_clipped, v.frame_size_planned, (double)v.attempts, (double)v.filler, v.qp_final,
+                               (double)v.overhead_bits, h->rc.buffer_size, h->rc.vbv_max_rate, h->rc.frame_size_maximum };
+        memcpy(out, o, sizeof(o));
+    }
+    int n = 0;
+    while (n < RateControl::PLAN_MAX && v.planned.type[n] != RateControl::PLAN_END) n++;
+    for (int i = 0; i <= n && i < cap; i++) {
+        if (planned_type) planned_type[i] = i < n ? v.planned.type[i] : -1;
+        if (planned_satd) planned_satd[i] = i < n ? v.planned.satd[i] : 0;
+    }
+    return n;
+}
 int x264host_pass2_plan(x264_t *h, double *new_qscale, double *expected_bits, int n)
 {
     if (!h || !h->rc.pass2) return 0;

@@ -49,6 +49,10 @@ struct SliceParams {
 // differences: i_mv_bits) and what follows them (coded block pattern, quantiser delta, residual: i_tex_bits); everything else is 'misc'
 struct SliceStats { int skip; long mv_bits = 0, tex_bits = 0; };
 
+// --nal-hrd: hrd_parameters() of the VUI (E.1.2, one CPB) as x264 derives it from --vbv-maxrate / --vbv-bufsize: rate and size in value / scale form (the unscaled
+// values are what the rate control then runs on), the lengths of the delay fields of the buffering-period and picture-timing SEI messages
+struct HrdParams { int present = 0, cbr = 0, bit_rate_scale = 0, cpb_size_scale = 0, bit_rate_value = 0, cpb_size_value = 0, bit_rate_unscaled = 0, cpb_size_unscaled = 0,
+                   initial_cpb_removal_delay_length = 0, cpb_removal_delay_length = 0, dpb_output_delay_length = 0; };
 struct SpsParams {
     int profile_idc, level_idc, sps_id;
     int mbw, mbh, crop_right, crop_bottom;       // crop in luma samples
@@ -59,12 +63,18 @@ struct SpsParams {
     int mv_range;            // --mvrange (luma samples): log2_max_mv_length_* = floor(log2(4 * mv_range - 1)) + 1, as x264's sps init
     int log2_max_poc_lsb = 0;    // > 0: pic_order_cnt_type 0 (sessions with B pictures), else type 2
     int num_reorder_frames = 0;  // x264: 2 with --b-pyramid, 1 with B pictures, else 0
+    HrdParams hrd;               // nal_hrd_parameters_present_flag and what follows it
 };
 struct PpsParams { int pps_id, sps_id, cabac, num_ref, pic_init_qp, chroma_qp_offset, transform8x8_mode; int weighted_bipred_idc = 0; int weighted_pred = 0; };
 
 void write_sps(std::vector<uint8_t> &out, const SpsParams &s, bool annexb);
 void write_pps(std::vector<uint8_t> &out, const PpsParams &p, bool annexb);
 void write_sei_version(std::vector<uint8_t> &out, const char *text, bool annexb);
+// buffering period (D.1.2: in front of every keyframe) and picture timing (D.1.3: every picture; no pic_struct) under --nal-hrd; a filler NAL unit (7.3.2.7) of
+// `payload` 0xFF bytes (--nal-hrd cbr)
+void write_sei_buffering_period(std::vector<uint8_t> &out, const HrdParams &hrd, int sps_id, uint32_t initial_cpb_removal_delay, uint32_t initial_cpb_removal_delay_offset, bool annexb, bool long_startcode);
+void write_sei_pic_timing(std::vector<uint8_t> &out, const HrdParams &hrd, uint32_t cpb_removal_delay, uint32_t dpb_output_delay, bool annexb, bool long_startcode);
+void write_filler(std::vector<uint8_t> &out, int payload, bool annexb);
 void write_slice_header(BitWriter &bw, const SliceParams &p);
 // the levels of macroblock i: levels + i * X264GPU_MB_LEVELS, or — index != nullptr: the device packed them (x264gpu_pack_levels) — its kept groups of 16 spread out
 // into `scratch` (X264GPU_MB_LEVELS zeros first)

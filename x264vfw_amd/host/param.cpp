@@ -18,17 +18,17 @@
 extern "C" {
 
 const x264_level_t x264_levels[] = {
-    { 10, 1485, 99, 396, 64, 175, 64 },       { 9, 1485, 99, 396, 128, 350, 64 },        /* "1b" */
-    { 11, 3000, 396, 900, 192, 500, 128 },    { 12, 6000, 396, 2376, 384, 1000, 128 },
-    { 13, 11880, 396, 2376, 768, 2000, 128 }, { 20, 11880, 396, 2376, 2000, 2000, 128 },
-    { 21, 19800, 792, 4752, 4000, 4000, 256 }, { 22, 20250, 1620, 8100, 4000, 4000, 256 },
-    { 30, 40500, 1620, 8100, 10000, 10000, 256 }, { 31, 108000, 3600, 18000, 14000, 14000, 512 },
-    { 32, 216000, 5120, 20480, 20000, 20000, 512 }, { 40, 245760, 8192, 32768, 20000, 25000, 512 },
-    { 41, 245760, 8192, 32768, 50000, 62500, 512 }, { 42, 522240, 8704, 34816, 50000, 62500, 512 },
-    { 50, 589824, 22080, 110400, 135000, 135000, 512 }, { 51, 983040, 36864, 184320, 240000, 240000, 512 },
-    { 52, 2073600, 36864, 184320, 240000, 240000, 512 }, { 60, 4177920, 139264, 696320, 240000, 240000, 8192 },
-    { 61, 8355840, 139264, 696320, 480000, 480000, 8192 }, { 62, 16711680, 139264, 696320, 800000, 800000, 8192 },
-    { 0, 0, 0, 0, 0, 0, 0 } };
+    { 10, 1485, 99, 396, 64, 175, 64, 2 },       { 9, 1485, 99, 396, 128, 350, 64, 2 },        /* "1b" */
+    { 11, 3000, 396, 900, 192, 500, 128, 2 },    { 12, 6000, 396, 2376, 384, 1000, 128, 2 },
+    { 13, 11880, 396, 2376, 768, 2000, 128, 2 }, { 20, 11880, 396, 2376, 2000, 2000, 128, 2 },
+    { 21, 19800, 792, 4752, 4000, 4000, 256, 2 }, { 22, 20250, 1620, 8100, 4000, 4000, 256, 2 },
+    { 30, 40500, 1620, 8100, 10000, 10000, 256, 2 }, { 31, 108000, 3600, 18000, 14000, 14000, 512, 4 },
+    { 32, 216000, 5120, 20480, 20000, 20000, 512, 4 }, { 40, 245760, 8192, 32768, 20000, 25000, 512, 4 },
+    { 41, 245760, 8192, 32768, 50000, 62500, 512, 2 }, { 42, 522240, 8704, 34816, 50000, 62500, 512, 2 },
+    { 50, 589824, 22080, 110400, 135000, 135000, 512, 2 }, { 51, 983040, 36864, 184320, 240000, 240000, 512, 2 },
+    { 52, 2073600, 36864, 184320, 240000, 240000, 512, 2 }, { 60, 4177920, 139264, 696320, 240000, 240000, 8192, 2 },
+    { 61, 8355840, 139264, 696320, 480000, 480000, 8192, 2 }, { 62, 16711680, 139264, 696320, 800000, 800000, 8192, 2 },
+    { 0, 0, 0, 0, 0, 0, 0, 0 } };
 
 void x264_param_default(x264_param_t *p)
 {

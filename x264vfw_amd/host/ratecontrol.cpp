@@ -78,6 +78,22 @@ bool RateControl::open(const x264_param_t &param, int mbw_, int mbh_, int bframe
         abr_buffer = 2.0 * (p->rc.f_rate_tolerance > 0.01f ? p->rc.f_rate_tolerance : 0.01f) * bitrate;
         lstep = pow(2.0, (p->rc.i_qp_step > 0 ? p->rc.i_qp_step : 4) / 6.0);
     }
+    if (vbv) {
+        // x264_ratecontrol_init_reconfigurable with the parameters x264_encoder_open validated (kbit -> bit; the HRD, when signalled, carries these unscaled values)
+        vbv_max_rate = hrd_rate ? hrd_rate : p->rc.i_vbv_max_bitrate * 1000.0; buffer_size = hrd_size ? hrd_size : p->rc.i_vbv_buffer_size * 1000.0;
+        buffer_rate = vbv_max_rate / fps;
+        single_frame_vbv = buffer_rate * 1.1 > buffer_size;
+        vbv_min_rate = abr && p->rc.i_vbv_max_bitrate <= p->rc.i_bitrate;
+        cbr_decay = 1.0;
+        if (abr) { const double t = 1.5 - buffer_rate * fps / bitrate; cbr_decay = 1.0 - buffer_rate / buffer_size * 0.5 * (t > 0 ? t : 0); }
+        buffer_fill_final = buffer_size * p->rc.f_vbv_buffer_init;
+        // x264_ratecontrol_new: the size predictors by slice type (coefficients 1.0 / 1.0 / 1.5 for P / B / I), and a B picture's size from the P picture behind it
+        const float coeff[3] = { 1.5f, 1.0f, 1.0f };
+        for (int i = 0; i < 3; i++) pred[i] = { coeff[i] / 2, coeff[i], 1.0f, 0.5f, 0.0f };
+        pred_b_from_p = { 0.5f / 2, 0.5f, 1.0f, 0.5f, 0.0f };
+        level_mbps = 0; level_mincr = 2;
+        for (int i = 0; x264_levels[i].level_idc; i++) if (x264_levels[i].level_idc == p->i_level_idc) { level_mbps = x264_levels[i].mbps; level_mincr = x264_levels[i].mincr; }
+    }
     if (pass2) {
         if (!p2_load(p->rc.psz_stat_in) || !p2_init()) return false;
         xlog(p, X264_LOG_INFO, "2-pass: %d pictures planned from the first pass' statistics, %.1f kbit expected before the last one\n", (int)p2.size(), p2_final_bits / 1000.0);
@@ -111,7 +127,8 @@ double RateControl::pick_qp(bool is_i, const int32_t costs[4], int frame)
     } else q = FL(last_qscale_for[is_i ? 0 : 1]);
     // get_qscale: a zone forces its quantiser or scales the picture's bits (an I picture after P pictures still takes the running P quantiser below, as in x264)
     if (const Zone *z = get_zone(frame)) q = FL(z->force_qp ? qp2qscale(z->qp) : q / z->bitrate_factor);
-    if (abr && satd > 0) {
+    last_satd = satd;
+    if (abr && satd > 0 && !vbv_min_rate) {
         // pull towards the target: bits so far against time so far, within an abr_buffer that grows with sqrt(time)
         const double time_done = frames_done / fps, wanted_bits = time_done * bitrate;
         if (wanted_bits > 0) {
@@ -129,9 +146,18 @@ double RateControl::pick_qp(bool is_i, const int32_t costs[4], int frame)
             q = FL(clampd(q, lo, hi));
         }
     } else if (crf && qcompress != 1.0) q = FL(qp2qscale(p->rc.f_rf_constant) / ip_factor);       // very first picture: ABR_INIT_QP / ipratio
+    if (vbv) {
+        qp_novbv = qscale2qp(q);
+        q = FL(clip_qscale(is_i, q));
+    } else
     q = FL(clampd(q, lmin, lmax));
     last_qscale_for[is_i ? 0 : 1] = q;
     if (frames_done == 0) last_qscale_for[1] = q * ip_factor;
+    if (vbv) {
+        // rate_estimate_qscale: the size the picture is expected to take (a single-frame buffer is always used up), limited by MinCR
+        frame_size_planned = single_frame_vbv ? buffer_rate : predict_size(pred[is_i ? 0 : 1], q, last_satd);
+        if (frame_size_planned > frame_size_maximum) frame_size_planned = frame_size_maximum;
+    }
     const double qpf = clampd(qscale2qp(q), p->rc.i_qp_min, p->rc.i_qp_max);
     accum_p_qp = accum_p_qp * 0.95 + (is_i ? qpf + ip_offset : qpf);      // accum_p_qp_update
     accum_p_norm = accum_p_norm * 0.95 + 1.0;
@@ -154,6 +180,13 @@ double RateControl::pick_qp_b(int kind, const BRefs &b)
     else qf = (q0 * dt1 + q1 * dt0) / (dt0 + dt1);
     qf = (float)(qf + (kind == PIC_BREF ? pb_offset / 2 : pb_offset));
     const double q = clampd(qscale2qp(qp2qscale(qf)), p->rc.i_qp_min, p->rc.i_qp_max);
+    if (vbv) {
+        // B pictures are not clipped (the P pictures' quantisers control them); their cost is the list-1 reference's, their planned size the B predictor's of it
+        last_satd = slot_satd[s1];
+        qp_novbv = qf;
+        frame_size_planned = predict_size(pred[2], qp2qscale(qf), last_satd);
+        if (frame_size_planned > frame_size_maximum) frame_size_planned = frame_size_maximum;
+    }
     // x264_ratecontrol_start: accum_p_qp_update runs for every picture type — a B picture's own quantiser (no ip_offset) enters the running average an I picture
     // after P pictures takes its quantiser from
     accum_p_qp = accum_p_qp * 0.95 + q;
@@ -165,6 +198,13 @@ int RateControl::start(int kind, int frame, const int32_t costs[4], const BRefs 
 {
     const bool is_i = kind == PIC_IDR || kind == PIC_I, is_b = kind == PIC_B || kind == PIC_BREF;
     double q; int qp;
+    if (vbv) {
+        // update_vbv_plan: what the buffer holds when this picture is removed, less the header NAL units already written for it
+        buffer_fill = (buffer_fill_final < buffer_size ? buffer_fill_final : buffer_size) - (double)cur_overhead;
+        // x264_ratecontrol_start: the largest picture the level allows (Table A-1 MaxMBPS and MinCR; "the spec has a bizarre special case for the first frame")
+        if (frames_done == 0) { const double fr = 1.0 / (p->i_level_idc >= 60 ? 300 : 172); frame_size_maximum = 384 * 8 * ((double)nmb > fr * level_mbps ? (double)nmb : fr * level_mbps) / level_mincr; }
+        else frame_size_maximum = 384 * 8 * (1.0 / fps) * level_mbps / level_mincr;
+    }
     if (pass2) {          // the plan with feedback (zones are not applied to it)
         q = clampd(qscale2qp(p2_pick_qscale(frame)), p->rc.i_qp_min, p->rc.i_qp_max);
         qp = clampi((int)(q + 0.5), 1, 51);
@@ -189,7 +229,87 @@ int RateControl::start(int kind, int frame, const int32_t costs[4], const BRefs 
     return qp;
 }
 
-void RateControl::kept(int slot, double qpf, int kind) { slot_qp_rc[slot] = qp_avg_rc((float)qpf, mbw, mbh); slot_kind[slot] = kind; }
+void RateControl::kept(int slot, double qpf, int kind) { slot_qp_rc[slot] = qp_avg_rc((float)qpf, mbw, mbh); slot_kind[slot] = kind; slot_satd[slot] = last_satd; }
+
+void RateControl::vbv_picture(const Planned *planned, int bframes, bool last_minigop_b, long overhead_bits) { cur_planned = planned; cur_bframes = bframes; cur_last_b = last_minigop_b; cur_overhead = overhead_bits; }
+int RateControl::qp_ceiling() const { return p->rc.i_qp_max < 51 ? p->rc.i_qp_max : 51; }
+
+// predict_size / update_predictor: x264's, in its single floats
+double RateControl::predict_size(const Predictor &pr, double q, double var) { return (double)((pr.coeff * (float)var + pr.offset) / ((float)q * pr.count)); }
+void RateControl::update_predictor(Predictor &pr, double q_, double var_, double bits_)
+{
+    const float q = (float)q_, var = (float)var_, bits = (float)bits_, range = 1.5f;
+    if (var < 10) return;
+    const float old_coeff = pr.coeff / pr.count, old_offset = pr.offset / pr.count;
+    float new_coeff = (bits * q - old_offset) / var;
+    if (new_coeff < pr.coeff_min) new_coeff = pr.coeff_min;
+    const float new_coeff_clipped = new_coeff < old_coeff / range ? old_coeff / range : new_coeff > old_coeff * range ? old_coeff * range : new_coeff;
+    float new_offset = bits * q - new_coeff_clipped * var;
+    if (new_offset >= 0) new_coeff = new_coeff_clipped; else new_offset = 0;
+    pr.count *= pr.decay; pr.coeff *= pr.decay; pr.offset *= pr.decay;
+    pr.count++; pr.coeff += new_coeff; pr.offset += new_offset;
+}
+
+// clip_qscale for an I or P picture (q: double throughout, as in x264; the caller's float takes the result): raise the quantiser until neither this picture nor
+// the planned ones behind it under-run the buffer, lower it (only when the rate is a minimum too) while the buffer would end too full
+double RateControl::clip_qscale(bool is_i, double q)
+{
+    const double q0 = q;
+    const Predictor &pt = pred[is_i ? 0 : 1];
+    if (last_satd > 0) {
+        const double dur = 1.0 / fps;          // (constant frame rate: every cpb duration is one picture's)
+        if (vbv_lookahead) {
+            int terminate = 0;
+            for (int it = 0; it < 1000 && terminate != 3; it++) {
+                double cur_bits = predict_size(pt, q, last_satd), fill = buffer_fill - cur_bits, total_duration = 0;
+                double frame_q[3];          // as pred[]: [0] I, [1] P, [2] B
+                frame_q[1] = is_i ? q * p->rc.f_ip_factor : q; frame_q[2] = frame_q[1] * p->rc.f_pb_factor; frame_q[0] = frame_q[1] / p->rc.f_ip_factor;
+                for (int j = 0; fill >= 0 && fill <= buffer_size; j++) {
+                    total_duration += dur;
+                    fill += vbv_max_rate * dur;
+                    const int t = cur_planned && j < PLAN_MAX ? cur_planned->type[j] : (int)PLAN_END;
+                    if (t == PLAN_END) break;
+                    const int k = t == PIC_IDR || t == PIC_I ? 0 : t == PIC_P ? 1 : 2;
+                    fill -= predict_size(pred[k], frame_q[k], cur_planned->satd[j]);
+                }
+                double target = buffer_fill + total_duration * vbv_max_rate * 0.5;          // at least half full, but no impossible goal
+                if (target > buffer_size * 0.5) target = buffer_size * 0.5;
+                if (fill < target) { q *= 1.01; terminate |= 1; continue; }
+                target = clampd(buffer_fill - total_duration * vbv_max_rate * 0.5, buffer_size * 0.8, buffer_size);          // no more than 80 % full
+                if (vbv_min_rate && fill > target) { q /= 1.01; terminate |= 2; continue; }
+                break;
+            }
+        } else {
+            // the purely reactive algorithm
+            if ((!is_i || last_non_b_is_i) && buffer_fill / buffer_size < 0.5) q /= clampd(2.0 * buffer_fill / buffer_size, 0.5, 1.0);
+            // a hard threshold so that the picture fits (mostly for I pictures); small buffers may be used up entirely, a single-frame buffer must be
+            double bits = predict_size(pt, q, last_satd);
+            const double max_fill_factor = p->rc.i_vbv_buffer_size >= 5 * p->rc.i_vbv_max_bitrate / fps ? 2 : 1, min_fill_factor = single_frame_vbv ? 1 : 2;
+            if (bits > buffer_fill / max_fill_factor) { const double qf = clampd(buffer_fill / (max_fill_factor * bits), 0.2, 1.0); q /= qf; bits *= qf; }
+            if (bits < buffer_rate / min_fill_factor) { const double qf = clampd(bits * min_fill_factor / buffer_rate, 0.001, 1.0); q *= qf; }
+            if (q < q0) q = q0;
+        }
+        // a P picture: use up the bits that would overflow before the next P picture, going by what the B pictures behind it are expected to take
+        if (!is_i && !single_frame_vbv) {
+            int nb = cur_bframes;
+            const double bits = predict_size(pt, q, last_satd), bbits = predict_size(pred_b_from_p, q * p->rc.f_pb_factor, last_satd);
+            double pbbits = bits, bdur = nb * dur;
+            if (bbits * nb > bdur * vbv_max_rate) { nb = 0; bdur = 0; }
+            pbbits += nb * bbits;
+            const double space = buffer_fill + (bdur + dur) * vbv_max_rate - buffer_size;
+            if (pbbits < space) { const double a = pbbits / space, b = bits / (0.5 * buffer_size); q *= a > b ? a : b; }
+            if (q < q0 / 2) q = q0 / 2;
+        }
+        // MinCR and the buffer's fill
+        const double bits = predict_size(pt, q, last_satd);
+        double fmax = buffer_fill > 0.001 ? buffer_fill : 0.001;
+        if (fmax > frame_size_maximum) fmax = frame_size_maximum;
+        if (bits > fmax) q *= bits / fmax;
+        if (!vbv_min_rate && q < q0) q = q0;
+    }
+    if (lmin == lmax) return lmin;
+    return clampd(q, lmin, lmax);
+}
 
 static double qscale2bits(const RateControl::Pass2Entry &e, double qscale)
 {
@@ -197,9 +317,10 @@ static double qscale2bits(const RateControl::Pass2Entry &e, double qscale)
     return (e.tex + .1) * pow(e.qscale / qscale, 1.1) + e.mv * pow((e.qscale > 1 ? e.qscale : 1) / (qscale > 1 ? qscale : 1), 0.5) + e.misc;
 }
 
-void RateControl::end(size_t bytes, int kind, int frame, double qpf, const PicStats *st)
+int RateControl::end(size_t bytes, int kind, int frame, double qpf, const PicStats *st)
 {
     const long total = (long)bytes * 8;
+    int filler_bytes = 0;
     if (stat_file && st) {
         const char t = kind == PIC_IDR ? 'I' : kind == PIC_I ? 'i' : kind == PIC_P ? 'P' : kind == PIC_BREF ? 'B' : 'b';
         fprintf(stat_file, "in:%d out:%ld type:%c dur:%d cpbdur:%d q:%.2f aq:%.2f tex:%ld mv:%ld misc:%ld imb:%ld pmb:%ld smb:%ld d:%c ref:;\n", frame, coded, t, 1, 1, qpf,
@@ -215,8 +336,29 @@ void RateControl::end(size_t bytes, int kind, int frame, double qpf, const PicSt
         total_bits += (double)total;
         cplxr_sum += (double)total * qp2qscale(qp_avg_rc((float)qpf, mbw, mbh)) / (last_rceq * (is_b ? pb_factor : 1.0));          // (rc->qpa_rc: the float gathered row by row)
         wanted_bits_window += bitrate / fps;
+        if (vbv) { cplxr_sum *= cbr_decay; wanted_bits_window *= cbr_decay; }
+    }
+    if (vbv) {
+        // update_vbv: the predictor of the picture's type learns from its size, then the buffer's account
+        const bool is_b = kind == PIC_B || kind == PIC_BREF, is_i = kind == PIC_IDR || kind == PIC_I;
+        const double qs = qp2qscale(qp_avg_rc((float)qpf, mbw, mbh));
+        if (last_satd >= nmb) update_predictor(pred[is_i ? 0 : is_b ? 2 : 1], qs, last_satd, (double)total);
+        if (is_b) {          // x264_ratecontrol_end: a B picture's size from the P picture's cost, learnt from the run's mean at its last picture
+            bframe_bits += (double)total;
+            if (cur_last_b) { update_predictor(pred_b_from_p, qs, last_satd, bframe_bits / (cur_bframes > 0 ? cur_bframes : 1)); bframe_bits = 0; }
+        }
+        buffer_fill_final -= (double)total;
+        if (buffer_fill_final < 0) { xlog(p, X264_LOG_WARNING, "VBV underflow (frame %d, %.0f bits)\n", frame, buffer_fill_final); buffer_fill_final = 0; }
+        buffer_fill_final += buffer_rate;
+        if (filler && buffer_fill_final > buffer_size) {
+            // --nal-hrd cbr: what arrives beyond the buffer's size has to be sent (a filler NAL unit is never smaller than its overhead)
+            const long over = (long)ceil((buffer_fill_final - buffer_size) / 8.0);
+            filler_bytes = (int)(over > filler_overhead() ? over : filler_overhead());
+            buffer_fill_final -= 8.0 * filler_bytes;
+        } else if (buffer_fill_final > buffer_size) buffer_fill_final = buffer_size;
     }
     coded++;
+    return filler_bytes;
 }
 
 void RateControl::close()

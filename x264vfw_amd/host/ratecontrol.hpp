@@ -1,6 +1,8 @@
 // ratecontrol.hpp — the host encoder's rate control ([x264-upstream] encoder/ratecontrol.c restated; checker twin: oracle/decide.py class RateControl, init_pass2,
-// pass2_quantisers): constant quantiser with --ipratio / --pbratio and zones, single-pass CRF and ABR, both passes of a 2-pass encode.  No VBV.  One object per
-// session behind x264's three calls — open, start for every picture about to be coded, end once its size is known; plain C++ over x264_param_t and numbers.
+// pass2_quantisers; the VBV part: tests/vbv_ref.py): constant quantiser with --ipratio / --pbratio and zones, single-pass CRF and ABR, both passes of a 2-pass encode,
+// and the VBV of single-pass CRF / ABR sessions at picture level (clip_qscale, the size predictors, the buffer account; no row-level re-quantisation: the session
+// codes a picture again instead, encoder.cpp).  One object per session behind x264's three calls — open, start for every picture about to be coded, end once its
+// size is known; plain C++ over x264_param_t and numbers.
 #pragma once
 #include "host.hpp"
 #include <stdio.h>
@@ -13,7 +15,11 @@ struct RateControl {
     bool crf = false, abr = false;       // single pass: the quantisers follow the lookahead's frame costs (ABR: and the coded sizes)
     bool pass1 = false, pass2 = false;   // a statistics line per coded picture; every quantiser planned from the first pass' statistics
     bool by_cost() const { return crf || abr; }
-    bool reads_sizes() const { return abr || pass1 || pass2; }          // end() feeds start(): such a session codes one picture at a time
+    bool reads_sizes() const { return abr || pass1 || pass2 || vbv; }          // end() feeds start(): such a session codes one picture at a time
+    // VBV (session policy as well: x264_encoder_open validates --vbv-maxrate / --vbv-bufsize / --vbv-init / --nal-hrd and leaves the effective values in the parameters)
+    bool vbv = false, vbv_lookahead = false;          // vbv_lookahead: rc-lookahead > 0, every I / P picture comes with the planned types and costs of the pictures behind it
+    bool filler = false;                              // --nal-hrd cbr: what the buffer cannot hold is sent as filler (end() says how many bytes)
+    int hrd_rate = 0, hrd_size = 0;                   // --nal-hrd: the rate and size the HRD signals (value << scale: what is left of the request), which the VBV then runs on; 0: as asked
     int qp_constant[5] = { 23, 23, 23, 23, 23 };          // x264 rc->qp_constant[] by PIC_*: a constant-quantiser session's quantisers outside its zones
 
     struct Zone { int start, end; bool force_qp; int qp; float bitrate_factor; };      // x264_zone_t: pictures start..end (display order) at quantiser qp, or at bitrate_factor times their bits
@@ -28,10 +34,22 @@ struct RateControl {
     // the float one (x264 rc->qpm before the macroblock offsets)
     struct BRefs { int slot[2], dpoc[2]; };
     int start(int kind, int frame, const int32_t costs[4] = nullptr, const BRefs *b = nullptr, double *qpf = nullptr);
+    // VBV sessions, before start(): what x264 keeps on the frame — the planned types (PIC_*, PLAN_END behind the last) and costs of the pictures coded after this one
+    // (vbv_lookahead in the slice-type analysis; nullptr: none), the B pictures of the mini-GOP it closes (or belongs to), whether it is the last B picture of its
+    // mini-GOP, and the bits of the header NAL units already in its access unit
+    enum { PLAN_MAX = 64, PLAN_END = -1 };
+    struct Planned { int type[PLAN_MAX + 1] = { PLAN_END }; int satd[PLAN_MAX + 1] = { 0 }; };
+    void vbv_picture(const Planned *planned, int bframes, bool last_minigop_b, long overhead_bits);
+    // ... and what start() made of them: the buffer fill it saw, the quantiser before clip_qscale (x264 rc->qp_novbv), the planned size and the size limit
+    double buffer_fill = 0, qp_novbv = 0, frame_size_planned = 0, frame_size_maximum = 0;
+    double buffer_size = 0, vbv_max_rate = 0, buffer_rate = 0, buffer_fill_final = 0;          // bits, bits / s, bits a picture; the fill behind the last coded picture
+    int qp_ceiling() const;          // the highest quantiser a picture may be coded again with (qpmax)
     void kept(int slot, double qpf, int kind);          // a picture kept as a reference went into DPB slot `slot` (x264 fdec->f_qp_avg_rc, i_type)
     // x264_ratecontrol_end: ABR's feedback, the second pass' account, the statistics line (st: needed for that line only)
     struct PicStats { long imb = 0, pmb = 0, smb = 0, mv_bits = 0, tex_bits = 0; double aq_mean = 0; char direct = '-'; };      // intra / inter / skipped macroblocks, header / residual bits, mean quantiser
-    void end(size_t bytes, int kind, int frame, double qpf, const PicStats *st = nullptr);
+    // -> the size of the filler NAL unit the access unit is to be padded with (--nal-hrd cbr under VBV; filler_overhead() of it is not payload), else 0
+    int end(size_t bytes, int kind, int frame, double qpf, const PicStats *st = nullptr);
+    int filler_overhead() const { return p->b_annexb ? 5 : 6; }          // start code (or length), NAL header, trailing bits
     void close();          // x264_ratecontrol_delete: the statistics file takes its name (a second pass that stopped short keeps the statistics it read)
 
     // the second pass' plan by display index (nullptr behind its end)
@@ -53,6 +71,16 @@ private:
     int last_non_b_is_i = 1;
     double bitrate = 0, cplxr_sum = 0, wanted_bits_window = 0, abr_buffer = 0, total_bits = 0, last_rceq = 1, lstep = 1.3195;      // single-pass ABR
     double slot_qp_rc[8] = { 0 }; int slot_kind[8] = { 0 };          // kept(): by DPB slot
+    // VBV (x264's predictor_t: single floats)
+    struct Predictor { float coeff_min, coeff, count, decay, offset; };
+    Predictor pred[3] = {}, pred_b_from_p = {};          // [0] I, [1] P, [2] B
+    bool vbv_min_rate = false, single_frame_vbv = false;
+    double cbr_decay = 1.0, last_satd = 0, bframe_bits = 0, slot_satd[8] = { 0 };
+    const Planned *cur_planned = nullptr; int cur_bframes = 0; bool cur_last_b = false; long cur_overhead = 0;
+    int level_mbps = 0, level_mincr = 2;
+    static double predict_size(const Predictor &p, double q, double var);
+    static void update_predictor(Predictor &p, double q, double var, double bits);
+    double clip_qscale(bool is_i, double q);
     // 2-pass: the statistics file being written (a line per coded picture); the plan init_pass2 made from the one read, followed with feedback
     FILE *stat_file = nullptr;
     std::vector<Pass2Entry> p2;          // by display index ("in:")

@@ -62,7 +62,16 @@ void write_sps(std::vector<uint8_t> &out, const SpsParams &s, bool annexb)
         bool timing = s.num_units_in_tick > 0 && s.time_scale > 0;
         bw.put1(timing);
         if (timing) { bw.put(s.num_units_in_tick, 32); bw.put(s.time_scale, 32); bw.put1(1); }   // fixed_frame_rate_flag
-        bw.put1(0); bw.put1(0);                 // nal_hrd, vcl_hrd
+        bw.put1(s.hrd.present);                 // nal_hrd_parameters_present_flag
+        if (s.hrd.present) {                    // hrd_parameters() (E.1.2)
+            bw.ue(0);                           // cpb_cnt_minus1
+            bw.put((uint32_t)s.hrd.bit_rate_scale, 4); bw.put((uint32_t)s.hrd.cpb_size_scale, 4);
+            bw.ue((uint32_t)s.hrd.bit_rate_value - 1); bw.ue((uint32_t)s.hrd.cpb_size_value - 1); bw.put1(s.hrd.cbr);
+            bw.put((uint32_t)s.hrd.initial_cpb_removal_delay_length - 1, 5); bw.put((uint32_t)s.hrd.cpb_removal_delay_length - 1, 5);
+            bw.put((uint32_t)s.hrd.dpb_output_delay_length - 1, 5); bw.put(0, 5);      // time_offset_length
+        }
+        bw.put1(0);                             // vcl_hrd_parameters_present_flag
+        if (s.hrd.present) bw.put1(0);          // low_delay_hrd_flag
         bw.put1(0);                             // pic_struct_present_flag
         bw.put1(1);                             // bitstream_restriction_flag
         bw.put1(1);                             // motion_vectors_over_pic_boundaries_flag
@@ -118,6 +127,41 @@ void write_sei_version(std::vector<uint8_t> &out, const char *text, bool annexb)
     bw.put(0, 8);
     bw.trailing();
     append_nal(out, 0, 6, bw.bytes(), annexb, true);
+}
+
+// one SEI message in a NAL unit of its own: payloadType, payloadSize, the payload (byte-aligned by sei_payload's bit_equal_to_one + zeros), rbsp_trailing_bits
+static void append_sei(std::vector<uint8_t> &out, int type, BitWriter &payload, bool annexb, bool long_startcode)
+{
+    if (payload.bits() & 7) { payload.put1(1); payload.align_zero(); }
+    BitWriter bw;
+    bw.put((uint32_t)type, 8);
+    size_t l = payload.bytes().size();
+    while (l >= 255) { bw.put(255, 8); l -= 255; }
+    bw.put((uint32_t)l, 8);
+    bw.append(payload);
+    bw.trailing();
+    append_nal(out, 0, 6, bw.bytes(), annexb, long_startcode);
+}
+void write_sei_buffering_period(std::vector<uint8_t> &out, const HrdParams &hrd, int sps_id, uint32_t initial_cpb_removal_delay, uint32_t initial_cpb_removal_delay_offset, bool annexb, bool long_startcode)
+{
+    BitWriter pl;
+    pl.ue((uint32_t)sps_id);
+    pl.put(initial_cpb_removal_delay, hrd.initial_cpb_removal_delay_length);
+    pl.put(initial_cpb_removal_delay_offset, hrd.initial_cpb_removal_delay_length);
+    append_sei(out, 0, pl, annexb, long_startcode);
+}
+void write_sei_pic_timing(std::vector<uint8_t> &out, const HrdParams &hrd, uint32_t cpb_removal_delay, uint32_t dpb_output_delay, bool annexb, bool long_startcode)
+{
+    BitWriter pl;
+    pl.put(cpb_removal_delay, hrd.cpb_removal_delay_length);
+    pl.put(dpb_output_delay, hrd.dpb_output_delay_length);
+    append_sei(out, 1, pl, annexb, long_startcode);
+}
+void write_filler(std::vector<uint8_t> &out, int payload, bool annexb)
+{
+    std::vector<uint8_t> rbsp((size_t)(payload > 0 ? payload : 0), 0xff);
+    rbsp.push_back(0x80);                       // rbsp_trailing_bits
+    append_nal(out, 0, 12, rbsp, annexb, false);
 }
 
 }  // namespace x264host

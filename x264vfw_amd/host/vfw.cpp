@@ -327,6 +327,11 @@ LRESULT compress_begin(CODEC *codec, BITMAPINFO *in, BITMAPINFO *out)
                 goto fail;
             }
             param.b_annexb = annexb; param.b_repeat_headers = annexb;       /* containers: length-prefixed NALs, headers once (codec.c:1121-1143) */
+            {   /* mp4 carries no filler: a CBR HRD becomes a VBR one (codec.c:1126-1129) */
+                const char *dot = strrchr(out_file.c_str(), '.');
+                const std::string ext = strcasecmp(muxer.c_str(), "auto") ? muxer : std::string(dot ? dot + 1 : "");
+                if (!strcasecmp(ext.c_str(), "mp4") && param.i_nal_hrd == X264_NAL_HRD_CBR) { vlog(codec, X264_LOG_WARNING, "cbr nal-hrd is not compatible with mp4\n"); param.i_nal_hrd = X264_NAL_HRD_VBR; }
+            }
         }
     }
     codec->h = x264_encoder_open(&param);

@@ -67,7 +67,7 @@ class Nal(C.Structure):
 
 
 class Level(C.Structure):
-    _fields_ = [(n, _i) for n in ("level_idc", "mbps", "frame_size", "dpb", "bitrate", "cpb", "mv_range")]
+    _fields_ = [(n, _i) for n in ("level_idc", "mbps", "frame_size", "dpb", "bitrate", "cpb", "mv_range", "mincr")]
 
 
 def _sig(name, res, args):
@@ -113,6 +113,21 @@ _sig("x264host_last_decision", _i, [C.c_void_p, C.POINTER(_i), C.POINTER(_i), C.
 _sig("x264host_last_qpm", C.c_float, [C.c_void_p])
 _sig("x264host_pictures_in_flight", C.c_int, [C.c_void_p])
 _sig("x264host_pass2_plan", _i, [C.c_void_p, C.c_void_p, C.c_void_p, _i])
+_sig("x264host_last_vbv", _i, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(_i), C.POINTER(_i), _i])
+VBV_FIELDS = ("fill_before", "fill_after", "qp_novbv", "qp_clipped", "frame_size_planned", "attempts", "filler", "qp_final", "overhead_bits", "buffer_size", "max_rate",
+              "frame_size_maximum")
+
+
+def last_vbv(h, cap=80):
+    """x264host_last_vbv as a dict (None: no VBV, or no picture yet): the twelve figures by name, 'planned' = [(type, satd), ...], 'planned_end' = the type behind the list"""
+    out, pt, ps = (C.c_double * 12)(), (_i * cap)(), (_i * cap)()
+    n = H.x264host_last_vbv(h, out, pt, ps, cap)
+    if n < 0:
+        return None
+    d = dict(zip(VBV_FIELDS, out))
+    d["planned"] = [(pt[i], ps[i]) for i in range(min(n, cap))]
+    d["planned_end"] = pt[n] if n < cap else None          # the terminator behind the list (-1: x264's X264_TYPE_AUTO)
+    return d
 _sig("x264host_last_quality", _i, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint64)])
 _sig("x264host_quality_summary", _i, [C.c_void_p, C.c_char_p, _i])
 _sig("x264host_psnr", C.c_double, [C.c_double, C.c_double])
