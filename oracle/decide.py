@@ -1,6 +1,6 @@
 """oracle/decide.py — CHECKER twin of the lookahead's decisions and the single-pass rate control (test infrastructure: only tests/ import it).
 
-The product decides picture types in host/encoder.cpp and quantisers in host/ratecontrol.cpp on the device's frame costs.  This file restates the same parts of libx264
+The product decides picture types in host/slicetype.cpp and quantisers in host/ratecontrol.cpp on the device's frame costs.  This file restates the same parts of libx264
 a second time, independently of that code, in plain Python over the CPU checker's frame costs (oracle/slicetype.c through
 tests/oracle_lib.OracleSlicetype), so that a session's decisions can be compared with something other than themselves:
 

@@ -396,7 +396,7 @@ const int32_t *x264o_slicetype_propagate_cost(x264o_slicetype *st, int slot) { r
  * half-resolution picture from a reference under an explicit luma weight: per 8x8 block min(mbcmp(weighted reference block, source block),
  * intra cost), every block of the picture, + the bits the weights cost in the slice header.  The reference is motion-compensated by the
  * lookahead's vectors of (list 0, dist) when that search has run (weight_cost_init_luma), else taken in place.  The analysis itself — guessing
- * scale and offset from the statistics, the candidates around the guess, the 0.2 % gain threshold — is the caller's (host/encoder.cpp). */
+ * scale and offset from the statistics, the candidates around the guess, the 0.2 % gain threshold — is the caller's (host/slicetype.cpp). */
 void x264o_slicetype_pixel_stats(x264o_slicetype *st, int slot, const uint8_t *i420, uint64_t out[2])
 {
     (void)slot;

@@ -1,6 +1,6 @@
 """x264's macroblock_tree ([x264-upstream] encoder/slicetype.c) as a walk over a slicetype object (oracle_lib.OracleSlicetype or
 gpu_enc.GpuSlicetype: cost / clear_propagate / propagate / finish): frames[0] = the last non-B picture, frames[1..num_frames] the
-queued ones with their decided types ('I', 'P', 'B').  The product's host code (host/encoder.cpp st_macroblock_tree) is the same walk."""
+queued ones with their decided types ('I', 'P', 'B').  The product's host code (host/slicetype.cpp Window::macroblock_tree) is the same walk."""
 
 
 def macroblock_tree(st, slots, types, num_frames, b_intra, pyramid, strength):

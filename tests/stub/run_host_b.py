@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """A session with B pictures through x264_encoder_encode() of the STUB-backed host library: prints one JSON line with the picture types, pts / dts of
-the pictures as they leave, and writes the stream to the given file.  Usage: run_host_b.py OUT W H FRAMES SEED key=value ..."""
+the pictures as they leave, and writes the stream to the given file.  Usage: run_host_b.py OUT W H FRAMES SEED key=value ...
+force=<display index>:<I|K> (may be repeated) hands that picture in with pic_in->i_type = X264_TYPE_I / X264_TYPE_KEYFRAME."""
 import ctypes as C
 import json
 import os
@@ -35,9 +36,13 @@ def make_frames(w, h, n, seed, scene_len=0, static=0, fade=0):
 def main():
     out_path = sys.argv[1]
     w, h, n, seed = (int(x) for x in sys.argv[2:6])
-    opts = {}
+    opts, forced = {}, {}
     for a in sys.argv[6:]:
         k, _, v = a.partition("=")
+        if k == "force":
+            i, _, t = v.partition(":")
+            forced[int(i)] = {"I": 2, "K": 6}[t]          # X264_TYPE_I, X264_TYPE_KEYFRAME
+            continue
         opts[k] = v if _ else None
     H = HL.H
     scene_len = int(opts.pop("scene_len", 0) or 0)
@@ -90,6 +95,7 @@ def main():
         for pl, (sz, off) in enumerate(planes):
             C.memmove(pic.img.plane[pl], f[off:off + sz].ctypes.data, sz)
         pic.i_pts = i
+        pic.i_type = forced.get(i, 0)          # X264_TYPE_AUTO
         size = H.x264_encoder_encode(h_, C.byref(nal), C.byref(nn), C.byref(pic), C.byref(out))
         assert size >= 0
         if size > 0 and first_out is None:

@@ -587,3 +587,27 @@ def test_host_session_aq_mode_2_and_3(tmp_path, mode):
     assert stream != stream1
     dec = O.h264_decode(stream, n, w, h)
     assert len(dec) == n
+
+
+@pytest.mark.parametrize("opts", [["b-adapt=0", "scenecut=0"], ["b-adapt=1", "scenecut=40"]], ids=["fixed", "analysed"])
+def test_host_session_caller_forced_picture_types(tmp_path, opts):
+    """picture types the caller forces in pic_in->i_type (IDR at display index 6, I at 11), in a session with a fixed picture structure (no slice-type object) and in one
+    whose types come from the slice-type analysis: x264's rules hold on the types the session reports — the forced pictures get their types, the picture in front of the
+    IDR closes its GOP as P, runs of B pictures are at most --bframes long, the last picture is not B — every pts comes back once and the stream decodes to every source
+    picture"""
+    import subprocess
+    subprocess.check_call(["make", "-s", "-C", __file__.rsplit("/", 1)[0] + "/stub"])
+    n, w, h = 16, 96, 80
+    info, stream = _host_b_session(tmp_path, n, ["qp=23", "keyint=60", "bframes=3", "b-pyramid=normal", "force=6:K", "force=11:I"] + opts, w, h, seed=5)
+    assert (info["bframes"], info["pyramid"], info["badapt"]) == (3, 2, int(opts[0][-1]))
+    recs = info["recs"]
+    assert sorted(r[1] for r in recs) == list(range(n))                  # the output pts are a permutation of the input's
+    t = _types_by_display(recs)
+    assert t[6] == "I" and t[5] == "P" and t[11] == "i", t               # IDR, a closed GOP in front of it, I
+    assert "BBBB" not in t.replace("R", "B") and t[-1] not in "RB", t
+    dec = O.h264_decode(stream, n, w, h)
+    assert len(dec) == n
+    frames = synth_frames(w, h, n, seed=5)
+    from synth import psnr
+    for d, r in zip(dec, recs):
+        assert psnr(d[:w * h], frames[r[1]][:w * h]) > 33.0

@@ -1,5 +1,5 @@
 """CPU: the session's DECISIONS — picture types (scenecut, --b-adapt 1, keyint / min-keyint, closed GOPs) and single-pass CRF quantisers (I / P from the
-frame costs, B from its nearest references) — as host/encoder.cpp and host/ratecontrol.cpp take them on the stand-in device, against oracle/decide.py, a second restatement of
+frame costs, B from its nearest references) — as host/slicetype.cpp and host/ratecontrol.cpp take them on the stand-in device, against oracle/decide.py, a second restatement of
 the same parts of libx264 written independently of the host code (numpy / plain python over the CPU checker's frame costs).  Reference consumers of
 these decisions: codec.c:1786 (every ICM_COMPRESS), config.c:1504-1514 (CRF / ABR rate control of the dialog)."""
 import ctypes as C

@@ -9,6 +9,7 @@
 #include "dpb.hpp"
 #include "quality.hpp"
 #include "ratecontrol.hpp"
+#include "slicetype.hpp"
 #include <limits.h>
 #include <math.h>
 #include <stdarg.h>
@@ -135,31 +136,15 @@ struct x264_t {
     std::vector<x264gpu_mb> h_mb2;       // second download buffers (the pool reads one pair while the next position lands in the other)
     std::vector<int16_t> h_lv2;
     int dl = 0;                          // download buffer in use for the NEXT position
-    // ---- sessions with B pictures (threads 1; x264 --bframes N --b-pyramid): pictures wait in display order until the mini-GOP they belong to
-    //      is closed by a P / I picture (x264_slicetype_decide with --b-adapt 0: N B pictures between non-B pictures, fewer in front of a keyframe
-    //      or at the end), then leave in coding order: the closing picture, the B-reference of the run, the other B pictures.  The DPB, the
-    //      reference lists and the slice header's share of them come from host/dpb.hpp ----
+    // ---- sessions with B pictures (threads 1; x264 --bframes N --b-pyramid): the picture types and the coding order come from host/slicetype.hpp, the DPB, the
+    //      reference lists and the slice header's share of them from host/dpb.hpp ----
     int bframes = 0, bpyramid = 0, log2_max_poc_lsb = 0;
     // dpbmode: the session runs on the DPB model (host/dpb.hpp) and x264gpu_encode_pictures — every session with B pictures, and sessions
     // without them that use --weightp 2 (whose duplicate references need explicit lists); weightp: the effective --weightp (0 or 2)
     bool dpbmode = false; int weightp = 0;
-    bool weightp_fake = false;           // x264 X264_WEIGHTP_FAKE: --weightp 0 with macroblock-tree and psy: the lookahead still looks for fades, for the tree's sake alone
     Dpb dpb;
-    struct BEntry { int64_t pts; int frame; int slot; int forced; int scenecut; int32_t costs[4]; x264_image_t img;      // forced: 0 auto, 1 I, 2 IDR
-                    int type = 0; int b_scenecut = 1;         // slicetype analysis: the type decided so far (ST_*), "may still be a real scene cut"
-                    Dpb::LumaWeight w;                        // x264_weights_analyse's luma weight of reference 0 when the picture is coded as P (--weightp)
-                    RateControl::Planned planned;             // VBV with rc-lookahead: the types and costs of the pictures coded after this one (x264 i_planned_type / i_planned_satd)
-                    float weighted_cost_delta[18] = { 0 }; }; // f_weighted_cost_delta[distance - 1]: weighted / unweighted cost where the fake analysis found a luma weight
-    // x264's lookahead in its own structure (x264_slicetype_analyse: scenecut against the last non-B picture with flash detection, --b-adapt 1)
-    // on the device's frame costs of arbitrary (p0, p1, b) triples; the half-resolution planes of a queued picture live in the slicetype object's
-    // slot of the same number as its raw picture
-    x264gpu_slicetype *st = nullptr;
-    bool have_last_nonb = false; BEntry last_nonb;
-    int last_keyframe = 0;                // display index of the last IDR picture decided (x264 h->lookahead->i_last_keyframe)
-    int badapt = 0;
+    SliceType slicetype;                 // the display-order and coding-order queues, every picture's type
     std::vector<float *> q_tree;         // device, per queue slot: the quantiser offsets the macroblock-tree left with the picture (AQ offsets until it ran)
-    bool st_aq_costs = false;            // AQ session without macroblock-tree on the DPB model: the rate control reads the AQ-weighted frame costs (i_cost_est_aq)
-    int st_wait = 0;                     // pictures the lookahead holds before a decision (x264 i_slicetype_length: max(bframes, rc-lookahead under mbtree))
     // cross-session batcher (X264GPU_BATCH=N): N sessions of equal geometry and toolset share ONE device encoder with N streams; the pictures
     // they submit are coded in one lock-step launch, every session entropy-codes its own stream on its caller's thread
     struct BatchGroup *batch = nullptr; int batch_idx = -1, batch_n = 0;
@@ -172,7 +157,6 @@ struct x264_t {
                       int qp = 0, scenecut = 0; float qpm = 0.f; int32_t costs[4] = { 0, 0, 0, 0 };
                       x264gpu_quality q = {}; int q_type = 0, q_poc = 0; };      // --psnr / --ssim: the picture's statistics (downloaded with its records), slice type and POC      // the decision hooks' values of THIS picture (x264host_last_decision / _last_qpm)
     Deferred defer[2]; int defer_cur = 0;
-    struct BPlanned { BEntry e; int type; };                                                                            // type: PIC_*
     // ---- several pictures of ONE session in flight (threads-1 sessions on the DPB model; x264's frame threads overlap pictures too).  The b pictures of a mini-GOP, the
     //      B reference between two finished P pictures and the next P picture share only FINISHED references: each is issued through a launch context of its own (the
     //      encoder or a view of it: own scratch, the shared DPB) on a stream of its own, behind the events of the pictures it references, into a slot no picture in
@@ -180,12 +164,10 @@ struct x264_t {
     struct LaunchCtx { x264gpu_encoder *gpu = nullptr; void *stream = nullptr, *ev = nullptr; x264gpu_mb *d_mb = nullptr; int16_t *d_lv = nullptr; bool busy = false; x264gpu_quality *d_q = nullptr; };
     // a picture of a session on the DPB model between plan and finish: what was decided for it, what the device is told, what the slice writer is told;
     // with several pictures in flight also its launch context and the DPB slots it reads or writes
-    struct PicPlan { BPlanned pl; x264gpu_pic pic; SliceParams sp; int nal_ref_idc = 0; double qpf = 0; const float *d_offsets = nullptr; bool direct_auto_write = false; char direct_char = '-';
+    struct PicPlan { SliceType::Pic pl; x264gpu_pic pic; SliceParams sp; int nal_ref_idc = 0; double qpf = 0; const float *d_offsets = nullptr; bool direct_auto_write = false; char direct_char = '-';
                      int ctx = 0; unsigned slots_used = 0; bool last_minigop_b = false; };
     void *ev_la = nullptr;               // the default stream's position when a picture is issued: its upload, offsets and lowres vectors are complete behind it
     std::vector<LaunchCtx> lctx; std::deque<PicPlan> fl; int inflight = 1; int slot_writer[8] = { -1, -1, -1, -1, -1, -1, -1, -1 }; int last_retired_slot = -1;
-    std::deque<BEntry> bq;
-    std::deque<BPlanned> bcoding;
     std::vector<int64_t> all_pts;        // every pts seen, in display order (the dts delay line)
     long coded_count = 0;
     // --direct temporal / auto (x264 h->stat.i_direct_score, frame->i_poc_l0ref0): 1 spatial, 2 temporal, 3 auto; the running skip-probe counts of
@@ -1029,7 +1011,6 @@ static bool open_lookahead(x264_t *h)
     }
     // lookahead queue: rc-lookahead pictures are held back when the macroblock-tree is on (x264's sync lookahead), none otherwise
     h->mbtree = p.rc.b_mb_tree && h->la != nullptr;
-    h->weightp_fake = !h->weightp && h->mbtree && p.analyse.b_psy && h->dpbmode;          // x264 validate_parameters: X264_WEIGHTP_FAKE (sessions on the DPB model: the others' tree has no weight analysis)
     h->L = h->mbtree || h->vbv ? p.rc.i_lookahead : 0;
     // pictures are held back anyway and the quantisers do not depend on coded sizes: overlap the GPU stage of the next picture with
     // the entropy coding of this one (one more picture of delay); X264GPU_HOST_PIPELINE=0 keeps the two stages in one call
@@ -1039,21 +1020,17 @@ static bool open_lookahead(x264_t *h)
         if (h->L > 60) { xlog(&p, X264_LOG_INFO, "rc-lookahead %d -> 60 in sessions with B pictures (the lookahead keeps every queued picture's half-resolution planes and searches on the device)\n", h->L); h->L = 60; p.rc.i_lookahead = 60; }
         h->pipeline = false; h->Q = h->L + 2 * (h->bframes + 1) + 2;      // the lookahead window + display-order queue + the mini-GOP being coded
     }
-    h->st_wait = h->bframes > h->L ? h->bframes : h->L;
+    int st_wait = h->bframes > h->L ? h->bframes : h->L;          // x264 i_slicetype_length
     // x264 h->frames.i_delay: the trellis over picture types looks max(bframes, 3) * 4 pictures ahead
-    if (h->dpbmode && h->bframes && p.i_bframe_adaptive == 2) { const int d = (h->bframes > 3 ? h->bframes : 3) * 4; if (d > h->st_wait) h->st_wait = d; if (h->Q < h->st_wait + 2 * (h->bframes + 1) + 2) h->Q = h->st_wait + 2 * (h->bframes + 1) + 2; }
+    if (h->dpbmode && h->bframes && p.i_bframe_adaptive == 2) { const int d = (h->bframes > 3 ? h->bframes : 3) * 4; if (d > st_wait) st_wait = d; if (h->Q < st_wait + 2 * (h->bframes + 1) + 2) h->Q = st_wait + 2 * (h->bframes + 1) + 2; }
     if (h->dpbmode && h->inflight > 1) h->Q += h->inflight + h->bframes + 1;           // ... + the pictures in flight (their source pictures and offsets are read when their kernels run)
     if (h->dpbmode && h->Q > 128) {          // the lookahead object holds 128 pictures
         const int over = h->Q - 128;
         xlog(&p, X264_LOG_INFO, "lookahead window shortened by %d pictures (128 pictures are held at most)\n", over);
         h->L = h->L > over ? h->L - over : 0; p.rc.i_lookahead = h->L;
-        if (h->st_wait > 128 - 2 * (h->bframes + 1) - 2) h->st_wait = 128 - 2 * (h->bframes + 1) - 2;
+        if (st_wait > 128 - 2 * (h->bframes + 1) - 2) st_wait = 128 - 2 * (h->bframes + 1) - 2;
         h->Q = 128;
     }
-    h->last_keyframe = -p.i_keyint_max;
-    h->badapt = h->bframes ? p.i_bframe_adaptive : 0;
-    // (sessions with a fixed picture structure — no scenecut, b-adapt 0, no mbtree — run without the lookahead object: no fade weights and no
-    // lookahead vectors as search candidates there; that is also what makes the sessions of a batch equal to the same sessions run alone)
     h->rc.vbv_lookahead = h->vbv && h->L > 0;
     if (h->vbv) {
         p.rc.i_lookahead = h->L;
@@ -1063,27 +1040,18 @@ static bool open_lookahead(x264_t *h)
         if (p.b_vfr_input) xlog(&p, X264_LOG_INFO, "VBV: variable frame rate durations are not implemented in the MI355X path: every picture stays in the buffer for 1 / fps\n");
         if (p.rc.f_rf_constant_max > 0) xlog(&p, X264_LOG_WARNING, "crf-max is not implemented in the MI355X path: ignored\n");
     }
-    if (h->dpbmode && (h->badapt || p.i_scenecut_threshold > 0 || h->mbtree || h->rc.vbv_lookahead)) {
-        // x264's own lookahead structure: frame costs of (p0, p1, b) triples on the half-resolution planes (x264_slicetype_analyse)
-        if (x264gpu_slicetype_create(&h->st, p.i_width, p.i_height, 1, h->Q, h->bframes, p.analyse.i_me_method, p.analyse.i_subpel_refine, p.analyse.i_me_range,
-                                     p.analyse.b_weighted_bipred, p.analyse.i_mv_range, h->mbtree || h->vbv ? 1 : 0) != X264GPU_OK) {
-            xlog(&p, X264_LOG_ERROR, "GPU lookahead setup failed: %s\n", x264gpu_last_error());
-            return false;
-        }
-        p.i_bframe_bias = clampi(p.i_bframe_bias, -90, 100);
-        (void)x264gpu_slicetype_set_bframe_bias(h->st, p.i_bframe_bias);          // --b-bias also scales the B costs of slicetype_frame_cost
-    }
     h->aq_strength = h->aq_mode == X264_AQ_VARIANCE ? p.rc.f_aq_strength * 1.0397f : h->aq_mode >= 2 ? p.rc.f_aq_strength : 0.f;      // (modes 2 / 3: the plain strength, x264_adaptive_quant_frame scales it by the picture's mean itself)
-    h->st_aq_costs = h->st && h->la && !h->mbtree && h->aq_strength != 0.f && h->rc.by_cost();
     h->tree_strength = 5.0f * (1.0f - p.rc.f_qcompress);
     h->q_raw.assign((size_t)h->Q, nullptr); h->q_info.assign((size_t)h->Q, nullptr); h->q_aq.assign((size_t)h->Q, nullptr); h->q_tree.assign((size_t)h->Q, nullptr);
+    if (h->dpbmode && !h->slicetype.open(p, h->rc, { h->Q, st_wait, h->mbw, h->mbh, h->bframes, h->bpyramid, h->weightp, h->mbtree, h->vbv, h->aq_strength, h->tree_strength,
+                                                     h->q_raw.data(), h->q_aq.data(), h->q_tree.data() })) return false;
     if (h->Q == 1) h->q_raw[0] = h->d_in;            // no delay: the staging buffer is the one slot; with a delay the ring is separate,
                                                      // because a zero-copy caller rewrites the staging buffer every call
     {
         // one device block per array, cut into the queue's slots (an allocation and a release each cost a fraction of a millisecond: thousands of sessions open and close)
         bool ok = true;
         const size_t Q = (size_t)h->Q, insz_al = (insz + 255) & ~(size_t)255, nmbf = ((size_t)h->nmb * sizeof(float) + 255) & ~(size_t)255, ninfo = ((size_t)h->nmb * 4 * sizeof(int32_t) + 255) & ~(size_t)255;
-        const bool want_aq = h->mbtree || h->st_aq_costs || h->aq_mode >= 2, want_tree = h->mbtree && h->dpbmode;
+        const bool want_aq = h->mbtree || h->slicetype.aq_costs || h->aq_mode >= 2, want_tree = h->mbtree && h->dpbmode;
         if (!h->q_raw[0]) ok = x264gpu_malloc((void **)&h->q_block[0], Q * insz_al) == X264GPU_OK;
         if (ok && h->mbtree) ok = x264gpu_malloc((void **)&h->q_block[1], Q * ninfo) == X264GPU_OK;
         if (ok && want_aq) ok = x264gpu_malloc((void **)&h->q_block[2], Q * nmbf) == X264GPU_OK;
@@ -1574,547 +1542,10 @@ static int encode_queued(x264_t *h, x264_nal_t **pp_nal, int *pi_nal, x264_pictu
 }
 
 
-// ---- sessions with B pictures ---------------------------------------------------------------------------------------------------
-// x264_slicetype_decide with --b-adapt 0 over the display-order queue: the pictures up to the next non-B picture become one mini-GOP.
-// A forced I / IDR picture closes the run in front of it (the picture before an IDR becomes P: closed GOPs); otherwise the run is
-// `bframes` long, or what is left when the input ends (the last picture is never B).  Returns false while more input is needed.
-// ---- x264_slicetype_analyse / x264_slicetype_decide on the device's frame costs (sessions whose slicetype object exists: scenecut or
-//      --b-adapt 1).  frames[0] = the last non-B picture, frames[1..] = the pictures waiting in display order ----
-enum { ST_AUTO = 0, ST_IDR, ST_I, ST_P, ST_BREF, ST_B };
-struct StFrames { x264_t *h; std::vector<x264_t::BEntry *> f; };
-// x264_weights_analyse: guess scale and offset of each plane from the two pictures' statistics, cost the candidates around the guess — luma on the
-// half-resolution planes (per 8x8 block min(mbcmp, intra cost)), the chroma planes at full resolution on the blocks' DC differences — keep a weight
-// if it saves more than 0.2 %.  b_lookahead: luma alone, the guess alone, reference in place (called before a P cost is searched); else, for the P
-// picture about to be coded: +- the distances of the sub-pel level around the guess, the reference motion-compensated by the lookahead's vectors,
-// and the chroma planes once luma has a weight.
-static Dpb::LumaWeight st_weights_analyse(x264_t *h, x264_t::BEntry &fenc, const x264_t::BEntry &ref, int dist, bool b_lookahead)
-{
-    Dpb::LumaWeight none, w;
-    if (dist >= 1 && dist <= 18) fenc.weighted_cost_delta[dist - 1] = 0;
-    uint64_t sf[6], sr[6];
-    if (x264gpu_slicetype_pixel_stats(h->st, fenc.slot, h->q_raw[(size_t)fenc.slot], sf, nullptr) != X264GPU_OK ||
-        x264gpu_slicetype_pixel_stats(h->st, ref.slot, h->q_raw[(size_t)ref.slot], sr, nullptr) != X264GPU_OK) { h->failed = true; return none; }
-    const int nplanes = b_lookahead ? 1 : 3;
-    if (!b_lookahead && (x264gpu_slicetype_chroma_stats(h->st, fenc.slot, h->q_raw[(size_t)fenc.slot], sf + 2, nullptr) != X264GPU_OK ||
-                         x264gpu_slicetype_chroma_stats(h->st, ref.slot, h->q_raw[(size_t)ref.slot], sr + 2, nullptr) != X264GPU_OK)) { h->failed = true; return none; }
-    const float epsilon = 1.f / 128.f;
-    float guess_scale[3] = { 1, 1, 1 }, fenc_mean[3] = { 0, 0, 0 }, ref_mean[3] = { 0, 0, 0 };
-    for (int plane = 0; plane < nplanes; plane++) {
-        const int zero_bias = !sr[2 * plane + 1];
-        const float fenc_var = (float)(sf[2 * plane + 1] + (uint64_t)zero_bias), ref_var = (float)(sr[2 * plane + 1] + (uint64_t)zero_bias);
-        guess_scale[plane] = sqrtf(fenc_var / ref_var);
-        const float npix = plane ? (float)(h->mbw * 8) * (float)(h->mbh * 8) : (float)(h->mbw * 16) * (float)(h->mbh * 16);
-        fenc_mean[plane] = (float)(sf[2 * plane] + (uint64_t)zero_bias) / npix; ref_mean[plane] = (float)(sr[2 * plane] + (uint64_t)zero_bias) / npix;
-    }
-    int chroma_denom = 7;
-    if (!b_lookahead)          // make sure both chroma scale factors fit
-        while (chroma_denom > 0) {
-            const float thresh = 127.f / (1 << chroma_denom);
-            if (guess_scale[1] < thresh && guess_scale[2] < thresh) break;
-            chroma_denom--;
-        }
-    static const uint8_t check_distance[12][2] = { { 0, 0 }, { 0, 0 }, { 0, 1 }, { 0, 1 }, { 0, 1 }, { 0, 1 }, { 0, 1 }, { 1, 1 }, { 1, 1 }, { 2, 1 }, { 2, 1 }, { 4, 2 } };
-    const int sub = clampi(h->param.analyse.i_subpel_refine, 0, 11);
-    const int scale_dist = b_lookahead ? 0 : check_distance[sub][0], offset_dist = b_lookahead ? 0 : check_distance[sub][1];
-    bool planes_on[3] = { false, false, false };
-    int p_scale[3] = { 1, 1, 1 }, p_denom[3] = { 0, 0, 0 }, p_off[3] = { 0, 0, 0 };
-    // (the chroma planes are not checked in the lookahead, or if there was no luma weight)
-    for (int plane = 0; plane < nplanes && !(plane && !planes_on[0]); plane++) {
-        if (fabsf(ref_mean[plane] - fenc_mean[plane]) < 0.5f && fabsf(1.f - guess_scale[plane]) < epsilon) continue;      // early termination
-        int mindenom, minscale, minoff = 0;
-        if (plane) {
-            mindenom = chroma_denom;
-            minscale = clampi((int)roundf(guess_scale[plane] * (1 << chroma_denom)), 0, 255);
-            if (minscale > 127) { planes_on[1] = planes_on[2] = false; break; }
-        } else {
-            // weight_get_h264( round( guess_scale * 128 ), 0 )
-            mindenom = 7; minscale = (int)roundf(guess_scale[0] * 128);
-            while (mindenom > 0 && minscale > 127) { mindenom--; minscale >>= 1; }
-            if (minscale > 127) minscale = 127;
-        }
-        auto cost_of = [&](int on, int scale, int denom, int offset, int64_t &score) {
-            if (!plane) return x264gpu_slicetype_weight_cost(h->st, fenc.slot, ref.slot, dist, on, scale, denom, offset, &score, nullptr) == X264GPU_OK;
-            return x264gpu_slicetype_weight_cost_chroma(h->st, fenc.slot, h->q_raw[(size_t)fenc.slot], h->q_raw[(size_t)ref.slot], dist, plane, on, scale, denom, offset, &score, nullptr) == X264GPU_OK;
-        };
-        int32_t dummy = 0;
-        int64_t score = 0;
-        if ((!plane && x264gpu_slicetype_frame_cost(h->st, fenc.slot, fenc.slot, fenc.slot, 0, 0, &dummy, nullptr) != X264GPU_OK) ||       // the picture's intra costs
-            !cost_of(0, 1, 0, 0, score)) { h->failed = true; return none; }
-        const unsigned origscore = (unsigned)score;
-        unsigned minscore = origscore;
-        if (!minscore) continue;
-        const int start_scale = clampi(minscale - scale_dist, 0, 127), end_scale = clampi(minscale + scale_dist, 0, 127);
-        bool found = false;
-        for (int i_scale = start_scale; i_scale <= end_scale; i_scale++) {
-            int cur_scale = i_scale;
-            int cur_offset = (int)(fenc_mean[plane] - ref_mean[plane] * cur_scale / (1 << mindenom) + 0.5f * b_lookahead);
-            if (cur_offset < -128 || cur_offset > 127) {
-                cur_offset = clampi(cur_offset, -128, 127);
-                float cs = (1 << mindenom) * (fenc_mean[plane] - cur_offset) / ref_mean[plane] + 0.5f;
-                cur_scale = (int)(cs < 0 ? 0 : cs > 127 ? 127 : cs);
-            }
-            const int start_offset = clampi(cur_offset - offset_dist, -128, 127), end_offset = clampi(cur_offset + offset_dist, -128, 127);
-            for (int i_off = start_offset; i_off <= end_offset; i_off++) {
-                if (!cost_of(1, cur_scale, mindenom, i_off, score)) { h->failed = true; return none; }
-                if ((unsigned)score < minscore) { minscore = (unsigned)score; minscale = cur_scale; minoff = i_off; found = true; }
-                if (minoff == start_offset && i_off != start_offset) break;          // the previous offset was better: no more
-            }
-        }
-        if (!plane) while (mindenom > 0 && !(minscale & 1)) { mindenom--; minscale >>= 1; }      // a smaller denominator if possible
-        if (!found || (minscale == 1 << mindenom && minoff == 0) || (float)minscore / origscore > 0.998f) continue;
-        planes_on[plane] = true; p_scale[plane] = minscale; p_denom[plane] = mindenom; p_off[plane] = minoff;
-        if (h->weightp_fake && !plane && dist >= 1 && dist <= 18) fenc.weighted_cost_delta[dist - 1] = (float)minscore / origscore;
-    }
-    if (!planes_on[0]) return none;           // (x264 keeps chroma weights only beside a luma weight: they are not even analysed without one)
-    w.on = 1; w.scale = p_scale[0]; w.denom = p_denom[0]; w.offset = p_off[0];
-    if (planes_on[1] || planes_on[2]) {
-        // optimise and unify the chroma denominator: a plane weighted alone leaves the other with the implicit scale 1 << denom, which 7 cannot carry
-        int denom = planes_on[1] ? p_denom[1] : p_denom[2];
-        const bool both = planes_on[1] && planes_on[2];
-        while ((!both && denom == 7) || (denom > 0 && !(planes_on[1] && (p_scale[1] & 1)) && !(planes_on[2] && (p_scale[2] & 1)))) {
-            denom--;
-            for (int i = 1; i <= 2; i++) if (planes_on[i]) { p_scale[i] >>= 1; p_denom[i] = denom; }
-        }
-        w.cdenom = denom;
-        for (int c = 0; c < 2; c++) if (planes_on[c + 1]) { w.con[c] = 1; w.cscale[c] = p_scale[c + 1]; w.coffset[c] = p_off[c + 1]; }
-    }
-    return w;
-}
-
-static int st_cost(StFrames &F, int p0, int p1, int b)
-{
-    int32_t sc = 0;
-    Dpb::LumaWeight w;
-    // slicetype_frame_cost: a P cost that is searched for the first time runs on the reference weighted by the lookahead's analysis
-    if ((F.h->weightp || F.h->weightp_fake) && p1 == b && b != p0 && !x264gpu_slicetype_lowres_mvs(F.h->st, F.f[(size_t)b]->slot, 0, b - p0) &&
-        x264gpu_slicetype_cost_est(F.h->st, F.f[(size_t)b]->slot, b - p0, 0, 0) < 0)
-        w = st_weights_analyse(F.h, *F.f[(size_t)b], *F.f[(size_t)p0], b - p0, true);
-    if (x264gpu_slicetype_frame_cost_w(F.h->st, F.f[(size_t)p0]->slot, F.f[(size_t)p1]->slot, F.f[(size_t)b]->slot, b - p0, p1 - b, w.on, w.scale, w.denom, w.offset, &sc, nullptr) != X264GPU_OK) {
-        xlog(&F.h->param, X264_LOG_ERROR, "lookahead frame cost failed: %s\n", x264gpu_last_error());
-        F.h->failed = true;
-    }
-    return sc;
-}
-// scenecut_internal: P cost against I cost of frames[p1], the bias growing with the distance from the last keyframe
-static bool st_scenecut_internal(StFrames &F, int p0, int p1)
-{
-    x264_t *h = F.h;
-    const x264_param_t &p = h->param;
-    st_cost(F, p0, p1, p1);
-    const x264_t::BEntry *fr = F.f[(size_t)p1];
-    const int icost = x264gpu_slicetype_cost_est(h->st, fr->slot, 0, 0, 0), pcost = x264gpu_slicetype_cost_est(h->st, fr->slot, p1 - p0, 0, 0);
-    const int gop = fr->frame - h->last_keyframe;
-    const float tmax = (float)(p.i_scenecut_threshold / 100.0);
-    float tmin = (float)(tmax * 0.25), bias;
-    if (p.i_keyint_min == p.i_keyint_max) tmin = tmax;
-    if (gop <= p.i_keyint_min / 4) bias = tmin / 4;
-    else if (gop <= p.i_keyint_min) bias = tmin * gop / p.i_keyint_min;
-    else bias = tmin + (tmax - tmin) * (gop - p.i_keyint_min) / (p.i_keyint_max - p.i_keyint_min);
-    return pcost >= (1.0 - bias) * icost;
-}
-// scenecut: with B pictures a short flash between two scenes must not become a keyframe (x264 looks one picture past p1 under --b-adapt 1)
-static bool st_scenecut(StFrames &F, int p0, int p1, bool real, int num_frames, int i_max_search)
-{
-    x264_t *h = F.h;
-    if (real && h->bframes) {
-        const int origmaxp1 = p0 + 1 + (h->badapt == 2 ? h->bframes : 1), maxp1 = origmaxp1 < num_frames ? origmaxp1 : num_frames;      // the trellis may put bframes pictures between p0 and p1
-        for (int curp1 = p1; curp1 <= maxp1; curp1++)
-            if (!st_scenecut_internal(F, p0, curp1))
-                for (int i = curp1; i > p0; i--) F.f[(size_t)i]->b_scenecut = 0;          // nothing between p0 and curp1 can be a real scene cut
-        for (int curp0 = p0; curp0 <= maxp1; curp0++)
-            if (origmaxp1 > i_max_search || (curp0 < maxp1 && st_scenecut_internal(F, curp0, maxp1)))
-                F.f[(size_t)curp0]->b_scenecut = 0;                                     // the p0 of a scene cut cannot be the p1 of one
-    }
-    if (!F.f[(size_t)p1]->b_scenecut) return false;
-    return st_scenecut_internal(F, p0, p1);
-}
-// x264's macroblock_tree over frames[0 .. num_frames] with the types decided so far (tests/mbtree_walk.py is the same walk): every picture hands
-// the cost its references explain back to them, last picture first; the next picture to be coded (and the B-reference of its run) get their
-// quantiser offsets.  b_intra: the pass x264 runs for a keyframe after it was decided (frames[0] = that keyframe).
-static void st_macroblock_tree(x264_t *h, StFrames &F, int num_frames, bool b_intra)
-{
-    const int idx = b_intra ? 0 : 1;
-    auto isb = [&](int i) { return F.f[(size_t)i]->type == ST_B || F.f[(size_t)i]->type == ST_BREF; };
-    auto slot = [&](int i) { return F.f[(size_t)i]->slot; };
-    auto prop = [&](int p0, int p1, int b, int referenced) {
-        if (x264gpu_slicetype_propagate(h->st, slot(p0), slot(p1), slot(b), b - p0, p1 - b, referenced, nullptr) != X264GPU_OK) {
-            xlog(&h->param, X264_LOG_ERROR, "macroblock-tree failed: %s\n", x264gpu_last_error());
-            h->failed = true;
-        }
-    };
-    auto clear = [&](int i) { if (x264gpu_slicetype_clear_propagate(h->st, slot(i), nullptr) != X264GPU_OK) h->failed = true; };
-    auto finish = [&](int i, int ref0_distance) {
-        st_cost(F, i, i, i);          // (the intra costs the analysis left with the picture; a no-op when they exist)
-        // macroblock_tree_finish: a fade the (fake) weight analysis explained is not held against the picture
-        float weightdelta = 0.0;
-        if (ref0_distance >= 1 && ref0_distance <= 18 && F.f[(size_t)i]->weighted_cost_delta[ref0_distance - 1] > 0) weightdelta = (float)(1.0 - F.f[(size_t)i]->weighted_cost_delta[ref0_distance - 1]);
-        if (x264gpu_slicetype_finish(h->st, slot(i), h->tree_strength, weightdelta, h->q_tree[(size_t)slot(i)], nullptr) != X264GPU_OK) h->failed = true;
-    };
-    if (b_intra) st_cost(F, 0, 0, 0);
-    int i = num_frames;
-    while (i > 0 && isb(i)) i--;
-    int last_nonb = i, bframes = 0;
-    if (last_nonb < idx) return;
-    clear(last_nonb);
-    while (i-- > idx) {
-        int cur_nonb = i;
-        while (isb(cur_nonb) && cur_nonb > 0) cur_nonb--;
-        if (cur_nonb < idx) break;
-        // (distances beyond bframes + 1 cannot occur: the analysis never leaves longer runs)
-        st_cost(F, cur_nonb, last_nonb, last_nonb);
-        clear(cur_nonb);
-        bframes = last_nonb - cur_nonb - 1;
-        if (h->bpyramid && bframes > 1) {
-            const int middle = (bframes + 1) / 2 + cur_nonb;
-            st_cost(F, cur_nonb, last_nonb, middle);
-            clear(middle);
-            while (i > cur_nonb) {
-                const int p0 = i > middle ? middle : cur_nonb, p1 = i < middle ? middle : last_nonb;
-                if (i != middle) { st_cost(F, p0, p1, i); prop(p0, p1, i, 0); }
-                i--;
-            }
-            prop(cur_nonb, last_nonb, middle, 1);
-        } else
-            while (i > cur_nonb) { st_cost(F, cur_nonb, last_nonb, i); prop(cur_nonb, last_nonb, i, 0); i--; }
-        prop(cur_nonb, last_nonb, last_nonb, 1);
-        last_nonb = cur_nonb;
-        if (h->failed) return;
-    }
-    finish(last_nonb, last_nonb);
-    if (h->bpyramid && bframes > 1) finish(last_nonb + (bframes + 1) / 2, 0);
-}
-
-// x264 slicetype_path_cost: the cost of coding frames[1 ..] with the types in `path` ('P' / 'B' / 'I' per picture) — each non-B picture against the one
-// before it, the B pictures between them against both (through the middle one under b-pyramid); stops early beyond `threshold`
-static uint64_t st_path_cost(StFrames &F, const char *path0, uint64_t threshold)
-{
-    x264_t *h = F.h;
-    uint64_t cost = 0;
-    int loc = 1, cur_nonb = 0;
-    const char *path = path0 - 1;          // the first path element is the second frame
-    while (path[loc]) {
-        int next_nonb = loc;
-        while (path[next_nonb] == 'B') next_nonb++;
-        cost += path[next_nonb] == 'P' ? st_cost(F, cur_nonb, next_nonb, next_nonb) : st_cost(F, next_nonb, next_nonb, next_nonb);
-        if (cost > threshold || h->failed) break;
-        if (h->bpyramid && next_nonb - cur_nonb > 2) {
-            const int middle = cur_nonb + (next_nonb - cur_nonb) / 2;
-            cost += st_cost(F, cur_nonb, next_nonb, middle);
-            for (int next_b = loc; next_b < middle && cost < threshold; next_b++) cost += st_cost(F, cur_nonb, middle, next_b);
-            for (int next_b = middle + 1; next_b < next_nonb && cost < threshold; next_b++) cost += st_cost(F, middle, next_nonb, next_b);
-        } else
-            for (int next_b = loc; next_b < next_nonb && cost < threshold; next_b++) cost += st_cost(F, cur_nonb, next_nonb, next_b);
-        loc = next_nonb + 1;
-        cur_nonb = next_nonb;
-    }
-    return cost;
-}
-
-// x264 slicetype_path (--b-adapt 2): the best way to code the first `length` pictures ends in 0 .. bframes B pictures and a P picture behind the
-// best way to code the pictures in front of them (Viterbi over the lengths; best_paths is indexed by length modulo 17)
-constexpr int ST_PATH_MAX = 96;
-static void st_path(StFrames &F, int length, char (*best_paths)[ST_PATH_MAX + 1])
-{
-    x264_t *h = F.h;
-    char paths[2][ST_PATH_MAX + 1];
-    const int num_paths = h->bframes + 1 < length ? h->bframes + 1 : length;
-    uint64_t best_cost = ~0ull >> 1;
-    int best_possible = 0, idx = 0;
-    memset(paths, 0, sizeof(paths));
-    for (int path = 0; path < num_paths; path++) {
-        const int len = length - (path + 1);
-        memcpy(paths[idx], best_paths[len % 17], (size_t)len);
-        memset(paths[idx] + len, 'B', (size_t)path);
-        paths[idx][len + path] = 'P'; paths[idx][len + path + 1] = 0;
-        int possible = 1;
-        for (int i = 1; i <= length; i++) {
-            const int t = F.f[(size_t)i]->type;
-            if (t == ST_AUTO) continue;
-            if (t == ST_B || t == ST_BREF) possible = possible && (i < len || i == length || paths[idx][i - 1] == 'B');
-            else {
-                possible = possible && (i < len || paths[idx][i - 1] != 'B');
-                paths[idx][i - 1] = t == ST_I || t == ST_IDR ? 'I' : 'P';
-            }
-        }
-        if (possible || !best_possible) {
-            if (possible && !best_possible) best_cost = ~0ull >> 1;
-            const uint64_t cost = st_path_cost(F, paths[idx], best_cost);
-            if (cost < best_cost) { best_cost = cost; best_possible = possible; idx ^= 1; }
-        }
-    }
-    memcpy(best_paths[length % 17], paths[idx ^ 1], (size_t)length);
-    best_paths[length % 17][length] = 0;
-}
-
-// x264's vbv_lookahead: the pictures of the window in coding order (each non-B picture, then the B pictures in front of it) with the types the analysis gave them
-// and their frame costs (vbv_frame_cost: the AQ-weighted ones in AQ sessions), left with the picture that is coded next — the first non-B picture of the window,
-// or (keyframe) frames[0] itself, a keyframe that has just been decided.  The window's last picture is not part of the plan, as in x264
-static int st_vbv_frame_cost(StFrames &F, int p0, int p1, int b)
-{
-    x264_t *h = F.h;
-    int32_t cost = st_cost(F, p0, p1, b);
-    if (!h->failed && h->aq_strength != 0.f && (h->mbtree || h->st_aq_costs) &&
-        x264gpu_slicetype_cost_aq(h->st, F.f[(size_t)b]->slot, b - p0, p1 - b, &cost, nullptr) != X264GPU_OK) {
-        xlog(&h->param, X264_LOG_ERROR, "lookahead frame cost failed: %s\n", x264gpu_last_error());
-        h->failed = true;
-    }
-    return cost;
-}
-static void st_vbv_lookahead(StFrames &F, int num_frames, bool keyframe)
-{
-    auto isb = [&](int i) { const int t = F.f[(size_t)i]->type; return t == ST_B || t == ST_BREF; };
-    int last_nonb = 0, cur_nonb = 1, idx = 0;
-    while (cur_nonb < num_frames && isb(cur_nonb)) cur_nonb++;
-    const int next_nonb = keyframe ? last_nonb : cur_nonb;
-    RateControl::Planned &pl = F.f[(size_t)next_nonb]->planned;
-    while (cur_nonb < num_frames && idx < RateControl::PLAN_MAX && !F.h->failed) {
-        if (next_nonb != cur_nonb) {          // the P / I picture (its cost as the type it was given; not next_nonb's own)
-            const int t = F.f[(size_t)cur_nonb]->type;
-            const bool is_i = t == ST_I || t == ST_IDR;
-            pl.satd[idx] = st_vbv_frame_cost(F, is_i ? cur_nonb : last_nonb, cur_nonb, cur_nonb);
-            pl.type[idx] = t == ST_IDR ? PIC_IDR : t == ST_I ? PIC_I : PIC_P;
-            idx++;
-        }
-        for (int i = last_nonb + 1; i < cur_nonb && idx < RateControl::PLAN_MAX; i++, idx++) {          // the B pictures, coded behind it
-            pl.satd[idx] = st_vbv_frame_cost(F, last_nonb, cur_nonb, i);
-            pl.type[idx] = PIC_B;
-        }
-        last_nonb = cur_nonb;
-        cur_nonb++;
-        while (cur_nonb <= num_frames && isb(cur_nonb)) cur_nonb++;
-    }
-    pl.type[idx] = RateControl::PLAN_END;
-}
-
-static void st_analyse(x264_t *h, StFrames &F, int framecnt, bool keyframe = false)
-{
-    const x264_param_t &p = h->param;
-    auto type = [&](int i) -> int & { return F.f[(size_t)i]->type; };
-    auto forced = [&](int i) { const int f = F.f[(size_t)i]->forced; return f == 2 ? ST_IDR : f == 1 ? ST_I : ST_AUTO; };
-    auto auto_or_i = [](int t) { return t == ST_AUTO || t == ST_I || t == ST_IDR; };
-    const int i_max_search = framecnt;
-    if (!framecnt) return;
-    const int keyint_limit = p.i_keyint_max - F.f[0]->frame + h->last_keyframe - 1;
-    int num_frames = framecnt < keyint_limit ? framecnt : keyint_limit;
-    const int orig_num_frames = num_frames;
-    if (p.analyse.b_psy && h->mbtree) num_frames = framecnt;           // psy-wise the pictures before a keyframe must not lose their share of the tree
-    else if (num_frames <= 0) { type(1) = ST_I; return; }
-    // a picture whose type the caller forced ends the window in front of it (x264 warns and overrides; here the analysis stops short)
-    for (int j = 2; j <= num_frames; j++) if (forced(j) != ST_AUTO) { num_frames = j - 1; break; }
-    if (!keyframe && auto_or_i(type(1)) && p.i_scenecut_threshold && st_scenecut(F, 0, 1, true, orig_num_frames, i_max_search)) {
-        if (type(1) == ST_AUTO) type(1) = ST_I;
-        return;
-    }
-    int num_bframes = 0, reset_start, num_analysed = num_frames;
-    if (h->bframes) {
-        if (h->badapt == 2) {
-            if (num_frames > ST_PATH_MAX) num_frames = ST_PATH_MAX;
-            if (num_frames > 1) {
-                static thread_local char best_paths[17][ST_PATH_MAX + 1];
-                memset(best_paths, 0, sizeof(best_paths));
-                best_paths[1][0] = 'P';
-                const int best_path_index = num_frames % 17;
-                for (int j = 2; j <= num_frames && !h->failed; j++) st_path(F, j, best_paths);
-                if (h->failed) return;
-                for (int j = 1; j < num_frames; j++) {
-                    if (best_paths[best_path_index][j - 1] != 'B') { if (type(j) == ST_AUTO || type(j) == ST_B || type(j) == ST_BREF) type(j) = ST_P; }
-                    else if (type(j) == ST_AUTO) type(j) = ST_B;
-                }
-            }
-            if (type(num_frames) == ST_AUTO || type(num_frames) == ST_B || type(num_frames) == ST_BREF) type(num_frames) = ST_P;
-            while (num_bframes < num_frames && type(num_bframes + 1) == ST_B) num_bframes++;
-        } else if (h->badapt == 1) {
-            // X264_B_ADAPT_FAST as the x264 generation this host restates has it (the one whose trellis loader and scene-cut loop know forced types): picture j becomes
-            // a B picture when the path "..BP" from the last non-B picture costs less than "..PP" (slicetype_path_cost on both), runs no longer than --bframes.
-            // (Older x264 compared pairwise frame costs against thresholds — INTER_THRESH / P_SENS_BIAS; which of the two the driver's core 157 carries cannot be
-            // checked here: DESIGN.md §0.)
-            auto isb = [&](int i) { return type(i) == ST_B || type(i) == ST_BREF; };
-            int last_nonb = 0, num_bf = h->bframes;
-            char path[ST_PATH_MAX + 4];
-            for (int j = 1; j < num_frames && !h->failed; j++) {
-                if (j - 1 > 0 && isb(j - 1)) num_bf--;
-                else { last_nonb = j - 1; num_bf = h->bframes; }
-                if (!num_bf) { if (type(j) == ST_AUTO || isb(j)) type(j) = ST_P; continue; }
-                if (type(j) != ST_AUTO) continue;
-                if (isb(j + 1)) { type(j) = ST_P; continue; }
-                const int bfr = j - last_nonb - 1;
-                StFrames sub;
-                sub.h = h;
-                sub.f.assign(F.f.begin() + last_nonb, F.f.end());
-                memset(path, 'B', (size_t)bfr);
-                strcpy(path + bfr, "PP");
-                const uint64_t cost_p = st_path_cost(sub, path, ~0ull >> 1);
-                strcpy(path + bfr, "BP");
-                const uint64_t cost_b = st_path_cost(sub, path, cost_p);
-                type(j) = cost_b < cost_p ? ST_B : ST_P;
-            }
-            if (h->failed) return;
-            if (type(num_frames) == ST_AUTO || type(num_frames) == ST_B || type(num_frames) == ST_BREF) type(num_frames) = ST_P;
-            while (num_bframes < num_frames && type(num_bframes + 1) == ST_B) num_bframes++;
-        } else {
-            num_bframes = num_frames - 1 < h->bframes ? num_frames - 1 : h->bframes;
-            for (int j = 1; j < num_frames; j++) type(j) = (j % (num_bframes + 1)) ? ST_B : ST_P;
-            type(num_frames) = ST_P;
-        }
-        // scene cut inside the first mini-GOP: the picture in front of it closes the run
-        for (int j = 1; j < num_bframes + 1; j++)
-            if (forced(j) == ST_AUTO && auto_or_i(forced(j + 1)) && p.i_scenecut_threshold && st_scenecut(F, j, j + 1, false, orig_num_frames, i_max_search)) {
-                type(j) = ST_P;
-                num_analysed = j;
-                break;
-            }
-        reset_start = keyframe ? 1 : num_bframes + 2 < num_analysed + 1 ? num_bframes + 2 : num_analysed + 1;
-    } else {
-        for (int j = 1; j <= num_frames; j++) if (auto_or_i(forced(j))) type(j) = ST_P;
-        reset_start = keyframe ? 1 : 2;
-    }
-    // the macroblock-tree over the window, no farther than a keyframe interval
-    if (h->mbtree) st_macroblock_tree(h, F, num_frames < p.i_keyint_max ? num_frames : p.i_keyint_max, keyframe);
-    if (h->failed) return;
-    // enforce the keyframe limit
-    {
-        int last_keyframe = h->last_keyframe, last_possible = 0;
-        for (int j = 1; j <= num_frames; j++) {
-            int kd = F.f[(size_t)j]->frame - last_keyframe;
-            if (auto_or_i(forced(j))) last_possible = j;
-            if (kd >= p.i_keyint_max) {
-                if (last_possible != 0 && last_possible != j) { j = last_possible; kd = F.f[(size_t)j]->frame - last_keyframe; }
-                last_possible = 0;
-                if (type(j) != ST_IDR) type(j) = ST_IDR;
-            }
-            if (type(j) == ST_I && kd >= p.i_keyint_min) type(j) = ST_IDR;
-            if (type(j) == ST_IDR) { last_keyframe = F.f[(size_t)j]->frame; if (j > 1 && (type(j - 1) == ST_B || type(j - 1) == ST_BREF)) type(j - 1) = ST_P; }
-        }
-    }
-    if (h->rc.vbv_lookahead) st_vbv_lookahead(F, num_frames, keyframe);
-    if (h->failed) return;
-    // the pictures behind the first mini-GOP are decided again when their turn comes
-    for (int j = reset_start; j <= framecnt; j++) type(j) = forced(j);
-}
-
-// x264_slicetype_decide: -> index of the picture that closes the first mini-GOP of the queue and its type (PIC_*)
-static bool st_decide(x264_t *h, bool flushing, int &j_out, int &closing_out)
-{
-    const x264_param_t &p = h->param;
-    const int n = (int)h->bq.size();
-    if (!flushing && n <= h->st_wait) return false;
-    for (auto &e : h->bq) e.type = e.forced == 2 ? ST_IDR : e.forced == 1 ? ST_I : ST_AUTO;
-    if (h->rc.pass2) {
-        // x264_ratecontrol_slice_type: the second pass codes every picture as the type the first pass gave it (the B-reference of a run is placed by
-        // the same rule in both passes)
-        for (auto &e : h->bq) {
-            const RateControl::Pass2Entry *pe = h->rc.plan(e.frame);
-            if (!pe) continue;
-            const char t = pe->type;
-            e.type = t == 'I' ? ST_IDR : t == 'i' ? ST_I : t == 'P' ? ST_P : ST_B;
-        }
-    } else
-    if (h->have_last_nonb && ((h->bframes && h->badapt) || p.i_scenecut_threshold || h->mbtree || h->rc.vbv_lookahead)) {
-        StFrames F;
-        F.h = h;
-        F.f.push_back(&h->last_nonb);
-        const int framecnt = n < h->st_wait + 1 ? n : h->st_wait + 1;          // what the lookahead holds for sure (deterministic mode), except at the end
-        for (int i = 0; i < framecnt; i++) F.f.push_back(&h->bq[(size_t)i]);
-        st_analyse(h, F, framecnt);
-        if (h->failed) return false;
-    }
-    int bfr;
-    for (bfr = 0;; bfr++) {
-        x264_t::BEntry &frm = h->bq[(size_t)bfr];
-        if (frm.frame - h->last_keyframe >= p.i_keyint_max) frm.type = ST_IDR;              // limit the GOP size
-        if (frm.type == ST_I && frm.frame - h->last_keyframe >= p.i_keyint_min) frm.type = ST_IDR;
-        if (frm.type == ST_IDR) {                                                          // close the GOP
-            h->last_keyframe = frm.frame;
-            // x264 keeps i_type on the frame; here the queue's types are re-derived from `forced` on every call, so the decision is pinned
-            // there: the IDR stays an IDR when it is reached after the run in front of it (which closes as P) has been coded
-            if (bfr > 0) { frm.forced = 2; bfr--; h->bq[(size_t)bfr].type = ST_P; }
-        }
-        if (bfr == h->bframes || bfr + 1 >= n) { if (frm.type == ST_AUTO || frm.type == ST_B || frm.type == ST_BREF) frm.type = ST_P; }
-        if (frm.type == ST_AUTO) frm.type = ST_B;
-        else if (frm.type != ST_B && frm.type != ST_BREF) break;
-    }
-    const int t = h->bq[(size_t)bfr].type;
-    j_out = bfr; closing_out = t == ST_IDR ? PIC_IDR : t == ST_I ? PIC_I : PIC_P;
-    return true;
-}
-
-static bool bmode_decide(x264_t *h, bool flushing)
-{
-    if (!h->bcoding.empty() || h->bq.empty()) return !h->bcoding.empty();
-    const int n = (int)h->bq.size();
-    if (!flushing && n <= (h->st ? h->st_wait : h->bframes)) return false;          // the lookahead x264 keeps in front of the slice-type decision
-    int j = -1;                                       // index of the closing picture
-    if (h->st) {
-        int closing = PIC_P;
-        if (!st_decide(h, flushing, j, closing)) return false;
-        if (h->weightp && closing == PIC_P && h->have_last_nonb) {
-            // x264_slicetype_decide: "analyse for weighted P frames" — the picture about to be coded against the last non-B picture
-            h->bq[(size_t)j].w = st_weights_analyse(h, h->bq[(size_t)j], h->last_nonb, j + 1, false);
-            if (h->failed) return false;
-        }
-        if (h->rc.by_cost()) {
-            // x264_rc_analyse_slice: the closing picture's complexity is its frame cost as the type it was given — the I cost, or the P cost
-            // against the last non-B picture (distance = run length + 1), from the lookahead that decided the types
-            x264_t::BEntry &c = h->bq[(size_t)j];
-            int32_t ic = 0, pc = 0;
-            bool ok = x264gpu_slicetype_frame_cost(h->st, c.slot, c.slot, c.slot, 0, 0, &ic, nullptr) == X264GPU_OK;
-            if (ok && closing == PIC_P && h->have_last_nonb) ok = x264gpu_slicetype_frame_cost(h->st, h->last_nonb.slot, c.slot, c.slot, j + 1, 0, &pc, nullptr) == X264GPU_OK;
-            else pc = ic;
-            if (ok && h->st_aq_costs) {
-                // x264_rc_analyse_slice: "in AQ, use the weighted score instead" (without macroblock-tree; with it the rate factor does not read the cost)
-                const bool isp = closing == PIC_P && h->have_last_nonb;
-                ok = x264gpu_slicetype_cost_aq(h->st, c.slot, 0, 0, &ic, nullptr) == X264GPU_OK && (!isp || x264gpu_slicetype_cost_aq(h->st, c.slot, j + 1, 0, &pc, nullptr) == X264GPU_OK);
-                if (!isp) pc = ic;
-            }
-            if (!ok) { xlog(&h->param, X264_LOG_ERROR, "lookahead frame cost failed: %s\n", x264gpu_last_error()); h->failed = true; return false; }
-            c.costs[0] = ic; c.costs[1] = pc;
-        }
-        h->bcoding.push_back({ h->bq[(size_t)j], closing });
-        h->last_nonb = h->bq[(size_t)j]; h->have_last_nonb = true;
-        const int bref = h->bpyramid && j > 1 ? (j - 1) / 2 : -1;
-        if (bref >= 0) h->bcoding.push_back({ h->bq[(size_t)bref], PIC_BREF });
-        for (int i = 0; i < j; i++) if (i != bref) h->bcoding.push_back({ h->bq[(size_t)i], PIC_B });
-        h->bq.erase(h->bq.begin(), h->bq.begin() + j + 1);
-        if ((h->mbtree || h->rc.vbv_lookahead) && (closing == PIC_IDR || closing == PIC_I)) {
-            // x264 lookahead_slicetype_decide: "for MB-tree and VBV lookahead, we have to perform propagation analysis on I-frames too" — the analysis again
-            // with the keyframe as frames[0]; it decides nothing, its tree reaches the keyframe itself, its plan is the keyframe's
-            StFrames F;
-            F.h = h;
-            F.f.push_back(&h->last_nonb);
-            const int n2 = (int)h->bq.size(), framecnt = n2 < h->st_wait + 1 - (j + 1) ? n2 : (h->st_wait + 1 - (j + 1) > 0 ? h->st_wait + 1 - (j + 1) : 0);
-            for (auto &e : h->bq) e.type = e.forced == 2 ? ST_IDR : e.forced == 1 ? ST_I : ST_AUTO;
-            for (int i = 0; i < framecnt; i++) F.f.push_back(&h->bq[(size_t)i]);
-            h->last_nonb.type = closing == PIC_IDR ? ST_IDR : ST_I;
-            if (framecnt > 0) st_analyse(h, F, framecnt, true);
-            else if (h->mbtree) st_macroblock_tree(h, F, 0, true);
-            if (h->failed) return false;
-            h->bcoding.front().e.planned = h->last_nonb.planned;          // (the closing picture was queued before its plan was made)
-        }
-        return true;
-    }
-    if (h->bq[0].forced) j = 0;
-    else {
-        for (int i = 0; i < n && i <= h->bframes; i++) {
-            if (h->bq[(size_t)i].forced == 2) { j = i > 0 ? i - 1 : 0; break; }        // IDR next: the picture before it closes the run as P
-            if (h->bq[(size_t)i].forced == 1) { j = i; break; }                        // I picture: B pictures in front of it may predict from it
-            if (i == h->bframes) { j = i; break; }
-        }
-        if (j < 0) { if (!flushing) return false; j = n - 1; }                      // end of input: the last picture closes the run
-    }
-    const int closing = h->bq[(size_t)j].forced == 2 ? PIC_IDR : h->bq[(size_t)j].forced == 1 ? PIC_I : PIC_P;
-    h->bcoding.push_back({ h->bq[(size_t)j], closing });
-    const int bref = h->bpyramid && j > 1 ? (j - 1) / 2 : -1;
-    if (bref >= 0) h->bcoding.push_back({ h->bq[(size_t)bref], PIC_BREF });
-    for (int i = 0; i < j; i++) if (i != bref) h->bcoding.push_back({ h->bq[(size_t)i], PIC_B });
-    h->bq.erase(h->bq.begin(), h->bq.begin() + j + 1);
-    return true;
-}
-
-// the bits of the NAL units a picture's access unit opens with (VBV: x264_ratecontrol_start's overhead)
 // --nal-hrd: the delays a picture's SEI messages carry, from the buffer's state in front of it (Annex C: removal times are cpb_removal_delay clock ticks behind
 // the last buffering-period picture's, two ticks a picture; a picture is output dpb_output_delay ticks after its removal, which puts the output times in display
 // order two ticks apart: 2 x (display index - coding index + the reorder depth))
-static bool au_timing(const x264_t *h, const x264_t::BPlanned &pl, AuTiming &tm)
+static bool au_timing(const x264_t *h, const SliceType::Pic &pl, AuTiming &tm)
 {
     if (!h->hrd.present) return false;
     const double rate = h->hrd.bit_rate_unscaled, size = h->hrd.cpb_size_unscaled;
@@ -2127,7 +1558,7 @@ static bool au_timing(const x264_t *h, const x264_t::BPlanned &pl, AuTiming &tm)
     return true;
 }
 // the bits of the NAL units a picture's access unit opens with (VBV: x264_ratecontrol_start's overhead)
-static long au_overhead_bits(const x264_t *h, const x264_t::BPlanned &pl)
+static long au_overhead_bits(const x264_t *h, const SliceType::Pic &pl)
 {
     std::vector<uint8_t> bytes; std::vector<size_t> off; std::vector<int> types;
     AuTiming tm;
@@ -2147,12 +1578,12 @@ static long au_overhead_bits(const x264_t *h, const x264_t::BPlanned &pl)
 // in flight: when the picture is issued).  serial: one picture at a time, so --direct auto can follow the skip counts of the picture before
 static void bmode_plan(x264_t *h, x264_t::PicPlan &f, x264gpu_encoder *gpu, long coded_index, bool serial)
 {
-    f.pl = h->bcoding.front();
-    h->bcoding.pop_front();
-    const x264_t::BPlanned &pl = f.pl;
+    f.pl = h->slicetype.pop();
+    const SliceType::Pic &pl = f.pl;
+    const std::deque<SliceType::Pic> &behind = h->slicetype.queue();
     // the disposable pictures coded right behind this one (x264_reference_hierarchy_reset looks at them)
     int fc[16], ff[16], nf = 0;
-    for (size_t i = 0; i < h->bcoding.size() && nf < 16 && h->bcoding[i].type == PIC_B; i++) { fc[nf] = (int)(coded_index + 1 + (long)i); ff[nf] = h->bcoding[i].e.frame; nf++; }
+    for (size_t i = 0; i < behind.size() && nf < 16 && behind[i].type == PIC_B; i++) { fc[nf] = (int)(coded_index + 1 + (long)i); ff[nf] = behind[i].e.frame; nf++; }
     const DpbPlan plan = h->dpb.plan(pl.type, pl.e.frame, nf, fc, ff, pl.type == PIC_P && pl.e.w.on ? &pl.e.w : nullptr);
     f.nal_ref_idc = plan.nal_ref_idc;
     x264gpu_pic &pic = f.pic;
@@ -2162,8 +1593,8 @@ static void bmode_plan(x264_t *h, x264_t::PicPlan &f, x264gpu_encoder *gpu, long
     if (h->vbv) {
         // x264 frame->i_bframes / b_last_minigop_bframe (every picture of a mini-GOP knows how many B pictures it holds), and the header NAL units the
         // access unit opens with (x264_ratecontrol_start's overhead)
-        if (!is_b) h->minigop_b = (int)h->bcoding.size();          // (what is left of the mini-GOP in the coding queue: its B pictures)
-        f.last_minigop_b = is_b && h->bcoding.empty();
+        if (!is_b) h->minigop_b = (int)behind.size();          // (what is left of the mini-GOP in the coding queue: its B pictures)
+        f.last_minigop_b = is_b && behind.empty();
         h->rc.vbv_picture(&pl.e.planned, h->minigop_b, f.last_minigop_b, au_overhead_bits(h, pl));
     }
     pic.qp = h->rc.start(pl.type, pl.e.frame, pl.e.costs, &near, &f.qpf);
@@ -2187,17 +1618,14 @@ static void bmode_plan(x264_t *h, x264_t::PicPlan &f, x264gpu_encoder *gpu, long
         pic.direct_temporal = !spatial; pic.direct_auto = f.direct_auto_write;
         h->dpb.set_direct(pic.direct_temporal, pic.direct_auto);
     }
-    if (h->st) {
+    if (h->slicetype.analyses()) {
         // x264_mb_predict_mv_ref16x16: the lookahead's vectors towards reference 0 of each list as search candidates, when that search ran
-        // (fenc->lowres_mvs[list][distance - 1], distances up to bframes + 1)
         const int dist0 = pic.nref[0] ? (pic.poc - plan.list_poc[0][0]) / 2 : 0, dist1 = pic.nref[1] ? (plan.list_poc[1][0] - pic.poc) / 2 : 0;
-        const int16_t *m0 = dist0 >= 1 && dist0 <= h->bframes + 1 ? x264gpu_slicetype_lowres_mvs(h->st, pl.e.slot, 0, dist0) : nullptr;
-        const int16_t *m1 = dist1 >= 1 && dist1 <= h->bframes + 1 ? x264gpu_slicetype_lowres_mvs(h->st, pl.e.slot, 1, dist1) : nullptr;
-        x264gpu_encoder_set_lowres_mvs(gpu, m0);
-        x264gpu_encoder_set_lowres_mvs1(gpu, m1);
+        x264gpu_encoder_set_lowres_mvs(gpu, h->slicetype.lowres_mvs(pl.e.slot, 0, dist0));
+        x264gpu_encoder_set_lowres_mvs1(gpu, h->slicetype.lowres_mvs(pl.e.slot, 1, dist1));
     }
     f.d_offsets = nullptr;
-    if (h->st && h->mbtree)          // P / I / B-reference pictures: what the tree left (AQ - tree); other B pictures: the AQ offsets alone (x264 f_qp_offset_aq)
+    if (h->slicetype.analyses() && h->mbtree)          // P / I / B-reference pictures: what the tree left (AQ - tree); other B pictures: the AQ offsets alone (x264 f_qp_offset_aq)
         f.d_offsets = pl.type == PIC_B ? h->q_aq[(size_t)pl.e.slot] : h->q_tree[(size_t)pl.e.slot];
     else if (h->aq_mode >= 2 && h->aq_strength != 0.f) f.d_offsets = h->q_aq[(size_t)pl.e.slot];      // --aq-mode 2 / 3: the offsets computed when the picture arrived
     // (the serial path names a buffer only when there is one; a launch context is always told, "none" included)
@@ -2214,7 +1642,7 @@ static void bmode_plan(x264_t *h, x264_t::PicPlan &f, x264gpu_encoder *gpu, long
 // picture).  idr_pic_id is read here — when the picture is handed to the slice writer, which for a picture in flight is when it retires, not when it was planned
 static bool bmode_open_au(x264_t *h, x264_t::PicPlan &f, std::vector<int> &types)
 {
-    const x264_t::BPlanned &pl = f.pl;
+    const SliceType::Pic &pl = f.pl;
     h->last_direct_char = f.direct_char;
     h->last_scenecut = pl.e.scenecut; h->last_qp = f.pic.qp; h->last_qpm = f.pic.qpm;
     memcpy(h->last_costs, pl.e.costs, sizeof(pl.e.costs));
@@ -2251,7 +1679,7 @@ static bool bmode_write_au(x264_t *h, x264_t::PicPlan &f, std::vector<int> &type
 static int bmode_finish_written(x264_t *h, x264_t::PicPlan &f, std::vector<int> &types, bool sets, const x264gpu_mb *mbs, x264_nal_t **pp_nal, int *pi_nal, x264_picture_t *pic_out)
 {
     const x264_param_t &p = h->param;
-    const x264_t::BPlanned &pl = f.pl;
+    const SliceType::Pic &pl = f.pl;
     const bool idr = pl.type == PIC_IDR;
     if (sets) h->sei_sent = 1;
     // x264_ratecontrol_end; a session that writes statistics or follows a plan is told what the picture's macroblocks were
@@ -2310,7 +1738,7 @@ static int publish_deferred(x264_t *h, x264_t::Deferred &d, x264_nal_t **pp_nal,
 static int bmode_defer(x264_t *h, x264_t::PicPlan &f, int bbuf, x264_nal_t **pp_nal, int *pi_nal, x264_picture_t *pic_out)
 {
     const x264_param_t &p = h->param;
-    const x264_t::BPlanned &pl = f.pl;
+    const SliceType::Pic &pl = f.pl;
     const bool idr = pl.type == PIC_IDR;
     std::vector<int> types;
     if (bmode_open_au(h, f, types)) h->sei_sent = 1;
@@ -2361,7 +1789,8 @@ static int encode_bmode(x264_t *h, x264_nal_t **pp_nal, int *pi_nal, x264_pictur
     auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     double tb0 = now(), tb1 = 0;
     auto BPHASE = [&](int i) { tb1 = now(); h->t_b[i] += tb1 - tb0; tb0 = tb1; };
-    const bool decided = bmode_decide(h, flushing);
+    const bool decided = h->slicetype.decide(flushing, h->rc);
+    h->failed |= h->slicetype.failed;
     BPHASE(0);
     if (!decided) return flushing ? publish_deferred(h, h->defer[h->defer_cur ^ 1].valid ? h->defer[h->defer_cur ^ 1] : h->defer[h->defer_cur], pp_nal, pi_nal, pic_out) : 0;
     x264_t::PicPlan f;
@@ -2446,8 +1875,7 @@ static bool inflight_issue(x264_t *h, bool flushing)
     int ci = -1;
     for (int i = 0; i < (int)h->lctx.size(); i++) if (!h->lctx[(size_t)i].busy) { ci = i; break; }
     if (ci < 0) return false;
-    if (h->bcoding.empty() && !bmode_decide(h, flushing)) return false;
-    if (h->failed) return false;
+    if (!h->slicetype.decide(flushing, h->rc)) { h->failed |= h->slicetype.failed; return false; }
     // the slots the pictures in flight write or read stay out of the choice of a destination
     unsigned avoid = 0;
     for (const x264_t::PicPlan &q : h->fl) avoid |= q.slots_used;
@@ -2509,7 +1937,7 @@ static int encode_bmode_inflight(x264_t *h, x264_nal_t **pp_nal, int *pi_nal, x2
     // ... and hand back the oldest picture once `inflight` pictures are out (x264's frame threads: i_thread_frames - 1 more calls of delay), when a decided picture
     // waits for a context or a slot, or when the input has ended; else this call returns nothing (a delayed frame).  The pictures behind the oldest keep running:
     // in the steady state a call issues one picture and waits for one that was issued inflight - 1 calls ago.
-    if (!(flushing || (int)h->fl.size() >= h->inflight || !h->bcoding.empty())) return 0;
+    if (!(flushing || (int)h->fl.size() >= h->inflight || !h->slicetype.queue().empty())) return 0;
     return inflight_retire(h, pp_nal, pi_nal, pic_out);
 }
 
@@ -2558,7 +1986,7 @@ int x264_encoder_encode(x264_t *h, x264_nal_t **pp_nal, int *pi_nal, x264_pictur
     bool idr = h->la_count == 0 || h->la_gop >= h->keyint || pic_in->i_type == X264_TYPE_IDR || pic_in->i_type == X264_TYPE_KEYFRAME, intra_pic = false;
     if (h->la) {
         if (x264gpu_lookahead_frame_cost(h->la, d_raw, h->la_count == 0, h->d_la, h->mbtree ? h->q_info[(size_t)slot] : nullptr, nullptr) != X264GPU_OK ||
-            ((h->mbtree || h->st_aq_costs || h->aq_mode >= 2) && h->aq_strength != 0.f && x264gpu_lookahead_aq_offsets_mode(h->la, d_raw, h->aq_mode >= 2 ? h->aq_mode : 1, h->aq_strength, h->q_aq[(size_t)slot], nullptr) != X264GPU_OK) ||
+            ((h->mbtree || h->slicetype.aq_costs || h->aq_mode >= 2) && h->aq_strength != 0.f && x264gpu_lookahead_aq_offsets_mode(h->la, d_raw, h->aq_mode >= 2 ? h->aq_mode : 1, h->aq_strength, h->q_aq[(size_t)slot], nullptr) != X264GPU_OK) ||
             x264gpu_memcpy_d2h(e.costs, h->d_la, sizeof(e.costs), nullptr) != X264GPU_OK) {
             xlog(&p, X264_LOG_ERROR, "x264_encoder_encode: lookahead failed: %s\n", x264gpu_last_error());
             return -1;
@@ -2580,29 +2008,14 @@ int x264_encoder_encode(x264_t *h, x264_nal_t **pp_nal, int *pi_nal, x264_pictur
     h->la_gop = idr ? 1 : h->la_gop + 1;
     h->la_count++;
     if (h->dpbmode) {
-        x264_t::BEntry be = {};
+        SliceType::Frame be = {};
         be.pts = e.pts; be.frame = (int)(h->la_count - 1); be.slot = slot; be.forced = e.type; be.scenecut = e.scenecut; be.img = e.img;
         memcpy(be.costs, e.costs, sizeof(e.costs));
         if (pic_in->i_type == X264_TYPE_I) be.forced = 1;
-        if (h->st) {
-            // the slice-type analysis decides keyframes and scene cuts itself: only what the caller forced stays forced
-            be.forced = pic_in->i_type == X264_TYPE_IDR || pic_in->i_type == X264_TYPE_KEYFRAME ? 2 : pic_in->i_type == X264_TYPE_I ? 1 : 0;
-            be.scenecut = 0;
-            bool ok = x264gpu_slicetype_put_frame(h->st, slot, d_raw, nullptr) == X264GPU_OK;
-            if (ok && h->weightp) { uint64_t stats[2]; ok = x264gpu_slicetype_pixel_stats(h->st, slot, d_raw, stats, nullptr) == X264GPU_OK; }      // x264_adaptive_quant_frame: i_pixel_sum / i_pixel_ssd
-            if (ok && h->mbtree) {
-                // x264_adaptive_quant_frame: the AQ offsets weight the lookahead's costs and are what the tree starts from (f_qp_offset = f_qp_offset_aq)
-                if (h->aq_strength == 0.f) ok = x264gpu_memset(h->q_aq[(size_t)slot], 0, (size_t)h->nmb * sizeof(float), nullptr) == X264GPU_OK;
-                ok = ok && x264gpu_slicetype_set_aq(h->st, slot, h->aq_strength != 0.f ? h->q_aq[(size_t)slot] : nullptr, nullptr) == X264GPU_OK &&
-                     x264gpu_memcpy_d2d(h->q_tree[(size_t)slot], h->q_aq[(size_t)slot], (size_t)h->nmb * sizeof(float), nullptr) == X264GPU_OK;
-            }
-            if (ok && h->st_aq_costs) ok = x264gpu_slicetype_set_aq(h->st, slot, h->q_aq[(size_t)slot], nullptr) == X264GPU_OK;      // i_inv_qscale_factor for i_cost_est_aq
-            if (!ok) {
-                xlog(&p, X264_LOG_ERROR, "x264_encoder_encode: lookahead failed: %s\n", x264gpu_last_error());
-                return -1;
-            }
+        if (!h->slicetype.put(be, d_raw, pic_in->i_type == X264_TYPE_IDR || pic_in->i_type == X264_TYPE_KEYFRAME ? 2 : pic_in->i_type == X264_TYPE_I ? 1 : 0)) {
+            xlog(&p, X264_LOG_ERROR, "x264_encoder_encode: lookahead failed: %s\n", x264gpu_last_error());
+            return -1;
         }
-        h->bq.push_back(be);
         h->all_pts.push_back(e.pts);
         PHASE(1);
         const int size = h->inflight > 1 ? encode_bmode_inflight(h, pp_nal, pi_nal, pic_out, false) : encode_bmode(h, pp_nal, pi_nal, pic_out, false);
@@ -2620,7 +2033,7 @@ int x264_encoder_encode(x264_t *h, x264_nal_t **pp_nal, int *pi_nal, x264_pictur
     return size;
 }
 
-int x264_encoder_delayed_frames(x264_t *h) { return !h || h->failed ? 0 : h->G > 1 ? (int)(h->submitted - h->emitted) : h->dpbmode ? (int)(h->bq.size() + h->bcoding.size() + h->fl.size()) + (h->defer[0].valid ? 1 : 0) + (h->defer[1].valid ? 1 : 0) : (int)h->queue.size(); }
+int x264_encoder_delayed_frames(x264_t *h) { return !h || h->failed ? 0 : h->G > 1 ? (int)(h->submitted - h->emitted) : h->dpbmode ? h->slicetype.delayed() + (int)h->fl.size() + (h->defer[0].valid ? 1 : 0) + (h->defer[1].valid ? 1 : 0) : (int)h->queue.size(); }
 
 void x264_encoder_close(x264_t *h)
 {
@@ -2662,7 +2075,7 @@ void x264_encoder_close(x264_t *h)
     for (void *blk : h->q_block) if (blk) x264gpu_free(blk);          // the queue's slots (source pictures, lookahead records, AQ and tree offsets) are cuts of these
     if (h->d_tree) x264gpu_free(h->d_tree);
     if (h->la) x264gpu_lookahead_destroy(h->la);
-    if (h->st) x264gpu_slicetype_destroy(h->st);
+    h->slicetype.close();
     if (h->d_la) x264gpu_free(h->d_la);
     delete h;
 }
