@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """N sessions in N threads with X264GPU_BATCH=N (the cross-session batcher of the product's host library over the stand-in device), then the same N
-sessions one after the other without it: prints one JSON line {"equal": [...], "sizes": [...], "types": "..."}.
-Usage: run_host_batch.py N W H FRAMES key=value ...   (X264_HOST_STUB selects the stand-in device; without it the real device is used)"""
+sessions one after the other without it: prints one JSON line {"equal": [...], "sizes": [...], "types": "...", "failed": [...]}.
+Usage: run_host_batch.py N W H FRAMES [lens=a,b,...] [--report] key=value ...   (X264_HOST_STUB selects the stand-in device; without it the real device is used)
+lens: session s submits lens[s] pictures instead of FRAMES (members that leave early).  --report: a session's failure does not end the run, it is named in
+"failed" (None: the session ran) and its "equal" / "sizes" entries are None.  A session whose call fails or hands back nothing closes its encoder before it reports."""
 import ctypes as C
 import json
 import os
@@ -42,27 +44,37 @@ def session(w, h, frames, opts, out, idx, errs):
                 C.memmove(pic.img.plane[pl], f[off:off + sz].ctypes.data, sz)
             pic.i_pts = i
             size = H.x264_encoder_encode(h_, C.byref(nal), C.byref(nn), C.byref(pic), C.byref(po))
-            assert size >= 0, "encode failed"
+            if size < 0:
+                H.x264_encoder_close(h_)
+                raise RuntimeError("encode failed")
             if size:
                 stream += C.string_at(nal[0].p_payload, size); types.append(po.i_type)
         while H.x264_encoder_delayed_frames(h_):
             size = H.x264_encoder_encode(h_, C.byref(nal), C.byref(nn), None, C.byref(po))
-            assert size > 0, "flush failed"
+            if size <= 0:
+                H.x264_encoder_close(h_)
+                raise RuntimeError("flush failed")
             stream += C.string_at(nal[0].p_payload, size); types.append(po.i_type)
         H.x264_encoder_close(h_)
         out[idx] = (stream, types)
     except Exception as e:  # noqa: BLE001
-        errs.append(f"session {idx}: {e!r}")
+        errs[idx] = f"session {idx}: {e!r}"
 
 
 def main():
     n, w, h, nf = (int(x) for x in sys.argv[1:5])
-    opts = {}
+    opts, lens, report = {}, [nf] * n, False
     for a in sys.argv[5:]:
         k, _, v = a.partition("=")
-        opts[k] = v if _ else None
-    clips = [synth_frames(w, h, nf, seed=100 + s) for s in range(n)]
-    batched, solo, errs = [None] * n, [None] * n, []
+        if a == "--report":
+            report = True
+        elif k == "lens":
+            lens = [int(x) for x in v.split(",")]
+            assert len(lens) == n, lens
+        else:
+            opts[k] = v if _ else None
+    clips = [synth_frames(w, h, lens[s], seed=100 + s) for s in range(n)]
+    batched, solo, errs, errs_solo = [None] * n, [None] * n, [None] * n, [None] * n
     os.environ["X264GPU_BATCH"] = str(n)
     ths = [threading.Thread(target=session, args=(w, h, clips[s], opts, batched, s, errs)) for s in range(n)]
     for t in ths:
@@ -70,13 +82,14 @@ def main():
     for t in ths:
         t.join()
     del os.environ["X264GPU_BATCH"]
-    assert not errs, errs
+    assert report or not any(errs), errs
     for s in range(n):
-        session(w, h, clips[s], opts, solo, s, errs)
-    assert not errs, errs
+        session(w, h, clips[s], opts, solo, s, errs_solo)
+    assert not any(errs_solo), errs_solo
     TYPE = {1: "I", 2: "i", 3: "P", 4: "R", 5: "B"}
-    print(json.dumps({"equal": [batched[s][0] == solo[s][0] for s in range(n)], "sizes": [len(b[0]) for b in batched],
-                      "distinct": len({b[0] for b in batched}), "types": "".join(TYPE[t] for t in batched[0][1])}))
+    ran = [b for b in batched if b is not None]
+    print(json.dumps({"equal": [batched[s] and batched[s][0] == solo[s][0] for s in range(n)], "sizes": [b and len(b[0]) for b in batched],
+                      "distinct": len({b[0] for b in ran}), "types": "".join(TYPE[t] for t in ran[0][1]) if ran else "", "failed": errs}))
 
 
 main()

@@ -359,16 +359,17 @@ def test_host_session_mbtree_through_b_pictures(tmp_path):
     assert info0["mbtree"] == 0 and stream0 != stream
 
 
-def _batch(n, w, h, nf, opts, gpu=False, timeout=900, overlap=True):
+def _batch(n, w, h, nf, opts, gpu=False, timeout=900, overlap=True, env=None, lens=None, report=False):
     import json
     import os
     import subprocess
     import sys
     here = os.path.dirname(os.path.abspath(__file__))
-    env = dict(os.environ)
+    env = dict(os.environ, **(env or {}))          # (env: further switches of the batcher, X264GPU_BATCH_ASYNC / _DENSE)
     env.pop("X264GPU_BATCH", None)
     env["X264GPU_BATCH_OVERLAP"] = "1" if overlap else "0"          # the host's entropy coding beside the device's next round (one picture of delay), or inside the call
-    r = subprocess.run([sys.executable, os.path.join(here, "stub", "run_host_batch.py"), str(n), str(w), str(h), str(nf)] + opts + (["--gpu"] if gpu else []),
+    more = (["lens=" + ",".join(str(x) for x in lens)] if lens else []) + (["--report"] if report else [])
+    r = subprocess.run([sys.executable, os.path.join(here, "stub", "run_host_batch.py"), str(n), str(w), str(h), str(nf)] + more + opts + (["--gpu"] if gpu else []),
                        capture_output=True, text=True, timeout=timeout, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     return json.loads(r.stdout.strip().splitlines()[-1])
@@ -386,6 +387,43 @@ def test_cross_session_batcher_is_byte_identical(n, opts):
     assert r["equal"] == [True] * n and r["distinct"] == n, r
     r0 = _batch(n, 176, 144, 11, opts, overlap=False)          # ... with download and entropy coding inside the call: the same streams
     assert r0["equal"] == [True] * n and r0["sizes"] == r["sizes"], (r0, r)
+
+
+BATCH_IP = ["qp=26", "keyint=30", "scenecut=0", "bframes=0", "weightp=2"]
+# the batcher's switches: rounds queued behind one another and entropy coding beside the next round; entropy coding inside the call; rounds awaited
+BATCH_SWITCHES = [dict(), dict(overlap=False), dict(env={"X264GPU_BATCH_ASYNC": "0"})]
+
+
+@pytest.mark.parametrize("switches", BATCH_SWITCHES, ids=["default", "overlap0", "async0"])
+@pytest.mark.parametrize("lens", [(11, 6, 9), (4, 11, 1)])
+def test_batch_members_that_leave_early(lens, switches):
+    """sessions of different lengths in one group: a member that closes leaves its seat empty (its stream is coded along from a copied picture and thrown away), the
+    round the others were only waiting for it to join is run by the leaver; every session's stream still equals the one it writes alone"""
+    r = _batch(3, 176, 144, 11, BATCH_IP, lens=list(lens), **switches)
+    assert r["equal"] == [True] * 3 and r["distinct"] == 3 and r["failed"] == [None] * 3, r
+
+
+BATCH_B = ["qp=23", "keyint=30", "scenecut=0", "b-adapt=0", "bframes=3"]
+_batch_b_default = []          # the default run of BATCH_B with three sessions, made once
+
+
+@pytest.mark.parametrize("env", [{"X264GPU_BATCH_ASYNC": "0"}, {"X264GPU_BATCH_DENSE": "1"}], ids=["async0", "dense"])
+def test_batch_awaited_rounds_and_dense_levels(env):
+    """X264GPU_BATCH_ASYNC=0 (the callers wait for every round) and X264GPU_BATCH_DENSE=1 (the levels are downloaded whole, not packed): the default run's bytes"""
+    if not _batch_b_default:
+        _batch_b_default.append(_batch(3, 176, 144, 11, BATCH_B))
+    r = _batch_b_default[0]
+    assert r["equal"] == [True] * 3 and r["distinct"] == 3, r
+    r1 = _batch(3, 176, 144, 11, BATCH_B, env=env)
+    assert r1["equal"] == [True] * 3 and r1["sizes"] == r["sizes"] and r1["types"] == r["types"], (env, r1, r)
+
+
+@pytest.mark.parametrize("switches", BATCH_SWITCHES, ids=["default", "overlap0", "async0"])
+def test_batch_refused_round_ends(switches):
+    """sessions whose picture structures part (the short session's flush closes its last mini-GOP differently): the group refuses the round, every session gets a
+    negative or empty result and closes, nothing waits for a round that will not come (the time-out only caps a hang)"""
+    r = _batch(3, 176, 144, 11, ["qp=26", "keyint=30", "scenecut=0", "bframes=3", "b-adapt=0"], lens=[11, 6, 9], report=True, timeout=120, **switches)
+    assert all(r["failed"]) and r["equal"] == [None] * 3 and r["sizes"] == [None] * 3, r
 
 
 def fade_frames(w, h, n, seed, step=6):

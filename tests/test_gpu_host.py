@@ -1040,6 +1040,14 @@ def test_cross_session_batcher_with_crf_on_the_device(gpu):
     assert r["equal"] == [True] * 6 and r["distinct"] == 6, r
 
 
+def test_batch_members_that_leave_early_on_the_device(gpu):
+    """four sessions of 9 / 4 / 7 / 1 pictures in one group: the seats of the members that closed are coded along and thrown away, the rounds the others were only
+    waiting for a leaver to join are run by the leaver; every session's stream equals the one it writes alone"""
+    from test_bframes_cpu import BATCH_IP, _batch
+    r = _batch(4, 176, 144, 9, BATCH_IP, gpu=True, lens=[9, 4, 7, 1])
+    assert r["equal"] == [True] * 4 and r["distinct"] == 4 and r["failed"] == [None] * 4, r
+
+
 def test_fade_session_gets_luma_weights_on_the_device(gpu):
     """a fade through x264_encoder_encode with medium's lookahead on the device: x264_weights_analyse's restatement (host) on the device's
     statistics and weight costs gives the P pictures luma weights; the stream is smaller than with --weightp 0 and decodes to the source"""

@@ -7,6 +7,7 @@
 // pic_out->{i_type,b_keyframe,i_pts,i_dts} filled.  No CPU fallback: open fails without a GPU.
 #include "host.hpp"
 #include "dpb.hpp"
+#include "batch.hpp"
 #include "quality.hpp"
 #include "ratecontrol.hpp"
 #include "slicetype.hpp"
@@ -147,9 +148,8 @@ struct x264_t {
     std::vector<float *> q_tree;         // device, per queue slot: the quantiser offsets the macroblock-tree left with the picture (AQ offsets until it ran)
     // cross-session batcher (X264GPU_BATCH=N): N sessions of equal geometry and toolset share ONE device encoder with N streams; the pictures
     // they submit are coded in one lock-step launch, every session entropy-codes its own stream on its caller's thread
-    struct BatchGroup *batch = nullptr; int batch_idx = -1, batch_n = 0;
-    void *up_stream = nullptr;           // a batch session's upload stream (one of the group's, async groups): its pictures go up while the group's round runs on the compute stream
-    // batch sessions with overlap (BatchGroup::overlap): the picture just submitted is downloaded and entropy-coded by a helper thread while the group's next round runs;
+    Batch batch;                         // host/batch.hpp: the session's seat in its group
+    // batch sessions with overlap (Batch::overlap): the picture just submitted is downloaded and entropy-coded by a helper thread while the group's next round runs;
     // its NAL units leave with the NEXT call (one picture of delay).  Two slots used in turn: the one being filled, the one waiting to be handed out
     struct Deferred { std::thread th; bool valid = false; std::atomic<bool> hurry{ false }; std::string err; std::vector<uint8_t> out; std::vector<size_t> off; std::vector<int> types; int nal_ref_idc = 0;
                       std::vector<x264gpu_mb> mb; std::vector<x264gpu_level_index> ix; std::unique_ptr<int16_t[]> lv; SliceStats stats = { 0 };      // (lv: never cleared — what is downloaded is what is read)
@@ -175,264 +175,6 @@ struct x264_t {
     int direct_mode = 1, direct_score[2] = { 0, 0 }, slot_l0ref0poc[8] = { 0 };
     char last_direct_char = '-';
 };
-
-// ---- cross-session batcher ------------------------------------------------------------------------------------------------------
-// The reference opens one CODEC / x264_t per stream (driverproc.c:110-128); the device is fast only when many streams are coded in lock-step
-// (x264gpu_config.streams).  With X264GPU_BATCH=N in the environment, the first N sessions opened with the same geometry and toolset (and
-// a fixed picture structure: no scenecut / b-adapt / mbtree, so that picture k has the same type in all of them) form a group around one
-// device encoder with N streams.  A session's x264_encoder_encode hands its picture to the group and waits; the call that completes the
-// round launches the hot path for all streams; every caller then downloads its own records and entropy-codes its own stream on its own
-// thread.  Each stream is coded exactly as a session of its own would code it (streams never interact): the bytes are the same.
-struct BatchGroup {
-    std::mutex m; std::condition_variable cv;
-    x264gpu_config cfg; int N = 0, device = 0;
-    x264gpu_encoder *gpu = nullptr; uint8_t *d_in = nullptr; x264gpu_mb *d_mb = nullptr; int16_t *d_lv = nullptr;
-    // overlap: the records / levels of round k are downloaded and entropy-coded (by a helper thread of every session) WHILE round k + 1 runs: a second pair of
-    // output buffers used in turn, a stream of the group's own for the downloads; every session hands its pictures back one call later
-    bool overlap = false; x264gpu_mb *d_mb2 = nullptr; int16_t *d_lv2 = nullptr; void *dl_stream = nullptr;
-    // ... and (async) the callers do not wait for the round either: it is QUEUED on the group's own compute stream behind the round before, an event behind it tells the
-    // download of its results when it is done; the callers go on to copy in and upload their next pictures (on upload streams of their own) while the device works
-    bool async = false; void *cs = nullptr, *ev[2] = { nullptr, nullptr };
-    // the levels leave the device packed (x264gpu_pack_levels behind every round, in place): a member downloads its records, its index and the part of its levels that is kept
-    // (~10 % at medium; dense, 2048 members x 7 MB a round were what the first rounds waited for: fresh pages of the download buffers, 15 GB a round over the link)
-    bool pack = false; x264gpu_level_index *d_ix = nullptr, *d_ix2 = nullptr;
-    int qflags = 0; x264gpu_quality *d_q = nullptr, *d_q2 = nullptr;          // --psnr / --ssim of the members (all alike): one statistic per stream behind every round, two buffers as d_mb / d_mb2
-    std::vector<void *> up_streams;          // the members' uploads: a handful of streams dealt round-robin (a stream per member was 0.7 ms to create and 0.6 ms to destroy, x 2048, serialised in the runtime)
-    long ev_round[2] = { 0, 0 }, ev_done[2] = { 0, 0 }; bool ev_waiting[2] = { false, false }; std::string ev_err;      // per buffer pair: the round recorded behind it (1-based), the last one known complete, a member is waiting for the event
-    long launched = 0;            // rounds whose kernels have been issued: the helper threads start entropy coding round k once round k + 1 is on the device (or when asked to hurry),
-                                  // so that the host cores are the callers' while the next pictures are uploaded and submitted
-    bool running = false;         // a round is being waited for with the group's lock released (overlap): nobody starts another
-    int leaving = 0; bool orphaned = false;      // batch_leave: leavers between "decided to run the round" and "ran it"; the last member left meanwhile (the leaver destroys the group)
-    size_t insz = 0, nmb = 0;
-    std::vector<char> member, arrived; int joined = 0, active = 0, n_arrived = 0;
-    std::vector<x264gpu_pic> pics; long round = 0; int round_rc = 0; std::string err;
-    bool closed = false;          // a member left: no more joiners (batch_leave)
-    // X264GPU_BATCH_TIMING=1: where the members' threads spent their time, summed over members (printed when the group goes): waiting for a round's event,
-    // downloading records / levels, waiting for the next round's launch before the slices are written, writing them, waiting in batch_submit for the round to fill
-    std::atomic<long> t_us[6] = {};
-    std::atomic<long> r_dl[64] = {}, r_sl[64] = {}, r_dl_first[64] = {}, r_dl_last[64] = {};          // per round: download / slice seconds summed over the members; when the first / last download ended
-    std::vector<long> tl_launch, tl_done, tl_host;          // ... and per round: issued, its event seen, its results on the host (microseconds; the first launch = 0)
-    bool timing = getenv("X264GPU_BATCH_TIMING") != nullptr;
-};
-static inline long us_now() { return (long)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-static std::mutex g_batch_mu;
-static std::vector<BatchGroup *> g_batch_groups;
-
-static void batch_destroy(BatchGroup *g)
-{
-    const long t_destroy0 = g->timing ? us_now() : 0;
-    struct Tm { BatchGroup *g; long t0; bool on; ~Tm() { if (on) fprintf(stderr, "x264gpu batch: the group's device memory and streams took %.2f s to release\n", (us_now() - t0) / 1e6); } } tm{ g, t_destroy0, g->timing };
-    if (g->timing)
-        fprintf(stderr, "x264gpu batch timing, seconds summed over %d members: event wait %.1f, download %.1f, wait for the next launch %.1f, slices %.1f, submit wait %.1f, join of the helper %.1f\n", g->N,
-                g->t_us[0] / 1e6, g->t_us[1] / 1e6, g->t_us[2] / 1e6, g->t_us[3] / 1e6, g->t_us[4] / 1e6, g->t_us[5] / 1e6);
-    if (g->timing && !g->tl_launch.empty()) {
-        fprintf(stderr, "x264gpu batch rounds (s from the first launch): issued / event seen / results on the host:");
-        for (size_t i = 0; i < g->tl_launch.size(); i++)
-            fprintf(stderr, "  %zu: %.2f / %.2f / %.2f", i, (g->tl_launch[i] - g->tl_launch[0]) / 1e6, i < g->tl_done.size() ? (g->tl_done[i] - g->tl_launch[0]) / 1e6 : -1., i < g->tl_host.size() ? (g->tl_host[i] - g->tl_launch[0]) / 1e6 : -1.);
-        fprintf(stderr, "\n");
-        fprintf(stderr, "x264gpu batch rounds: download s per member / slices s per member / first .. last download done (s from the first launch):");
-        for (size_t i = 0; i < g->tl_launch.size() && i < 64; i++)
-            fprintf(stderr, "  %zu: %.2f / %.2f / %.2f .. %.2f", i, g->r_dl[i] / 1e6 / g->N, g->r_sl[i] / 1e6 / g->N, (g->r_dl_first[i] - g->tl_launch[0]) / 1e6, (g->r_dl_last[i] - g->tl_launch[0]) / 1e6);
-        fprintf(stderr, "\n");
-    }
-    if (g->gpu) x264gpu_encoder_destroy(g->gpu);
-    if (g->d_in) x264gpu_free(g->d_in);
-    if (g->d_mb) x264gpu_free(g->d_mb);
-    if (g->d_lv) x264gpu_free(g->d_lv);
-    if (g->d_mb2) x264gpu_free(g->d_mb2);
-    if (g->d_lv2) x264gpu_free(g->d_lv2);
-    if (g->d_ix) x264gpu_free(g->d_ix);
-    if (g->d_ix2) x264gpu_free(g->d_ix2);
-    if (g->d_q) x264gpu_free(g->d_q);
-    if (g->d_q2) x264gpu_free(g->d_q2);
-    if (g->cs) x264gpu_stream_sync(g->cs);
-    if (g->dl_stream) x264gpu_stream_destroy(g->dl_stream);
-    for (void *st : g->up_streams) { x264gpu_stream_sync(st); x264gpu_stream_destroy(st); }
-    for (int i = 0; i < 2; i++) if (g->ev[i]) x264gpu_event_destroy(g->ev[i]);
-    if (g->cs) x264gpu_stream_destroy(g->cs);
-    delete g;
-}
-// -> the group and the stream index of the caller, or nullptr (setup failed: last error set)
-static BatchGroup *batch_join(const x264gpu_config &cfg1, int N, size_t insz, size_t nmb, int qflags, int *idx)
-{
-    std::lock_guard<std::mutex> lk(g_batch_mu);
-    int dev = 0;
-    (void)x264gpu_get_device(&dev);
-    for (BatchGroup *g : g_batch_groups) {
-        x264gpu_config a = g->cfg, b = cfg1;
-        a.streams = b.streams = 0;
-        if (g->N == N && g->device == dev && g->joined < N && !g->closed && g->qflags == qflags && !memcmp(&a, &b, sizeof(a))) {
-            std::lock_guard<std::mutex> lg(g->m);
-            *idx = g->joined++; g->active++; g->member[(size_t)*idx] = 1;
-            g->cv.notify_all();
-            return g;
-        }
-    }
-    BatchGroup *g = new BatchGroup();
-    g->cfg = cfg1; g->cfg.streams = N; g->N = N; g->device = dev; g->insz = insz; g->nmb = nmb; g->qflags = qflags;
-    g->member.assign((size_t)N, 0); g->arrived.assign((size_t)N, 0); g->pics.resize((size_t)N);
-    if (x264gpu_encoder_create(&g->gpu, &g->cfg) != X264GPU_OK ||
-        x264gpu_malloc((void **)&g->d_in, (size_t)N * insz) != X264GPU_OK ||
-        x264gpu_malloc((void **)&g->d_mb, (size_t)N * nmb * sizeof(x264gpu_mb)) != X264GPU_OK ||
-        x264gpu_malloc((void **)&g->d_lv, (size_t)N * nmb * X264GPU_MB_LEVELS * sizeof(int16_t)) != X264GPU_OK ||
-        (qflags && (x264gpu_malloc((void **)&g->d_q, (size_t)N * sizeof(x264gpu_quality)) != X264GPU_OK || x264gpu_malloc((void **)&g->d_q2, (size_t)N * sizeof(x264gpu_quality)) != X264GPU_OK))) { batch_destroy(g); return nullptr; }
-    {
-        const char *oe = getenv("X264GPU_BATCH_OVERLAP");
-        if (!(oe && oe[0] == '0') && !getenv("X264GPU_DUMP_RECORDS") &&
-            x264gpu_malloc((void **)&g->d_mb2, (size_t)N * nmb * sizeof(x264gpu_mb)) == X264GPU_OK &&
-            x264gpu_malloc((void **)&g->d_lv2, (size_t)N * nmb * X264GPU_MB_LEVELS * sizeof(int16_t)) == X264GPU_OK && x264gpu_stream_create(&g->dl_stream) == X264GPU_OK) g->overlap = true;
-        const char *ae = getenv("X264GPU_BATCH_ASYNC");
-        if (g->overlap && !(ae && ae[0] == '0') && x264gpu_stream_create(&g->cs) == X264GPU_OK && x264gpu_event_create(&g->ev[0]) == X264GPU_OK && x264gpu_event_create(&g->ev[1]) == X264GPU_OK) g->async = true;
-        if (g->async && !getenv("X264GPU_BATCH_DENSE") && x264gpu_malloc((void **)&g->d_ix, (size_t)N * nmb * sizeof(x264gpu_level_index)) == X264GPU_OK &&
-            x264gpu_malloc((void **)&g->d_ix2, (size_t)N * nmb * sizeof(x264gpu_level_index)) == X264GPU_OK) g->pack = true;
-        if (g->async) for (int i = 0; i < 16 && i < N; i++) { void *st = nullptr; if (x264gpu_stream_create(&st) == X264GPU_OK) g->up_streams.push_back(st); else break; }
-    }
-    g->joined = 1; g->active = 1; g->member[0] = 1; *idx = 0;
-    g_batch_groups.push_back(g);
-    return g;
-}
-// the launch of a complete round; g->m is held through lk (released while an overlapping group waits for its kernels)
-static void batch_run_round(BatchGroup *g, std::unique_lock<std::mutex> &lk)
-{
-    int first = -1;
-    for (int s = 0; s < g->N; s++) if (g->arrived[(size_t)s]) { first = s; break; }
-    g->round_rc = 0; g->err.clear();
-    if (first >= 0) {
-        for (int s = 0; s < g->N; s++) {
-            if (!g->arrived[(size_t)s]) { g->pics[(size_t)s] = g->pics[(size_t)first]; continue; }      // a stream whose session has gone: coded along, thrown away
-            const x264gpu_pic &a = g->pics[(size_t)s], &b = g->pics[(size_t)first];
-            if (a.slice_type != b.slice_type || a.poc != b.poc || a.dst != b.dst || a.keep != b.keep || a.nref[0] != b.nref[0] || a.nref[1] != b.nref[1] ||
-                memcmp(a.slot, b.slot, sizeof(a.slot)) || a.blind_dupe != b.blind_dupe) { g->round_rc = -1; g->err = "the sessions of a batch must submit pictures of the same structure (same picture count, keyint, bframes, forced types)"; }
-        }
-        const bool second = g->overlap && (g->round & 1);          // the output buffers of this round (the other pair may still be downloading)
-        if (!g->round_rc && x264gpu_encode_pictures(g->gpu, g->d_in, g->pics.data(), second ? g->d_mb2 : g->d_mb, second ? g->d_lv2 : g->d_lv, g->async ? g->cs : nullptr) != X264GPU_OK) { g->round_rc = -1; g->err = x264gpu_last_error(); }
-        if (!g->round_rc && g->qflags && quality_queue(g->gpu, g->qflags, second ? g->d_q2 : g->d_q, g->async ? g->cs : nullptr) != X264GPU_OK) { g->round_rc = -1; g->err = x264gpu_last_error(); }
-        if (!g->round_rc && g->pack && x264gpu_pack_levels(second ? g->d_lv2 : g->d_lv, g->N, (int)g->nmb, second ? g->d_ix2 : g->d_ix, nullptr, g->cs) != X264GPU_OK) { g->round_rc = -1; g->err = x264gpu_last_error(); }
-        if (!g->round_rc && g->async) {
-            // queued, not awaited: the event behind the round is what its downloads wait for (batch_download)
-            if (x264gpu_event_record(g->ev[second ? 1 : 0], g->cs) != X264GPU_OK) { g->round_rc = -1; g->err = x264gpu_last_error(); }
-            g->launched++;
-            if (g->timing) g->tl_launch.push_back(us_now());
-            g->ev_round[second ? 1 : 0] = g->round + 1;
-        } else
-        // overlap: the downloads run on the group's own stream, which does not wait for the default one: the round must be complete before anyone is told
-        if (!g->round_rc && g->overlap) {
-            g->launched++; g->running = true;
-            g->cv.notify_all();          // the helper threads of the round before: the device is busy again, the host cores are theirs
-            lk.unlock();
-            const bool ok = x264gpu_stream_sync(nullptr) == X264GPU_OK;
-            std::string e = ok ? std::string() : std::string(x264gpu_last_error());
-            lk.lock();
-            g->running = false;
-            if (!ok) { g->round_rc = -1; g->err = e; }
-        }
-    }
-    g->round++; g->n_arrived = 0;
-    std::fill(g->arrived.begin(), g->arrived.end(), 0);
-    g->cv.notify_all();
-}
-// hands picture `pic` of stream s to the group and waits for the round that codes it; *buf = which pair of output buffers holds the round's results
-static int batch_submit(BatchGroup *g, int s, const uint8_t *d_src, const x264gpu_pic &pic, int *buf, std::string &err)
-{
-    // (async: on the group's compute stream, i.e. behind the round before — which may still be reading d_in — and in front of this round's launch)
-    if (x264gpu_memcpy_d2d(g->d_in + (size_t)s * g->insz, d_src, g->insz, g->async ? g->cs : nullptr) != X264GPU_OK) { err = x264gpu_last_error(); return -1; }
-    std::unique_lock<std::mutex> lk(g->m);
-    // every member must have been opened before the first picture is coded: a late joiner would be a picture behind for good
-    if (!g->cv.wait_for(lk, std::chrono::seconds(60), [&] { return g->joined == g->N; })) { err = "X264GPU_BATCH: fewer sessions were opened than the batch size"; return -1; }
-    g->pics[(size_t)s] = pic; g->arrived[(size_t)s] = 1; g->n_arrived++;
-    const long my_round = g->round;
-    *buf = g->overlap ? (int)(my_round & 1) : 0;
-    const long t0 = g->timing ? us_now() : 0;
-    struct Acc { BatchGroup *g; long t0; ~Acc() { if (g->timing) g->t_us[4] += us_now() - t0; } } acc{ g, t0 };
-    if (g->n_arrived >= g->active && !g->running) batch_run_round(g, lk);
-    else if (!g->cv.wait_for(lk, std::chrono::seconds(600), [&] { return g->round != my_round; })) {
-        // a member neither submitted its picture nor closed: give up on this session (the others keep waiting for it, or for its close)
-        g->arrived[(size_t)s] = 0; g->n_arrived--;
-        err = "X264GPU_BATCH: another session of the batch stopped submitting pictures";
-        return -1;
-    }
-    if (g->round_rc) { err = g->err; return -1; }
-    return 0;
-}
-// stream s' records and levels of the round whose results lie in buffer pair `buf`
-// (h_ix: the group packs its levels — the member's index; h_lv then receives only the kept groups)
-static int batch_download(BatchGroup *g, int s, int buf, x264gpu_mb *h_mb, int16_t *h_lv, std::string &err, x264gpu_level_index *h_ix = nullptr, x264gpu_quality *h_q = nullptr)
-{
-    const x264gpu_mb *dm = buf ? g->d_mb2 : g->d_mb; const int16_t *dl = buf ? g->d_lv2 : g->d_lv;
-    // (async groups: the members' downloads are dealt to the group's sixteen upload / download streams)
-    void *st = g->overlap ? (g->up_streams.empty() ? g->dl_stream : g->up_streams[(size_t)s % g->up_streams.size()]) : nullptr;
-    const long t0 = g->timing ? us_now() : 0;
-    if (g->async) {
-        // ONE thread waits for the round's event, the other members sleep on the group's condition variable (2048 helper threads in hipEventSynchronize would
-        // take the host's cores from the callers that are copying in and uploading the next pictures)
-        std::unique_lock<std::mutex> lk(g->m);
-        const long want = g->ev_round[buf ? 1 : 0];          // the round recorded behind this buffer pair (it cannot be re-recorded before every member has this round's results)
-        while (g->ev_done[buf ? 1 : 0] < want) {
-            if (!g->ev_waiting[buf ? 1 : 0]) {
-                g->ev_waiting[buf ? 1 : 0] = true;
-                lk.unlock();
-                const bool ok = x264gpu_event_sync(g->ev[buf ? 1 : 0]) == X264GPU_OK;
-                const long t_ev = g->timing ? us_now() : 0;
-                const std::string e = ok ? std::string() : std::string(x264gpu_last_error());
-                lk.lock();
-                if (g->timing) { g->tl_done.push_back(t_ev); g->tl_host.push_back(us_now()); }
-                g->ev_waiting[buf ? 1 : 0] = false;
-                if (!ok) { g->ev_err = e; g->ev_done[buf ? 1 : 0] = want; g->cv.notify_all(); err = e; return -1; }
-                g->ev_done[buf ? 1 : 0] = want;
-                g->cv.notify_all();
-            } else g->cv.wait(lk);
-        }
-        if (!g->ev_err.empty()) { err = g->ev_err; return -1; }
-    }
-    const long t1 = g->timing ? us_now() : 0;
-    const long rnd = g->async ? g->ev_round[buf ? 1 : 0] - 1 : 0;
-    struct Acc { BatchGroup *g; long t0, t1, rnd; ~Acc() { if (g->timing) { const long t2 = us_now(); g->t_us[0] += t1 - t0; g->t_us[1] += t2 - t1;
-        if (rnd >= 0 && rnd < 64) { g->r_dl[rnd] += t2 - t1; long f = g->r_dl_first[rnd].load(); while ((f == 0 || t2 < f) && !g->r_dl_first[rnd].compare_exchange_weak(f, t2)) {} long l = g->r_dl_last[rnd].load(); while (t2 > l && !g->r_dl_last[rnd].compare_exchange_weak(l, t2)) {} } } } } acc{ g, t0, t1, rnd };
-    if (g->qflags && h_q && x264gpu_memcpy_d2h(h_q, (buf ? g->d_q2 : g->d_q) + s, sizeof(x264gpu_quality), st) != X264GPU_OK) { err = x264gpu_last_error(); return -1; }
-    if (g->pack) {
-        if (!h_ix) { err = "X264GPU_BATCH: the group's levels are packed"; return -1; }
-        const x264gpu_level_index *di = (buf ? g->d_ix2 : g->d_ix) + (size_t)s * g->nmb;
-        if (x264gpu_memcpy_d2h(h_mb, dm + (size_t)s * g->nmb, g->nmb * sizeof(x264gpu_mb), st) != X264GPU_OK ||
-            x264gpu_memcpy_d2h(h_ix, di, g->nmb * sizeof(x264gpu_level_index), st) != X264GPU_OK) { err = x264gpu_last_error(); return -1; }
-        const size_t kept = ((size_t)h_ix[g->nmb - 1].at + (size_t)__builtin_popcount(h_ix[g->nmb - 1].groups)) * 16;          // levels
-        if (kept > g->nmb * (size_t)X264GPU_MB_LEVELS) { err = "X264GPU_BATCH: level index out of range"; return -1; }
-        if (kept && x264gpu_memcpy_d2h(h_lv, dl + (size_t)s * g->nmb * X264GPU_MB_LEVELS, kept * sizeof(int16_t), st) != X264GPU_OK) { err = x264gpu_last_error(); return -1; }
-        return 0;
-    }
-    if (x264gpu_memcpy_d2h(h_mb, dm + (size_t)s * g->nmb, g->nmb * sizeof(x264gpu_mb), st) != X264GPU_OK ||
-        x264gpu_memcpy_d2h(h_lv, dl + (size_t)s * g->nmb * X264GPU_MB_LEVELS, g->nmb * X264GPU_MB_LEVELS * sizeof(int16_t), st) != X264GPU_OK) { err = x264gpu_last_error(); return -1; }
-    return 0;
-}
-static void batch_leave(BatchGroup *g, int s)
-{
-    // the registry lock first (the order batch_join takes them in): "last" is decided and the group unlisted under it, so that a joiner can
-    // never be handed a group that is about to be destroyed; a group that lost a member takes no more joiners (closed), its seats stay empty
-    // ... and ONLY that under it: the round the others were waiting for (a whole device launch plus downloads) runs after the registry lock is released,
-    // under the group's own lock — every x264_encoder_open / close that touches the batcher would otherwise wait for a GPU round
-    bool last, run = false;
-    {
-        std::lock_guard<std::mutex> reg(g_batch_mu);
-        std::unique_lock<std::mutex> lk(g->m);
-        g->member[(size_t)s] = 0; g->active--; g->closed = true;
-        last = g->active == 0;
-        run = !last && g->n_arrived >= g->active && g->n_arrived > 0;      // the others were only waiting for this session
-        if (run) g->leaving++;          // keeps the group alive across the gap below: a member that times out and closes meanwhile must not destroy it under this thread
-        if (last)
-            for (size_t i = 0; i < g_batch_groups.size(); i++) if (g_batch_groups[i] == g) { g_batch_groups.erase(g_batch_groups.begin() + (long)i); break; }
-        if (last && g->leaving > 0) { g->orphaned = true; last = false; }          // the leaver still inside destroys it when it is done
-    }
-    if (run) {
-        bool destroy = false;
-        {
-            std::unique_lock<std::mutex> lk(g->m);
-            if (g->active > 0 && g->n_arrived >= g->active && g->n_arrived > 0 && !g->running) batch_run_round(g, lk);
-            g->leaving--;
-            destroy = g->orphaned && g->leaving == 0;
-        }
-        if (destroy) batch_destroy(g);
-    }
-    if (last) batch_destroy(g);
-}
 
 void x264host::xlog(const x264_param_t *p, int level, const char *fmt, ...)
 {
@@ -771,7 +513,7 @@ static void open_modes(x264_t *h)
             const char *why = p.i_threads > 1 ? "threads 1" : h->slices > 1 || p.b_sliced_threads ? "one slice per picture" : p.i_scenecut_threshold > 0 ? "scenecut 0" :
                               (h->bframes && p.i_bframe_adaptive) ? "b-adapt 0" : tree ? "no-mbtree" : p.rc.i_rc_method == X264_RC_ABR ? "constant-quantiser or CRF rate control" : nullptr;
             if (why) xlog(&p, X264_LOG_WARNING, "X264GPU_BATCH needs %s (picture k must have the same type in every session of a batch): this session runs on its own\n", why);
-            else { h->batch_n = bn; h->dpbmode = true; }
+            else { h->batch.want = bn; h->dpbmode = true; }
         }
     }
     if (h->dpbmode && !h->bframes) { p.rc.b_mb_tree = 0; }
@@ -924,7 +666,7 @@ static x264gpu_config open_device_config(x264_t *h)
     p.analyse.i_mv_range = clampi(p.analyse.i_mv_range, 32, 512);
     cfg.mv_range = p.analyse.i_mv_range;
     h->inflight = 1;
-    if (h->dpbmode && p.i_bframe > 0 && h->G == 1 && !h->batch_n && !h->rc.reads_sizes() && h->direct_mode != 3) {
+    if (h->dpbmode && p.i_bframe > 0 && h->G == 1 && !h->batch.want && !h->rc.reads_sizes() && h->direct_mode != 3) {
         // (--direct auto chooses a B picture's mode from the skip counts of the one before, ABR and 2-pass a picture's quantiser from the sizes of the ones before:
         //  those sessions code one picture at a time)
         const char *ie = getenv("X264GPU_INFLIGHT");
@@ -965,11 +707,9 @@ static bool open_device(x264_t *h)
         (void)x264gpu_set_device(h->device);
         if (!ok_setup) { xlog(&p, X264_LOG_ERROR, "GPU encoder setup failed: %s\n", err.c_str()); return false; }
         if (D > 1) xlog(&p, X264_LOG_INFO, "GOP slots on %d devices (%d + ... per device)\n", D, h->devs[0].nsl);
-    } else if (ok_setup && h->batch_n) {
-        h->batch = batch_join(cfg, h->batch_n, insz, (size_t)h->nmb, h->ql.flags, &h->batch_idx);
-        ok_setup = h->batch != nullptr;
-        if (ok_setup && h->batch->async && !h->batch->up_streams.empty()) h->up_stream = h->batch->up_streams[(size_t)h->batch_idx % h->batch->up_streams.size()];      // (the group's; without one the uploads wait on the default stream: slower, not wrong)
-        if (ok_setup) xlog(&p, X264_LOG_INFO, "X264GPU_BATCH: stream %d of a batch of %d sessions%s\n", h->batch_idx, h->batch_n, h->batch->async ? " (rounds queued: uploads overlap the device)" : "");
+    } else if (ok_setup && h->batch.want) {
+        ok_setup = h->batch.join(cfg, h->batch.want, insz, (size_t)h->nmb, h->ql.flags);
+        if (ok_setup) xlog(&p, X264_LOG_INFO, "X264GPU_BATCH: stream %d of a batch of %d sessions%s\n", h->batch.index(), h->batch.size(), h->batch.queued() ? " (rounds queued: uploads overlap the device)" : "");
     } else if (ok_setup) {
         ok_setup = x264gpu_encoder_create(&h->gpu, &cfg) == X264GPU_OK &&
                    x264gpu_malloc((void **)&h->d_mb, (size_t)h->nmb * sizeof(x264gpu_mb)) == X264GPU_OK &&
@@ -1079,7 +819,7 @@ static void open_host_buffers(x264_t *h)
     { const unsigned hw = std::thread::hardware_concurrency(); h->cavlc_threads = h->G > 1 ? 1 : cavlc_threads_default(hw >= 32 ? 16 : hw >= 16 ? 8 : hw >= 4 ? (int)hw / 2 : 1); }
     h->h_in.resize(insz);
     // (a batch session whose pictures are downloaded and coded by its helper threads keeps the records in the two deferred slots instead: 7 MB less to clear per open)
-    if (!(h->batch && h->batch->overlap)) { h->h_mb.resize((size_t)h->G * h->nmb); h->h_lv.resize((size_t)h->G * h->nmb * X264GPU_MB_LEVELS); }
+    if (!h->batch.overlap()) { h->h_mb.resize((size_t)h->G * h->nmb); h->h_lv.resize((size_t)h->G * h->nmb * X264GPU_MB_LEVELS); }
     if (h->pipeline) { h->h_mb2.resize(h->h_mb.size()); h->h_lv2.resize(h->h_lv.size()); }
     if (h->G > 1) {
         const size_t n = (size_t)h->G * h->keyint;
@@ -1708,17 +1448,20 @@ static int bmode_finish(x264_t *h, x264_t::PicPlan &f, const x264gpu_mb *mbs, co
     return bmode_finish_written(h, f, types, sets, mbs, pp_nal, pi_nal, pic_out);
 }
 
+// a helper thread still at work is told to hurry (it may be waiting for the group's next round), its sleep ended, and joined
+static void join_deferred(x264_t *h, x264_t::Deferred &d)
+{
+    if (!d.th.joinable()) return;
+    d.hurry = true;
+    h->batch.wake();
+    d.th.join();
+}
+
 // hands out a picture a helper thread finished (batch sessions with overlap): waits for the thread, publishes its NAL units; 0 when the slot is empty
 static int publish_deferred(x264_t *h, x264_t::Deferred &d, x264_nal_t **pp_nal, int *pi_nal, x264_picture_t *pic_out)
 {
     if (!d.valid) return 0;
-    if (d.th.joinable()) {
-        d.hurry = true;
-        if (h->batch) { std::lock_guard<std::mutex> lg(h->batch->m); h->batch->cv.notify_all(); }
-        const long t0 = h->batch && h->batch->timing ? us_now() : 0;
-        d.th.join();
-        if (h->batch && h->batch->timing) h->batch->t_us[5] += us_now() - t0;
-    }
+    h->batch.timed(Batch::JOIN, 0, [&] { join_deferred(h, d); });
     d.valid = false;
     if (!d.err.empty()) { xlog(&h->param, X264_LOG_ERROR, "x264_encoder_encode: download of a batched picture failed: %s\n", d.err.c_str()); h->failed = true; return -1; }
     h->out.swap(d.out); h->nal_off = d.off; h->last_stats = d.stats;
@@ -1746,7 +1489,7 @@ static int bmode_defer(x264_t *h, x264_t::PicPlan &f, int bbuf, x264_nal_t **pp_
     if (d.th.joinable()) d.th.join();          // (handed out two calls ago: long finished)
     d.out = h->out; d.off = h->nal_off; d.types = types; d.err.clear(); d.nal_ref_idc = f.nal_ref_idc; d.stats = SliceStats{ 0 };
     d.mb.resize((size_t)h->nmb);
-    if (h->batch->pack) d.ix.resize((size_t)h->nmb);
+    if (h->batch.packed()) d.ix.resize((size_t)h->nmb);
     if (!d.lv) d.lv.reset(new (std::nothrow) int16_t[(size_t)h->nmb * X264GPU_MB_LEVELS]);
     if (!d.lv) { xlog(&p, X264_LOG_ERROR, "x264_encoder_encode: out of memory (download buffers)\n"); h->failed = true; return -1; }
     d.i_type = x264_type_of(pl.type); d.b_keyframe = idr; d.pts = pl.e.pts; d.img = pl.e.img;
@@ -1754,26 +1497,19 @@ static int bmode_defer(x264_t *h, x264_t::PicPlan &f, int bbuf, x264_nal_t **pp_
     d.q_type = quality_type(pl.type); d.q_poc = f.pic.poc;
     if (h->rc.reads_sizes()) { xlog(&p, X264_LOG_ERROR, "x264_encoder_encode: a batched session cannot run rate control that reads the coded sizes\n"); h->failed = true; return -1; }
     d.dts = coded_dts(h, h->coded_count);
-    BatchGroup *g = h->batch;
+    Batch *b = &h->batch;
     const SliceParams sp = f.sp;
-    const int bidx = h->batch_idx, slices = h->slices, threads = h->cavlc_threads, dev = h->device;
+    const int slices = h->slices, threads = h->cavlc_threads, dev = h->device;
     const bool annexb = p.b_annexb != 0;
-    long my_launched;
-    { std::lock_guard<std::mutex> lg(g->m); my_launched = g->launched; }
+    const long my_launched = b->launched();
     d.hurry = false;
-    d.th = std::thread([&d, g, bidx, bbuf, sp, slices, threads, annexb, idr, dev, my_launched]() {
+    d.th = std::thread([&d, b, bbuf, sp, slices, threads, annexb, idr, dev, my_launched]() {
         x264gpu_set_device(dev);
         x264gpu_level_index *ix = d.ix.empty() ? nullptr : d.ix.data();
-        if (batch_download(g, bidx, bbuf, d.mb.data(), d.lv.get(), d.err, ix, &d.q)) return;
-        const long t0 = g->timing ? us_now() : 0;
-        {
-            // the slices are written once the group's next round is on the device (the callers need the cores to get it there), or when the picture is asked for
-            std::unique_lock<std::mutex> lk(g->m);
-            g->cv.wait_for(lk, std::chrono::seconds(30), [&] { return g->launched > my_launched || d.hurry.load() || g->closed; });
-        }
-        const long t1 = g->timing ? us_now() : 0;
-        write_slices(d.out, d.off, d.types, sp, slices, d.mb.data(), d.lv.get(), annexb, idr, &d.stats, threads, ix);
-        if (g->timing) { const long t2 = us_now(); g->t_us[2] += t1 - t0; g->t_us[3] += t2 - t1; if (my_launched >= 1 && my_launched <= 64) g->r_sl[my_launched - 1] += t2 - t1; }
+        if (b->download(bbuf, d.mb.data(), d.lv.get(), d.err, ix, &d.q)) return;
+        // the slices are written once the group's next round is on the device (the callers need the cores to get it there), or when the picture is asked for
+        b->wait_launched(my_launched, d.hurry);
+        b->timed(Batch::SLICES, my_launched, [&] { write_slices(d.out, d.off, d.types, sp, slices, d.mb.data(), d.lv.get(), annexb, idr, &d.stats, threads, ix); });
     });
     d.valid = true;
     h->dpb.commit();
@@ -1799,11 +1535,11 @@ static int encode_bmode(x264_t *h, x264_nal_t **pp_nal, int *pi_nal, x264_pictur
     // launch: the group's round (its results downloaded here unless a helper thread does it: deferred), or this session's encoder and two downloads on the default stream
     const uint8_t *d_src = h->q_raw[(size_t)f.pl.e.slot];
     int bbuf = 0;
-    const bool deferred = h->batch && h->batch->overlap;
-    if (h->batch) {
+    const bool deferred = h->batch.overlap();
+    if (h->batch.joined()) {
         std::string berr;
-        if (batch_submit(h->batch, h->batch_idx, d_src, f.pic, &bbuf, berr) ||
-            (!deferred && batch_download(h->batch, h->batch_idx, bbuf, h->h_mb.data(), h->h_lv.data(), berr, nullptr, &h->hq[0]))) {
+        if (h->batch.submit(d_src, f.pic, &bbuf, berr) ||
+            (!deferred && h->batch.download(bbuf, h->h_mb.data(), h->h_lv.data(), berr, nullptr, &h->hq[0]))) {
             xlog(&p, X264_LOG_ERROR, "x264_encoder_encode: GPU hot path failed: %s\n", berr.c_str());
             h->failed = true;
             return -1;
@@ -1897,8 +1633,8 @@ static bool inflight_issue(x264_t *h, bool flushing)
             if (w >= 0 && w != ci) ok = x264gpu_stream_wait_event(c.stream, h->lctx[(size_t)w].ev) == X264GPU_OK;
         }
     // ... and behind the default stream: this picture's upload, its quantiser offsets and the lookahead's vectors were produced there
-    ok = ok && x264gpu_event_record(h->ev_la, h->up_stream) == X264GPU_OK && x264gpu_stream_wait_event(c.stream, h->ev_la) == X264GPU_OK;
-    if (ok && h->up_stream) ok = x264gpu_event_record(h->ev_la, nullptr) == X264GPU_OK && x264gpu_stream_wait_event(c.stream, h->ev_la) == X264GPU_OK;
+    ok = ok && x264gpu_event_record(h->ev_la, h->batch.upload_stream()) == X264GPU_OK && x264gpu_stream_wait_event(c.stream, h->ev_la) == X264GPU_OK;
+    if (ok && h->batch.upload_stream()) ok = x264gpu_event_record(h->ev_la, nullptr) == X264GPU_OK && x264gpu_stream_wait_event(c.stream, h->ev_la) == X264GPU_OK;
     ok = ok && x264gpu_encode_pictures(c.gpu, h->q_raw[(size_t)f.pl.e.slot], &pic, c.d_mb, c.d_lv, c.stream) == X264GPU_OK &&
          (!h->ql.flags || h->ql.queue(c.gpu, c.d_q, c.stream) == X264GPU_OK) && x264gpu_event_record(c.ev, c.stream) == X264GPU_OK;
     if (!ok) { xlog(&h->param, X264_LOG_ERROR, "x264_encoder_encode: GPU hot path failed: %s\n", x264gpu_last_error()); h->failed = true; return false; }
@@ -1976,8 +1712,9 @@ int x264_encoder_encode(x264_t *h, x264_nal_t **pp_nal, int *pi_nal, x264_pictur
     //      AQ offsets, slice-type decision (keyint / forced type / scenecut) — all causal, so they are taken on arrival ----
     const int slot = (int)(h->la_count % h->Q);
     uint8_t *d_raw = h->q_raw[(size_t)slot];
-    if ((!resident && x264gpu_memcpy_h2d(d_raw, h->h_in.data(), h->h_in.size(), h->up_stream) != X264GPU_OK) ||
-        (resident && d_raw != h->d_in && (x264gpu_memcpy_d2d(d_raw, h->d_in, h->h_in.size(), h->up_stream) != X264GPU_OK || (h->up_stream && x264gpu_stream_sync(h->up_stream) != X264GPU_OK)))) {
+    void *const up = h->batch.upload_stream();          // (a batch session's: its pictures go up while the group's round runs on the compute stream)
+    if ((!resident && x264gpu_memcpy_h2d(d_raw, h->h_in.data(), h->h_in.size(), up) != X264GPU_OK) ||
+        (resident && d_raw != h->d_in && (x264gpu_memcpy_d2d(d_raw, h->d_in, h->h_in.size(), up) != X264GPU_OK || (up && x264gpu_stream_sync(up) != X264GPU_OK)))) {
         xlog(&p, X264_LOG_ERROR, "x264_encoder_encode: upload failed: %s\n", x264gpu_last_error());
         return -1;
     }
@@ -2040,7 +1777,7 @@ void x264_encoder_close(x264_t *h)
     if (!h) return;
     join_pool(h);
     join_gpu(h);
-    for (auto &d : h->defer) if (d.th.joinable()) { d.hurry = true; if (h->batch) { std::lock_guard<std::mutex> lg(h->batch->m); h->batch->cv.notify_all(); } d.th.join(); }
+    for (auto &d : h->defer) join_deferred(h, d);
     if (getenv("X264GPU_HOST_TIMING") && h->t_phase[5] > 0)
         fprintf(stderr, "x264gpu host timing, ms per call over %.0f calls: copy-in %.2f, upload+lookahead %.2f, GPU %.2f, download %.2f, entropy %.2f\n", h->t_phase[5],
                 1e3 * h->t_phase[0] / h->t_phase[5], 1e3 * h->t_phase[1] / h->t_phase[5], 1e3 * h->t_phase[2] / h->t_phase[5], 1e3 * h->t_phase[3] / h->t_phase[5], 1e3 * h->t_phase[4] / h->t_phase[5]);
@@ -2057,8 +1794,7 @@ void x264_encoder_close(x264_t *h)
     }
     h->lctx.clear();
     if (h->ev_la) x264gpu_event_destroy(h->ev_la);
-    if (h->batch) { batch_leave(h->batch, h->batch_idx); h->batch = nullptr; }
-    h->up_stream = nullptr;          // (the batch group's)
+    h->batch.leave();
     if (h->gpu) x264gpu_encoder_destroy(h->gpu);
     if (h->d_in) x264gpu_free(h->d_in);
     if (h->d_mb) x264gpu_free(h->d_mb);
