@@ -103,6 +103,10 @@ int x264gpu_mc_avg(const uint8_t *d_a, const uint8_t *d_b, size_t bytes, int wei
  * cat 3; AC blocks: entry 0 unused = 0), quantiser qp, inter / intra lambda, against the 460 context variables ((pStateIdx << 1) | valMPS) of a
  * slice.  d_levels receives the levels in the same layout, d_nz one byte per block.  The macroblock loop does not use it yet (cfg.trellis). */
 int x264gpu_trellis_blocks(const int16_t *d_coefs, int nblk, int cat, int qp, int intra, const uint8_t *d_states460, int16_t *d_levels, uint8_t *d_nz, void *stream);
+/* The same with the test hooks of the search's loop choice (csrc/trellis.hip.h): force_general != 0 runs the general loop whatever the input; d_paths
+ * (or NULL) receives one byte per pass of eight blocks, bit 0 = the levels-of-one loop ran, bit 1 = on 32-bit scores (no such loop is built: always 0). */
+int x264gpu_trellis_blocks_ex(const int16_t *d_coefs, int nblk, int cat, int qp, int intra, const uint8_t *d_states460, int16_t *d_levels, uint8_t *d_nz, int force_general,
+                              uint8_t *d_paths, void *stream);
 int x264gpu_mc_weight(const uint8_t *d_src, size_t bytes, int scale, int denom, int offset, uint8_t *d_out, void *stream);
 /* The level walk of the CABAC size pricing as a primitive ([x264-upstream] encoder/cabac.c coeff_abs_level_minus1 of residual_block_cabac, every block of a
  * macroblock at once — csrc/cabac_rd.hip.h cab_levels_all): n cases; d_levels the macroblocks' levels in x264gpu_mb layout (X264GPU_MB_LEVELS each);

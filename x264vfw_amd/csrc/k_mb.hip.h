@@ -885,7 +885,7 @@ __device__ __forceinline__ unsigned trellis_run(const TrCtx &tr, int16_t *coefs,
 {
     unsigned out = 0;
     for (int b0 = 0; b0 < nblk; b0 += 8)
-        out |= trellis_blocks<CAT>((lds_i16 *)(coefs + b0 * stride), stride, min(8, nblk - b0), qp, intra, tr.model, tr.tt, CAT == 5 ? tr.r8 : tr.r) << b0;
+        out |= (trellis_blocks<CAT>((lds_i16 *)(coefs + b0 * stride), stride, min(8, nblk - b0), qp, intra, tr.model, tr.tt, CAT == 5 ? tr.r8 : tr.r) & 0xffu) << b0;       // (bit 8: the levels-of-one loop ran)
     return out;
 }
 __device__ __forceinline__ void load_levels_scan(const int16_t *src, int v[4], int j)

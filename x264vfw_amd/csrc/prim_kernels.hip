@@ -349,8 +349,8 @@ int trellis_table_ptrs(const uint16_t **su, const uint8_t **tu, const int **l2)
     return rc;
 }
 
-template <int CAT>
-__global__ void __launch_bounds__(64) k_trellis_blocks(const int16_t *coefs, int nblk, int qp, int intra, const uint8_t *states, TrellisTab tt, int16_t *levels, uint8_t *nz)
+template <int CAT, bool FORCE_GENERAL>
+__global__ void __launch_bounds__(64) k_trellis_blocks(const int16_t *coefs, int nblk, int qp, int intra, const uint8_t *states, TrellisTab tt, int16_t *levels, uint8_t *nz, uint8_t *paths)
 {
     constexpr int NC = CAT == 5 ? 64 : CAT == 3 ? 4 : 16;
     __shared__ int16_t buf[8 * 64];
@@ -374,10 +374,11 @@ __global__ void __launch_bounds__(64) k_trellis_blocks(const int16_t *coefs, int
         const int nb = min(8, nblk - b0);
         for (int i = lane; i < nb * NC; i += 64) buf[i] = coefs[(size_t)b0 * NC + i];
         __syncthreads();
-        const unsigned m = trellis_blocks<CAT>((lds_i16 *)buf, NC, nb, qp, intra != 0, model, tt, reg);
+        const unsigned m = trellis_blocks<CAT, FORCE_GENERAL>((lds_i16 *)buf, NC, nb, qp, intra != 0, model, tt, reg);
         __syncthreads();
         for (int i = lane; i < nb * NC; i += 64) levels[(size_t)b0 * NC + i] = buf[i];
         if (lane < nb) nz[b0 + lane] = (uint8_t)((m >> lane) & 1);
+        if (paths && lane == 0) paths[b0 >> 3] = (uint8_t)((m >> 8) & 3);
         __syncthreads();
     }
 }
@@ -386,7 +387,8 @@ __global__ void __launch_bounds__(64) k_trellis_blocks(const int16_t *coefs, int
 
 extern "C" {
 
-int x264gpu_trellis_blocks(const int16_t *d_coefs, int nblk, int cat, int qp, int intra, const uint8_t *d_states460, int16_t *d_levels, uint8_t *d_nz, void *stream)
+int x264gpu_trellis_blocks_ex(const int16_t *d_coefs, int nblk, int cat, int qp, int intra, const uint8_t *d_states460, int16_t *d_levels, uint8_t *d_nz, int force_general,
+                             uint8_t *d_paths, void *stream)
 {
     ARG_TRY(d_coefs && d_states460 && d_levels && d_nz && nblk >= 0 && cat >= 0 && cat <= 5 && qp >= 0 && qp <= 51);
     if (!nblk) return X264GPU_OK;
@@ -394,16 +396,25 @@ int x264gpu_trellis_blocks(const int16_t *d_coefs, int nblk, int cat, int qp, in
     const int rc = trellis_tables(&tt);
     if (rc != X264GPU_OK) return rc;
     const hipStream_t st = (hipStream_t)stream;
+#define TRELLIS_LAUNCH(CAT_) \
+    if (force_general) hipLaunchKernelGGL((k_trellis_blocks<CAT_, true>), dim3(1), dim3(64), 0, st, d_coefs, nblk, qp, intra, d_states460, tt, d_levels, d_nz, d_paths); \
+    else hipLaunchKernelGGL((k_trellis_blocks<CAT_, false>), dim3(1), dim3(64), 0, st, d_coefs, nblk, qp, intra, d_states460, tt, d_levels, d_nz, d_paths)
     switch (cat) {
-    case 0: hipLaunchKernelGGL(k_trellis_blocks<0>, dim3(1), dim3(64), 0, st, d_coefs, nblk, qp, intra, d_states460, tt, d_levels, d_nz); break;
-    case 1: hipLaunchKernelGGL(k_trellis_blocks<1>, dim3(1), dim3(64), 0, st, d_coefs, nblk, qp, intra, d_states460, tt, d_levels, d_nz); break;
-    case 2: hipLaunchKernelGGL(k_trellis_blocks<2>, dim3(1), dim3(64), 0, st, d_coefs, nblk, qp, intra, d_states460, tt, d_levels, d_nz); break;
-    case 3: hipLaunchKernelGGL(k_trellis_blocks<3>, dim3(1), dim3(64), 0, st, d_coefs, nblk, qp, intra, d_states460, tt, d_levels, d_nz); break;
-    case 4: hipLaunchKernelGGL(k_trellis_blocks<4>, dim3(1), dim3(64), 0, st, d_coefs, nblk, qp, intra, d_states460, tt, d_levels, d_nz); break;
-    default: hipLaunchKernelGGL(k_trellis_blocks<5>, dim3(1), dim3(64), 0, st, d_coefs, nblk, qp, intra, d_states460, tt, d_levels, d_nz); break;
+    case 0: TRELLIS_LAUNCH(0); break;
+    case 1: TRELLIS_LAUNCH(1); break;
+    case 2: TRELLIS_LAUNCH(2); break;
+    case 3: TRELLIS_LAUNCH(3); break;
+    case 4: TRELLIS_LAUNCH(4); break;
+    default: TRELLIS_LAUNCH(5); break;
     }
+#undef TRELLIS_LAUNCH
     HIP_TRY(hipGetLastError());
     return X264GPU_OK;
+}
+
+int x264gpu_trellis_blocks(const int16_t *d_coefs, int nblk, int cat, int qp, int intra, const uint8_t *d_states460, int16_t *d_levels, uint8_t *d_nz, void *stream)
+{
+    return x264gpu_trellis_blocks_ex(d_coefs, nblk, cat, qp, intra, d_states460, d_levels, d_nz, 0, nullptr, stream);
 }
 
 

@@ -60,15 +60,20 @@ __device__ __forceinline__ int tr_next(uint32_t model, int st, int b)
 }
 __device__ __forceinline__ int tr_size_ue_big(unsigned v) { return 2 * (31 - __builtin_clz(v + 1)) + 1; }
 
+// a value from the lane N below in the row of sixteen (DPP row_shr:N; -1 where the row ends): how a node reads the nodes below it in its block
+template <int N> __device__ __forceinline__ uint32_t tr_row_shr(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, 0x110 + N, 0xf, 0xf, false); }
+template <int N> __device__ __forceinline__ unsigned long long tr_row_shr(unsigned long long v) { return ((unsigned long long)tr_row_shr<N>((uint32_t)(v >> 32)) << 32) | tr_row_shr<N>((uint32_t)v); }
+
 // Up to eight blocks of category CAT (0 luma DC, 1 luma AC, 2 luma 4x4, 3 chroma DC, 4 chroma AC, 5 luma 8x8) whose coefficients lie in LDS
 // in scan order, block b at coefs + b * stride (AC blocks: 16 entries, entry 0 = 0); the levels replace them.  nblk <= 8.  lane & 7 = node,
 // lane >> 3 = block.  st_sig / st_last / st_abs: accessors of the slice's context variables of the category (wave-uniform arguments).
-// Returns the mask of blocks with a non-zero level (wave-uniform).
+// Returns the mask of blocks with a non-zero level in bits 0..7 (wave-uniform), and 0x100 when the levels-of-one loop ran.  FORCE_GENERAL (the
+// primitive's test hook only): always the general loop.
 // The context variables come in `reg`: the role-indexed register of the category (cabac_rd.hip.h: r for categories 0..4 — this category's byte —,
 // r8 for 8x8 blocks).  ONE out-of-line copy per category serves every call site: inlined eight times the search cost the macroblock loop
 // twice the register spills.
 typedef __attribute__((address_space(3))) int16_t lds_i16;
-template <int CAT>
+template <int CAT, bool FORCE_GENERAL = false>
 __device__ __noinline__ unsigned trellis_blocks(lds_i16 *coefs, int stride, int nblk, int qp, bool intra, uint32_t model, TrellisTab tt, uint32_t reg)
 {
     namespace T = x264gpu_cabac;
@@ -103,7 +108,8 @@ __device__ __noinline__ unsigned trellis_blocks(lds_i16 *coefs, int stride, int 
 
     // the positions the guess leaves non-zero, per block (the same mask in its eight lanes)
     unsigned long long nzm = 0;
-    for (int p = n; p < NC; p += 8) if (blk_on && p >= B_AC && guess(mine[p], p)) nzm |= 1ull << p;
+    int qmax = 0;                                    // ... and the largest guess this lane has seen
+    for (int p = n; p < NC; p += 8) if (blk_on && p >= B_AC) { const int gq = guess(mine[p], p); if (gq) nzm |= 1ull << p; qmax = max(qmax, gq); }
     for (int m = 1; m < 8; m <<= 1) {
         const unsigned lo32 = (unsigned)__shfl_xor((int)(unsigned)nzm, m), hi32 = CAT == 5 ? (unsigned)__shfl_xor((int)(unsigned)(nzm >> 32), m) : 0u;
         nzm |= ((unsigned long long)hi32 << 32) | lo32;
@@ -156,6 +162,60 @@ __device__ __noinline__ unsigned trellis_blocks(lds_i16 *coefs, int stride, int 
 
     unsigned long long z_before = 0;                 // running sum of the zero costs below the block's previous non-zero position (exclusive)
     bool started = false;
+    // A call in which no active block has a guess of two or more (wave-uniform) runs the levels-of-one loop: ctx_hi never turns on, only nodes 0..3
+    // ever live, and the two candidates of every step are level 0 (node n <- n) and level 1 (1 <- 0, 2 <- 1, 3 <- 2 and 3).  No greater-than-one
+    // context, no unary tables, no escape suffix; the node below is one DPP row shift away, so nothing goes through ds_bpermute but the position's
+    // costs and the one model lookup.  Same scores, same order of evaluation, same levels as the general loop.
+    const bool ones = !FORCE_GENERAL && !__ballot(qmax >= 2);
+    if (ones) {
+        for (;;) {
+            const bool act = blk_on && nzm != 0;
+            if (!__ballot(act)) break;
+            const int i = act ? 63 - __builtin_clzll(nzm) : 0;          // this block's next non-zero position, from the top
+            nzm &= ~(1ull << i);
+            const int paddr = i << 2;
+            const uint32_t pa = (uint32_t)__builtin_amdgcn_ds_bpermute(paddr, (int)pos_a), t0i = (uint32_t)__builtin_amdgcn_ds_bpermute(paddr, (int)pos_t0);
+            const unsigned long long zi = ((unsigned long long)(uint32_t)__builtin_amdgcn_ds_bpermute(paddr, (int)(unsigned)(pos_z >> 32)) << 32) | (uint32_t)__builtin_amdgcn_ds_bpermute(paddr, (int)(unsigned)pos_z);
+            if (act && started && n == 0) score -= z_before - zi;          // the zeros since the previous non-zero position (as in the general loop)
+            if (act) { z_before = zi - t0i; started = true; }
+            const int cost1 = (int)(pa & 4095), cost2 = (int)((pa >> 12) & 4095), cl = (int)(pa >> 24);
+            const int un = pick(q_unq, cl), wgt = pick(q_w, cl);
+            const int c = act ? (int)mine[i] : 0, a = abs(c), ua = (un + 128) >> 8;
+            auto wsq = [&](int d) { return (unsigned long long)(unsigned)(d * d) * (unsigned)wgt; };
+            // level 0 reconstructs to 0 whatever the block (the DC-only term too), so its two distortions agree: ssd0[0] - ssd1[0] = -t0
+            const unsigned long long e0 = wsq(a) + t0i, e1 = wsq(a - ua);
+            unsigned long long e1_first = e1;
+            if (!DC) { if (i == 0) e1_first = wsq(c - (((c < 0 ? -ua : ua) + 8) & ~15)); }
+            const int l1state = n == 3 ? (int)((cs >> 8) & 255) : ls_l1;
+            const uint32_t tm = (uint32_t)__builtin_amdgcn_ds_bpermute((l1state >> 1) << 2, (int)model);
+            const int l1s = l1state >> 1, l1m = l1state & 1;
+            const int ent_l1_0 = l1m ? (int)((tm >> 9) & 0x7ff) : (int)(tm & 0x1ff);
+            const int nxt_l1_0 = l1m ? ((int)(tm >> 20) << 1) | (l1s == 0 ? l1m ^ 1 : l1m) : (min(l1s + 1, 62) << 1) | l1m;
+            const unsigned f8 = (unsigned)(n ? cost1 : cost2) + (unsigned)ent_l1_0 + 256u;
+            const bool src_ok = act && n <= 3 && (n == 0 || (long long)score >= 0);
+            const unsigned long long k0 = src_ok ? score - (n == 0 ? (unsigned long long)t0i : 0ull) : SMAX;
+            const unsigned long long k1 = src_ok ? score + ((n ? e1 : e1_first) - e0) + (((unsigned long long)f8 * (unsigned long long)lambda2) >> 4) : SMAX;
+            const uint32_t cs1 = n == 2 ? init4 : n == 3 ? (cs & ~0xff00u) | ((uint32_t)nxt_l1_0 << 8) : cs;
+            // as a destination, in x264's evaluation order (first strictly better wins): level 0 from the node itself, level 1 from the node
+            // below, level 1 from the node itself (node 3 only)
+            const unsigned long long km = tr_row_shr<1>(k1);
+            const uint32_t csm = tr_row_shr<1>(cs1);
+            unsigned long long best = k0;
+            int who = 0;
+            if (n >= 1 && n <= 3 && km < best) { best = km; who = 1; }
+            if (n == 3 && k1 < best) { best = k1; who = 2; }
+            uint32_t pathm[PW];
+            for (int w = 0; w < PW; w++) pathm[w] = tr_row_shr<1>(path[w]);
+            if (act) {
+                score = best;
+                cs = who == 0 ? cs : who == 1 ? csm : cs1;
+                const uint32_t choice = best != SMAX ? (who ? 2u : 1u) : 0u;       // 1 = level q - 1 = 0, 2 = level q = 1
+                for (int w = 0; w < PW; w++) { if (who == 1) path[w] = pathm[w]; if (w == (i >> 4)) path[w] |= choice << (2 * (i & 15)); }
+            }
+        }
+    }
+    // ---- the general loop (after a levels-of-one call nothing is left for it: it ends at its first test; laid out one after the other, not as
+    //      two branches, the pair needs no more registers than the general loop alone) ----
     for (;;) {
         const bool act = blk_on && nzm != 0, go = act;
         if (!__ballot(act)) break;
@@ -301,7 +361,7 @@ __device__ __noinline__ unsigned trellis_blocks(lds_i16 *coefs, int stride, int 
     const unsigned long long nzb = __ballot(nz);
     unsigned out = 0;
     for (int b = 0; b < 8; b++) if ((nzb >> (8 * b)) & 0xff) out |= 1u << b;
-    return out;
+    return out | (ones ? 0x100u : 0u);
 }
 
 }  // namespace x264gpu
