@@ -69,6 +69,8 @@ def main():
             print("     around the pricing: candidate's distortion terms + header inputs %.0f  cost bookkeeping %.0f cycles" % (a[27], a[28]))
         if a[24] > 0:
             print("     inter encode: prediction (b_predict) %.0f  luma transform / quantiser / reconstruction %.0f  chroma %.0f cycles" % (a[24], a[25], a[26]))
+        if a[29] + a[31] > 0:         # B slices: the prediction memo (k_mb.hip.h PMEMO)
+            print("     inter encode predictions per macroblock: %.2f served from the memo, %.2f fetched" % (a[29], a[31]))
         mx = out[:, :13].sum(axis=1).astype(np.float64)
         print("     slowest/mean stream cycles: %.3f   share: " % (mx.max() / mx.mean()) + " ".join("%8.1f%%" % (100 * v / tot) for v in a[:13]))
 

@@ -1447,33 +1447,72 @@ static __constant__ const uint32_t c_dia4d[33] = {
 #undef D4
 
 // x264_mb_mc of a B macroblock for this lane's row of four luma samples (Z layout) and, in lanes 0..31, its row of the chroma 4x4 block
-// (lane >> 2) & 3 of plane (lane >> 4) & 1: from list 0, list 1, or both averaged with the pair's implicit weight (biwv: lane r0 * 4 + r1)
-__device__ __forceinline__ void b_predict(const EncK &k, const MbCtx &c, const BCfg &g0, int biwv, uint32_t &pred, uint32_t &cpred)
+// (lane >> 2) & 3 of plane (lane >> 4) & 1: from list 0, list 1, or both averaged with the pair's implicit weight (biwv: lane r0 * 4 + r1).
+// Two steps, so that rows a wavefront already holds need no second trip to memory (the B slices' prediction memo, k_mb_slice):
+//   b_fetch    the trip to memory — per list, this lane's luma row (p0 / p1) and its chroma row of the lane's plane (c0 / c1)
+//   b_combine  the list select and the weighted average of fetched rows (only the references of g matter to it)
+// x264 mb_mc_*xywh: vectors are clipped to the macroblock's mv_min / mv_max before the fetch — a spatial-direct vector is a neighbour's, taken as it
+// is, and can point farther than the padding reaches (same samples inside the replicated border)
+__device__ __forceinline__ BCfg b_clip(const MbCtx &c, const BCfg &g0)
 {
-    const int lane = relane(c.lane), zx = z_x0(lane), zy = z_y(lane), j4 = lane & 3;
-    // x264 mb_mc_*xywh: vectors are clipped to the macroblock's mv_min / mv_max before the fetch — a spatial-direct vector is a neighbour's, taken as it
-    // is, and can point farther than the padding reaches (same samples inside the replicated border)
     BCfg g = g0;
     g.x0 = clampi(g.x0, c.mvmin0, c.mvmax0); g.y0 = clampi(g.y0, c.mvmin1, c.mvmax1); g.x1 = clampi(g.x1, c.mvmin0, c.mvmax0); g.y1 = clampi(g.y1, c.mvmin1, c.mvmax1);
-    {
-        // (both lists are fetched whether or not the block uses them — an unused list reads reference 0 at its clipped vector and is dropped: four
-        //  loads in flight together instead of two latencies one after the other behind per-lane branches)
-        const uint32_t p0 = mc_luma_row4(ref_plane00(k, c.s, max(g.r0, 0)), k.plane_bytes, k.rs, c.px + zx, c.py + zy, g.x0, g.y0);
-        const uint32_t p1 = mc_luma_row4(ref_plane00(k, c.s, k.nref + max(g.r1, 0)), k.plane_bytes, k.rs, c.px + zx, c.py + zy, g.x1, g.y1);
-        const int w = __shfl(biwv, max(g.r0, 0) * 4 + max(g.r1, 0));
-        pred = g.r0 >= 0 ? (g.r1 >= 0 ? avg_weight4_u8(p0, p1, w) : p0) : p1;
-    }
-    {
-        const int pl = (lane >> 4) & 1, ci = (lane >> 2) & 3, cx0 = (ci & 1) * 4, cyy = (ci >> 1) * 4 + j4;
-        const int r0 = __shfl(g.r0, ci * 16), x0 = __shfl(g.x0, ci * 16), y0 = __shfl(g.y0, ci * 16);
-        const int r1 = __shfl(g.r1, ci * 16), x1 = __shfl(g.x1, ci * 16), y1 = __shfl(g.y1, ci * 16);
-        uint32_t u0 = 0, v0 = 0, u1 = 0, v1 = 0;
-        mc_chroma_row4(ref_chroma00(k, c.s, max(r0, 0)), k.rs, c.mbx * 8 + cx0, c.mby * 8 + cyy, x0, y0, u0, v0);
-        mc_chroma_row4(ref_chroma00(k, c.s, k.nref + max(r1, 0)), k.rs, c.mbx * 8 + cx0, c.mby * 8 + cyy, x1, y1, u1, v1);
-        const int w = __shfl(biwv, max(r0, 0) * 4 + max(r1, 0));
-        const uint32_t a = pl ? v0 : u0, b = pl ? v1 : u1;
-        cpred = r0 >= 0 ? (r1 >= 0 ? avg_weight4_u8(a, b, w) : a) : b;
-    }
+    return g;
+}
+// (both lists are fetched whether or not the block uses them — an unused list reads reference 0 at its clipped vector and is dropped: four
+//  loads in flight together instead of two latencies one after the other behind per-lane branches)
+__device__ __forceinline__ void b_fetch_luma(const EncK &k, const MbCtx &c, const BCfg &g, uint32_t &p0, uint32_t &p1)
+{
+    const int lane = relane(c.lane), zx = z_x0(lane), zy = z_y(lane);
+    p0 = mc_luma_row4(ref_plane00(k, c.s, max(g.r0, 0)), k.plane_bytes, k.rs, c.px + zx, c.py + zy, g.x0, g.y0);
+    p1 = mc_luma_row4(ref_plane00(k, c.s, k.nref + max(g.r1, 0)), k.plane_bytes, k.rs, c.px + zx, c.py + zy, g.x1, g.y1);
+}
+__device__ __forceinline__ void b_combine_luma(const BCfg &g, int biwv, uint32_t p0, uint32_t p1, uint32_t &pred)
+{
+    const int w = __shfl(biwv, max(g.r0, 0) * 4 + max(g.r1, 0));
+    pred = g.r0 >= 0 ? (g.r1 >= 0 ? avg_weight4_u8(p0, p1, w) : p0) : p1;
+}
+__device__ __forceinline__ void b_fetch_chroma(const EncK &k, const MbCtx &c, const BCfg &g, uint32_t &c0, uint32_t &c1)
+{
+    const int lane = relane(c.lane), j4 = lane & 3;
+    const int pl = (lane >> 4) & 1, ci = (lane >> 2) & 3, cx0 = (ci & 1) * 4, cyy = (ci >> 1) * 4 + j4;
+    const int r0 = __shfl(g.r0, ci * 16), x0 = __shfl(g.x0, ci * 16), y0 = __shfl(g.y0, ci * 16);
+    const int r1 = __shfl(g.r1, ci * 16), x1 = __shfl(g.x1, ci * 16), y1 = __shfl(g.y1, ci * 16);
+    uint32_t u0 = 0, v0 = 0, u1 = 0, v1 = 0;
+    mc_chroma_row4(ref_chroma00(k, c.s, max(r0, 0)), k.rs, c.mbx * 8 + cx0, c.mby * 8 + cyy, x0, y0, u0, v0);
+    mc_chroma_row4(ref_chroma00(k, c.s, k.nref + max(r1, 0)), k.rs, c.mbx * 8 + cx0, c.mby * 8 + cyy, x1, y1, u1, v1);
+    c0 = pl ? v0 : u0; c1 = pl ? v1 : u1;
+}
+__device__ __forceinline__ void b_combine_chroma(const MbCtx &c, const BCfg &g, int biwv, uint32_t c0, uint32_t c1, uint32_t &cpred)
+{
+    const int ci = (relane(c.lane) >> 2) & 3;
+    const int r0 = __shfl(g.r0, ci * 16), r1 = __shfl(g.r1, ci * 16);
+    const int w = __shfl(biwv, max(r0, 0) * 4 + max(r1, 0));
+    cpred = r0 >= 0 ? (r1 >= 0 ? avg_weight4_u8(c0, c1, w) : c0) : c1;
+}
+
+__device__ __forceinline__ void b_fetch(const EncK &k, const MbCtx &c, const BCfg &g0, uint32_t &p0, uint32_t &p1, uint32_t &c0, uint32_t &c1)
+{
+    const BCfg g = b_clip(c, g0);
+    b_fetch_luma(k, c, g, p0, p1);
+    b_fetch_chroma(k, c, g, c0, c1);
+}
+
+__device__ __forceinline__ void b_combine(const MbCtx &c, const BCfg &g, int biwv, uint32_t p0, uint32_t p1, uint32_t c0, uint32_t c1, uint32_t &pred, uint32_t &cpred)
+{
+    b_combine_luma(g, biwv, p0, p1, pred);
+    b_combine_chroma(c, g, biwv, c0, c1, cpred);
+}
+
+// fetch + combine, luma then chroma (the call sites that hold nothing: the partition shapes' probes, the zero-vector probe, the RD refinement)
+__device__ __forceinline__ void b_predict(const EncK &k, const MbCtx &c, const BCfg &g0, int biwv, uint32_t &pred, uint32_t &cpred)
+{
+    const BCfg g = b_clip(c, g0);
+    uint32_t p0, p1, c0, c1;
+    b_fetch_luma(k, c, g, p0, p1);
+    b_combine_luma(g, biwv, p0, p1, pred);
+    b_fetch_chroma(k, c, g, c0, c1);
+    b_combine_chroma(c, g, biwv, c0, c1, cpred);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2018,6 +2057,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MB_WAVES_PER
         // SATD and RD costs of x264_mb_analysis_t's B fields, the per-block / per-half list decisions
         BCfg dcfg = { -1, 0, 0, -1, 0, 0 }, ecfg = { -1, 0, 0, -1, 0, 0 };
         unsigned euse = 0;
+        // the prediction memo (not in the RD-refinement instantiations): rows this macroblock's analysis fetched and its candidate encodes ask for again —
+        // the direct prediction (luma / chroma as combined; pm_dv: held) and each list's 16x16 winner's rows as phase 0's bi-prediction probe fetched
+        // them, keyed by what was fetched: pm_ref = reference of list 0 | of list 1 << 8 (0xff: none held), pm_k0 / pm_k1 = x & 0xffff | y << 16 of the
+        // vector as ecfg carries it (before b_fetch's clamp: equal vectors clamp equally within a macroblock).  A candidate is served from the memo
+        // only when it compares equal to what is held; everything else fetches.
+        constexpr bool PMEMO = BS && !REF;
+        uint32_t pm_dl = 0, pm_dc = 0, pm_l0 = 0, pm_c0 = 0, pm_l1 = 0, pm_c1 = 0;
+        unsigned pm_ref = 0xffffu, pm_k0 = 0, pm_k1 = 0;
+        bool pm_dv = false;
         bool d_avail = true;             // the direct prediction exists (temporal direct: not when a co-located block's reference is out of reach)
         int bskip_cost = MB_COST_MAX, cost16direct = MB_COST_MAX, cost8d_0 = MB_COST_MAX, cost8d_1 = MB_COST_MAX, cost8d_2 = MB_COST_MAX, cost8d_3 = MB_COST_MAX, cost16bi = MB_COST_MAX;
         int cost8x8bi = MB_COST_MAX, cost16x8bi = MB_COST_MAX, cost8x16bi = MB_COST_MAX;
@@ -2068,6 +2116,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MB_WAVES_PER
         if constexpr (BS) { \
             uni_all(euse, d_avail, bskip_cost, cost16direct, cost8d_0, cost8d_1, cost8d_2, cost8d_3, cost16bi, cost8x8bi, cost16x8bi, cost8x16bi); \
             uni_all(rd_dir, rd_l0, rd_l1, rd_bi, rd_8x8, rd_16x8, rd_8x16, sub8_0, sub8_1, sub8_2, sub8_3, p16x8_0, p16x8_1, p8x16_0, p8x16_1, b_type, b_part, b_use16, ds_t, ds_s); \
+            if constexpr (PMEMO) uni_all(pm_dv, pm_ref, pm_k0, pm_k1); \
         } \
         if constexpr (REF) { \
             uni_all(rf_on, rf_kind, rf_pk, rf_st, rf_part, rf_j, rf_i, rf_wait, rf_bmx, rf_bmy, rf_omx, rf_omy, rf_pmx, rf_pmy, rf_dir, rf_odir, rf_bsatd, rf_pmvchk); \
@@ -2427,7 +2476,20 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MB_WAVES_PER
             int mv0x = 0, mv0y = 0, ref0 = 0;
             if constexpr (BS) {
                 pf.begin2();
-                b_predict(k, c, ecfg, biwv, pred, cpred);
+                bool held = false;
+                uint32_t held_l = 0, held_c = 0;
+                if constexpr (PMEMO) {
+                    if (e_part == D_16x16 && euse == 0xffu) {          // the direct candidate (direct_cand: ecfg = dcfg)
+                        held = pm_dv; held_l = pm_dl; held_c = pm_dc;
+                    } else if (e_part == D_16x16 && e_type == X264GPU_MB_B_INTER) {          // one vector a list: every list in use against its key
+                        const int r0 = rl(ecfg.r0, 0), r1 = rl(ecfg.r1, 0);
+                        const unsigned k0 = ((unsigned)rl(ecfg.x0, 0) & 0xffffu) | ((unsigned)rl(ecfg.y0, 0) << 16), k1 = ((unsigned)rl(ecfg.x1, 0) & 0xffffu) | ((unsigned)rl(ecfg.y1, 0) << 16);
+                        held = (r0 < 0 || ((unsigned)r0 == (pm_ref & 0xffu) && k0 == pm_k0)) && (r1 < 0 || ((unsigned)r1 == (pm_ref >> 8) && k1 == pm_k1));
+                        if (held) b_combine(c, ecfg, biwv, pm_l0, pm_l1, pm_c0, pm_c1, held_l, held_c);
+                    }
+                }
+                if (held) { pf.count(29); pred = held_l; cpred = held_c; }          // (MB_PROF: encode-stage predictions served from the memo / fetched)
+                else { pf.count(31); b_predict(k, c, ecfg, biwv, pred, cpred); }
                 { const int tch = wave_sum((int)(pred & 1) + (int)(cpred & 1)); if (tch == 12345678) pf.count(30); }      // (MB_PROF: the prediction has arrived)
                 pf.mark2(24);
                 if (commit && (lane & 15) == 0) {      // one lane per 8x8 block writes that block's motion in both lists

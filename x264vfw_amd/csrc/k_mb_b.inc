@@ -145,6 +145,7 @@ for (;; rd_ph++) {
                 if (probed) { if (tmp) ds_t++; else ds_s++; }
             }
         }
+        if constexpr (PMEMO) { pm_dv = d_avail; pm_dl = dpred; pm_dc = dcpred; }          // (--direct auto: the slice's own mode is the last pass)
         // ---- B_SKIP when the direct prediction's distortion alone undercuts the cheapest coded macroblock ----
         bool try_skip = false;
         if constexpr (NORD) {
@@ -270,7 +271,17 @@ for (;; rd_ph++) {
             g.r0 = rl(S.ref, 0); g.x0 = rl(S.mvx, 0); g.y0 = rl(S.mvy, 0); g.r1 = rl(S.ref, 16); g.x1 = rl(S.mvx, 16); g.y1 = rl(S.mvy, 16);
             const int refc = rl(S.refcost, 0) + rl(S.refcost, 16);
             int cmv0 = rl(S.costmv, 0), cmv1 = rl(S.costmv, 16), csat;
-            cost16bi = bi_satd(g, 15u, csat) + refc + cmv0 + cmv1 + csat;
+            if constexpr (PMEMO) {
+                // the probe's trip to memory fills the memo: the L0, L1 and BI candidates and the winner's later encodes ask for these rows again
+                // (bi_satd(g, 15u, csat) with the rows kept)
+                uint32_t pred, cpred;
+                b_fetch(k, c, g, pm_l0, pm_l1, pm_c0, pm_c1);
+                pm_ref = ((unsigned)g.r0 & 0xffu) | (((unsigned)g.r1 & 0xffu) << 8);
+                pm_k0 = ((unsigned)g.x0 & 0xffffu) | ((unsigned)g.y0 << 16); pm_k1 = ((unsigned)g.x1 & 0xffffu) | ((unsigned)g.y1 << 16);
+                b_combine(c, g, biwv, pm_l0, pm_l1, pm_c0, pm_c1, pred, cpred);
+                csat = c.chroma_me ? wave_sum(lane < 32 ? cmp4(b_cenc, cpred) : 0) : 0;
+                cost16bi = wave_sum(cmp4(cz, pred)) + refc + cmv0 + cmv1 + csat;
+            } else cost16bi = bi_satd(g, 15u, csat) + refc + cmv0 + cmv1 + csat;
             if (g.x0 | g.y0 | g.x1 | g.y1) {
                 const int l0c = (int)c.cost_base[MVCOST_HALF - rl(S.mvpx, 0)] + (int)c.cost_base[MVCOST_HALF - rl(S.mvpy, 0)];
                 const int l1c = (int)c.cost_base[MVCOST_HALF - rl(S.mvpx, 16)] + (int)c.cost_base[MVCOST_HALF - rl(S.mvpy, 16)];

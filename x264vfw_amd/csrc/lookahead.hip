@@ -83,10 +83,13 @@ __global__ __launch_bounds__(256) void k_la_cost(LaK k)
         {   // median of the previous field: left, top, top-right (top-left when there is no top-right), oracle lookahead.c
             int a0 = 0, a1 = 0, b0 = 0, b1 = 0, c0 = 0, c1 = 0;
             const bool ia = bx > 0, ib = by > 0, ic = by > 0 && bx + 1 < k.bw;
-            if (ia && pin[bi - 1]) { a0 = pmv[2 * (bi - 1)]; a1 = pmv[2 * (bi - 1) + 1]; }
-            if (ib && pin[bi - k.bw]) { b0 = pmv[2 * (bi - k.bw)]; b1 = pmv[2 * (bi - k.bw) + 1]; }
-            if (ic) { if (pin[bi - k.bw + 1]) { c0 = pmv[2 * (bi - k.bw + 1)]; c1 = pmv[2 * (bi - k.bw + 1) + 1]; } }
-            else if (by > 0 && bx > 0 && pin[bi - k.bw - 1]) { c0 = pmv[2 * (bi - k.bw - 1)]; c1 = pmv[2 * (bi - k.bw - 1) + 1]; }
+            // (a block beyond an odd edge keeps the last block's index bi: in a picture one block wide or high its neighbours would lie in front of the
+            //  field — what it computes is dropped, but the read must stay inside; the blocks that count never reach the clamp)
+            const int ja = max(bi - 1, 0), jb = max(bi - k.bw, 0), jc = max(bi - k.bw + 1, 0), jd = max(bi - k.bw - 1, 0);
+            if (ia && pin[ja]) { a0 = pmv[2 * ja]; a1 = pmv[2 * ja + 1]; }
+            if (ib && pin[jb]) { b0 = pmv[2 * jb]; b1 = pmv[2 * jb + 1]; }
+            if (ic) { if (pin[jc]) { c0 = pmv[2 * jc]; c1 = pmv[2 * jc + 1]; } }
+            else if (by > 0 && bx > 0 && pin[jd]) { c0 = pmv[2 * jd]; c1 = pmv[2 * jd + 1]; }
             if (!ib && ia) { mvp0 = a0; mvp1 = a1; }
             else { mvp0 = median3(a0, b0, c0); mvp1 = median3(a1, b1, c1); }
         }
