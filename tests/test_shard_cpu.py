@@ -101,6 +101,63 @@ def test_device_cap_env_and_crf_across_devices():
     assert capped["sha"] == one["sha"] and sum(1 for c in capped["calls"] if c) == 1
 
 
+@pytest.mark.parametrize("n,seed,opts", [
+    (23, 7, {"qp": 27, "keyint": 4, "min-keyint": 4, "scenecut": 0, "ref": 2, "bframes": 0, "weightp": 0, "zones": "3,9,q=35"}),                         # I / P slots
+    (21, 11, {"qp": 27, "keyint": 8, "min-keyint": 8, "scenecut": 0, "ref": 2, "bframes": 2, "b-adapt": 0, "weightp": 0, "zones": "3,12,q=35"}),         # slots with B pictures
+])
+def test_gop_slots_look_zones_up_by_the_stream_index(n, seed, opts):
+    """a zone's quantiser reaches a slot's picture by the picture's display index in the STREAM (not in its batch, slot or GOP): 3 slots on 2 devices equal threads 1"""
+    serial = run_host(96, 80, n, seed, dict(opts, threads=1), 1)
+    par = run_host(96, 80, n, seed, dict(opts, threads=3), 2)
+    assert par["frames"] == serial["frames"] == n
+    assert par["sha"] == serial["sha"] and par["meta"] == serial["meta"]
+
+
+_IP = {"qp": 27, "keyint": 4, "min-keyint": 4, "scenecut": 0, "ref": 2, "bframes": 0, "weightp": 0}
+_B = {"qp": 27, "scenecut": 0, "ref": 2, "bframes": 3, "b-adapt": 0, "weightp": 0}
+_CRF = {"crf": 26, "keyint": 4, "min-keyint": 4, "scenecut": 0, "no-mbtree": None, "threads": 4}
+# name -> (pictures, seed, options, stand-in devices): the GOP-slot sessions of the tests above, then the edges of the call sequence
+CALL_SESSIONS = {
+    "b_d2_t3_n23_k8": (23, 11, dict(_B, keyint=8, **{"min-keyint": 8}, threads=3), 2),
+    "b_d3_t4_n27_k9_weightp2": (27, 11, dict(_B, keyint=9, **{"min-keyint": 9}, weightp=2, ref=3, threads=4), 3),
+    "b_d2_t2_n21_k8_nopyramid": (21, 11, dict(_B, keyint=8, **{"min-keyint": 8, "b-pyramid": "none"}, bframes=2, threads=2), 2),
+    "b_d4_t4_n14_k6_temporal": (14, 11, dict(_B, keyint=6, **{"min-keyint": 6}, direct="temporal", threads=4), 4),
+    "b_d1_t2_n5_k12": (5, 11, dict(_B, keyint=12, **{"min-keyint": 12}, threads=2), 1),
+    "b_d2_t3_n41_k7_slices2": (41, 11, dict(_B, keyint=7, **{"min-keyint": 7}, bframes=1, slices=2, threads=3), 2),
+    "ip_d2_t4": (23, 7, dict(_IP, threads=4), 2),
+    "ip_d3_t5": (23, 7, dict(_IP, threads=5), 3),
+    "ip_d2_t2": (23, 7, dict(_IP, threads=2), 2),
+    "ip_d4_t3": (23, 7, dict(_IP, threads=3), 4),
+    "crf_d1": (16, 3, _CRF, 1),
+    "crf_d2": (16, 3, _CRF, 2),
+    "zones_ip": (23, 7, dict(_IP, zones="3,9,q=35", threads=3), 2),
+    "zones_b": (21, 11, dict(_B, keyint=8, **{"min-keyint": 8}, bframes=2, zones="3,12,q=35", threads=3), 2),
+    "no_pictures": (0, 7, dict(_IP, threads=2), 2),                     # a flush call and nothing else
+    "one_full_batch": (8, 7, dict(_IP, threads=2), 2),                  # 2 slots x keyint 4: the flush finds the batch coded
+    "picture_after_flush": (10, 7, dict(_IP, threads=2, late=1), 2),    # refused (< 0, said in the log); the flush calls behind it keep draining
+}
+
+
+@pytest.mark.parametrize("name", sorted(CALL_SESSIONS))
+def test_gop_slot_sessions_answer_every_call_as_the_parent_did(name):
+    """tests/golden/gop_slots_parent_calls.json: tests/stub/run_host_calls.py's line for each of CALL_SESSIONS — every x264_encoder_encode's return value,
+    x264_encoder_delayed_frames after it, the log, the stream's and the metadata's hashes — recorded with the stand-in build of the commit before the GOP
+    slots became host/gopslots.cpp.  Serial-against-slots comparisons cannot see a change in WHEN a picture leaves or in what the session says; this does"""
+    gold = json.load(open(os.path.join(HERE, "golden", "gop_slots_parent_calls.json")))
+    assert sorted(gold) == sorted(CALL_SESSIONS)
+    n, seed, opts, devices = CALL_SESSIONS[name]
+    env = dict(os.environ, X264GPU_STUB_DEVICES=str(devices))
+    env.pop("X264GPU_DEVICES", None)
+    args = [sys.executable, os.path.join(HERE, "stub", "run_host_calls.py"), "96", "80", str(n), str(seed)] + [k if v is None else f"{k}={v}" for k, v in opts.items()]
+    out = subprocess.run(args, env=env, capture_output=True, timeout=600)
+    assert out.returncode == 0, out.stderr.decode()[-2000:]
+    got = json.loads(out.stdout.decode().strip().splitlines()[-1])
+    for key in ("rets", "delayed", "log", "sha", "meta"):
+        assert got[key] == gold[name][key], (name, key, got[key], gold[name][key])
+    if name == "picture_after_flush":
+        assert sum(1 for r in got["rets"] if r < 0) == 1 and any("pictures after a flush" in text for lvl, text in got["log"] if lvl == 0)
+
+
 def _free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))

@@ -8,6 +8,7 @@
 #include "host.hpp"
 #include "dpb.hpp"
 #include "batch.hpp"
+#include "gopslots.hpp"
 #include "quality.hpp"
 #include "ratecontrol.hpp"
 #include "slicetype.hpp"
@@ -25,8 +26,6 @@
 #include <chrono>
 #include <mutex>
 #include <condition_variable>
-
-#include <functional>
 
 using namespace x264host;
 
@@ -93,50 +92,17 @@ struct x264_t {
     std::thread gpu_thread;
     int gpu_rc = 0;                      // result of the GPU stage in flight
     int device = 0;
-    std::vector<float> gop_qpm;          // ... and its float quantiser (x264 rc->qpm)
-    std::vector<int8_t> gop_qp;          // GOP-parallel CRF: the quantiser of every ring picture (slot * keyint + position), decided on arrival
-    float last_qpm = 0.f;                // ... and its float quantiser as the device got it (x264 rc->qpm; 0 = the integer one)
     int last_qp = 0, last_scenecut = 0;  // diagnostics: quantiser and scenecut flag of the last coded picture
+    float last_qpm = 0.f;                // ... and its float quantiser as the device got it (x264 rc->qpm; 0 = the integer one)
     int32_t last_costs[4] = { 0, 0, 0, 0 };
-    // ---- GOP-parallel mode (--threads G > 1): G closed GOPs of the one stream are coded in lock-step on G stream slots of the
-    //      GPU encoder; frames come out in order, (G-1)*keyint calls late.  Fixed keyint + CQP make the GOPs independent, so
-    //      the bytes equal the serial encode's (tests/test_gpu_host.py::test_gop_parallel_equals_serial).
-    int G = 1;
+    int G = 1;                    // --threads G: GOP slots (1: none); G > 1 sessions run through `gops` alone
+    GopSlots gops;                // host/gopslots.hpp: G closed GOPs of the stream in lock-step, dealt to the visible devices
     int slices = 1;               // x264 slice threads: slices per picture (own wavefront + own NAL each)
     int slices_plain = 0;         // ... or x264 --slices N: the same split, filtered across the boundaries, up to one slice per macroblock row
-    // The G slots are dealt to the visible devices (slot s -> device s % D, its local slot s / D): every device runs its slots in lock-step
-    // with its own encoder, ring and download buffers, issued by one host thread per device; closed GOPs are independent, so there is no
-    // exchange between devices and the frames still leave in stream order (north star: "frames of one stream shard one-per-GPU").
-    struct DevCtx {
-        int dev = 0, nsl = 0, base = 0;  // device ordinal; slots it owns; its first row in the host download buffers
-        x264gpu_encoder *gpu = nullptr;
-        uint8_t *d_ring = nullptr;       // [keyint positions][nsl slots] tight I420 pictures of the batch being gathered
-        x264gpu_mb *d_mb = nullptr; int16_t *d_lv = nullptr;
-    };
-    std::vector<DevCtx> devs;            // GOP-parallel mode only (threads 1 sessions use gpu / d_mb / d_lv below on the caller's device)
-    long submitted = 0, emitted = 0;     // frames in / out
-    int next_pos = 0;                    // first position of the current batch not yet coded
-    bool flushed = false;                // the partly gathered batch has been coded (flush calls only drain after that)
-    bool failed = false;                 // GOP-parallel mode: a GPU call failed; the session only returns errors from now on
+    bool failed = false;                 // a GPU call failed; the session only returns errors from now on
     std::string gpu_err;                 // threads 1, pipelined: the helper thread's x264gpu_last_error() text (that buffer is thread-local)
-    struct Coded { std::vector<uint8_t> bytes; std::vector<size_t> off; std::vector<int> types; int idr; int ref_idc = -1, i_type = 0, disp = -1; };      // (ref_idc / i_type / disp: GOP slots with B pictures — a slot index is a CODING position there)
-    std::deque<Coded> ready;             // coded frames [emitted, emitted + ready.size())
-    std::deque<int64_t> pts;             // pts of frames not yet emitted
-    std::vector<Coded> slotbuf;          // G x keyint frames of the batch being coded (index slot * keyint + pos)
-    std::vector<uint8_t> slot_have;      // which of them are coded AND joined (written by the calling thread only)
-    int pool_t = -1, pool_nslots = 0, pool_slot0 = 0;    // position / slot count / first slot the running CAVLC threads are coding
-    // ---- GOP slots with B pictures (--threads G --bframes N under a constant quantiser): every slot is a closed GOP on the DPB model; the slots run the
-    //      same plan in lock-step (--b-adapt 0, no scenecut: picture c of the coding order has the same type, lists and marking in every GOP), a
-    //      mini-GOP is coded once the batch's last GOP has delivered its closing picture; the stream's last, shorter GOP is coded alone at the flush.
-    //      Frames leave in CODING order with x264's pts / dts, byte-identical to the threads-1 session (tests/test_shard_cpu.py).
-    bool gopb = false;
-    std::vector<std::pair<int, int>> gorder;      // coding order of a full GOP: (display index in the GOP, PIC_*)
-    int gb_next = 0;                              // next coding position of the batch being gathered
-    struct GopDpb { Dpb dpb; int l0ref0poc[8] = { 0 }; } gdpb;
-    std::vector<std::thread> pool;       // CAVLC threads of the position coded last: they overlap the GPU work of the next one
-    std::vector<x264gpu_mb> h_mb2;       // second download buffers (the pool reads one pair while the next position lands in the other)
+    std::vector<x264gpu_mb> h_mb2;       // pipelined sessions: second download buffers (one picture's land while the one before is coded)
     std::vector<int16_t> h_lv2;
-    int dl = 0;                          // download buffer in use for the NEXT position
     // ---- sessions with B pictures (threads 1; x264 --bframes N --b-pyramid): the picture types and the coding order come from host/slicetype.hpp, the DPB, the
     //      reference lists and the slice header's share of them from host/dpb.hpp ----
     int bframes = 0, bpyramid = 0, log2_max_poc_lsb = 0;
@@ -191,25 +157,6 @@ static int cavlc_threads_default(int dflt)
 {
     const char *e = getenv("X264GPU_CAVLC_THREADS");
     return clampi(e ? atoi(e) : dflt, 1, 64);
-}
-
-// Coding order of a closed GOP of n pictures under --b-adapt 0 (x264_slicetype_decide with a fixed pattern, as bmode_decide walks it for a session
-// without lookahead): an IDR picture, then runs of `bframes` B pictures closed by a P picture, the last picture always P; each closing picture first,
-// then under --b-pyramid the middle B of a run of two or more as a reference, then the other B pictures in display order.
-static std::vector<std::pair<int, int>> gop_coding_order(int n, int bframes, int bpyramid)
-{
-    std::vector<std::pair<int, int>> out;
-    std::vector<int> run;
-    for (int i = 0; i < n; i++) {
-        const bool closes = i == 0 || (int)run.size() == bframes || i == n - 1;
-        if (!closes) { run.push_back(i); continue; }
-        out.push_back({ i, i == 0 ? PIC_IDR : PIC_P });
-        const int j = (int)run.size(), bref = bpyramid && j > 1 ? (j - 1) / 2 : -1;
-        if (bref >= 0) out.push_back({ run[(size_t)bref], PIC_BREF });
-        for (int q = 0; q < j; q++) if (q != bref) out.push_back({ run[(size_t)q], PIC_B });
-        run.clear();
-    }
-    return out;
 }
 
 static int pick_level(const x264_param_t *p, int mbs, int refs)
@@ -628,15 +575,7 @@ static x264gpu_config open_device_config(x264_t *h)
 {
     x264_param_t &p = h->param;
     x264gpu_config cfg = {};
-    // GOP-parallel factor: bounded by the device ring (keyint x G pictures) staying under 24 GB
-    h->G = p.i_threads;
-    {
-        const double pic = (double)p.i_width * p.i_height * 1.5;
-        while (h->G > 1 && pic * h->keyint * h->G > 24e9) h->G--;
-        if (h->keyint >= (1 << 20)) h->G = 1;                  // "infinite" keyint: nothing to run in parallel
-        if (h->G != p.i_threads) xlog(&p, X264_LOG_INFO, "threads %d -> %d (GOP ring of keyint %d pictures)\n", p.i_threads, h->G, h->keyint);
-        p.i_threads = h->G;
-    }
+    h->G = GopSlots::fit(p, h->keyint);
     cfg.width = p.i_width; cfg.height = p.i_height; cfg.streams = h->G; cfg.refs = p.i_frame_reference; cfg.slices = h->slices; cfg.slices_plain = h->slices_plain; cfg.cabac = p.b_cabac;
     cfg.qp_i = h->qp_i; cfg.qp_p = h->qp_p; cfg.me_range = p.analyse.i_me_range; cfg.subme = p.analyse.i_subpel_refine;
     cfg.deblock = p.b_deblocking_filter; cfg.deblock_alpha = p.i_deblocking_filter_alphac0; cfg.deblock_beta = p.i_deblocking_filter_beta;
@@ -688,25 +627,17 @@ static bool open_device(x264_t *h)
     h->ql.open(p, h->G > 1);          // --psnr / --ssim: from here on h->ql.flags says whether the session computes them
     bool ok_setup = x264gpu_malloc((void **)&h->d_in, insz) == X264GPU_OK;
     if (ok_setup && h->G > 1) {
-        // GOP-parallel: the slots are dealt to the devices (X264GPU_DEVICES caps how many are used)
-        int D = x264gpu_device_count();
-        if (const char *de = getenv("X264GPU_DEVICES")) { const int v = atoi(de); if (v >= 1 && v < D) D = v; }
-        D = clampi(D, 1, h->G);
-        h->devs.resize((size_t)D);
-        int base = 0;
-        for (int d = 0; d < D && ok_setup; d++) {
-            x264_t::DevCtx &dc = h->devs[(size_t)d];
-            dc.dev = D == 1 ? h->device : d; dc.nsl = (h->G - d + D - 1) / D; dc.base = base; base += dc.nsl;
-            cfg.streams = dc.nsl;
-            ok_setup = x264gpu_set_device(dc.dev) == X264GPU_OK && x264gpu_encoder_create(&dc.gpu, &cfg) == X264GPU_OK &&
-                       x264gpu_malloc((void **)&dc.d_mb, (size_t)dc.nsl * h->nmb * sizeof(x264gpu_mb)) == X264GPU_OK &&
-                       x264gpu_malloc((void **)&dc.d_lv, (size_t)dc.nsl * h->nmb * X264GPU_MB_LEVELS * sizeof(int16_t)) == X264GPU_OK &&
-                       x264gpu_malloc((void **)&dc.d_ring, (size_t)dc.nsl * h->keyint * insz) == X264GPU_OK;
-        }
-        const std::string err = ok_setup ? "" : x264gpu_last_error();
-        (void)x264gpu_set_device(h->device);
-        if (!ok_setup) { xlog(&p, X264_LOG_ERROR, "GPU encoder setup failed: %s\n", err.c_str()); return false; }
-        if (D > 1) xlog(&p, X264_LOG_INFO, "GOP slots on %d devices (%d + ... per device)\n", D, h->devs[0].nsl);
+        // the access unit of a slot's picture (a pool thread of the unit's): AUD, the sets in front of an IDR picture (the SEI in the stream's first GOP only), the slices
+        const x264_t *ch = h;
+        auto write_coded = [ch](GopSlots::Coded &cd, int pic_type, long gop, SliceParams sp, const x264gpu_mb *mb, const int16_t *lv) {
+            cd.bytes.clear(); cd.off.clear(); cd.types.clear();
+            cd.idr = pic_type == PIC_IDR; cd.i_type = x264_type_of(pic_type);
+            begin_access_unit(ch, cd.bytes, cd.off, cd.types, pic_type, gop == 0);
+            sp.idr_pic_id = (int)(gop & 0xffff);
+            write_slices(cd.bytes, cd.off, cd.types, sp, ch->slices, mb, lv, ch->param.b_annexb != 0, cd.idr, nullptr, 1);
+        };
+        return h->gops.open(p, cfg, h->rc, { h->G, h->keyint, h->nmb, h->qp_i, h->qp_p, h->bframes, h->bpyramid, h->weightp, h->log2_max_frame_num, h->direct_mode, h->dpbmode,
+                                             h->device, slice_params_base(h), write_coded });
     } else if (ok_setup && h->batch.want) {
         ok_setup = h->batch.join(cfg, h->batch.want, insz, (size_t)h->nmb, h->ql.flags);
         if (ok_setup) xlog(&p, X264_LOG_INFO, "X264GPU_BATCH: stream %d of a batch of %d sessions%s\n", h->batch.index(), h->batch.size(), h->batch.queued() ? " (rounds queued: uploads overlap the device)" : "");
@@ -811,7 +742,7 @@ static bool open_lookahead(x264_t *h)
     return true;
 }
 
-// host buffers and the GOP slots' bookkeeping
+// host buffers
 static void open_host_buffers(x264_t *h)
 {
     x264_param_t &p = h->param;
@@ -819,21 +750,9 @@ static void open_host_buffers(x264_t *h)
     { const unsigned hw = std::thread::hardware_concurrency(); h->cavlc_threads = h->G > 1 ? 1 : cavlc_threads_default(hw >= 32 ? 16 : hw >= 16 ? 8 : hw >= 4 ? (int)hw / 2 : 1); }
     h->h_in.resize(insz);
     // (a batch session whose pictures are downloaded and coded by its helper threads keeps the records in the two deferred slots instead: 7 MB less to clear per open)
-    if (!h->batch.overlap()) { h->h_mb.resize((size_t)h->G * h->nmb); h->h_lv.resize((size_t)h->G * h->nmb * X264GPU_MB_LEVELS); }
+    // (... and GOP slots own their download buffers)
+    if (!h->batch.overlap() && h->G == 1) { h->h_mb.resize((size_t)h->nmb); h->h_lv.resize((size_t)h->nmb * X264GPU_MB_LEVELS); }
     if (h->pipeline) { h->h_mb2.resize(h->h_mb.size()); h->h_lv2.resize(h->h_lv.size()); }
-    if (h->G > 1) {
-        const size_t n = (size_t)h->G * h->keyint;
-        h->gop_qp.assign(n, (int8_t)h->qp_p); h->gop_qpm.assign(n, 0.f);
-        h->slotbuf.resize(n);
-        h->slot_have.assign(n, 0);
-        h->h_mb2.resize(h->h_mb.size()); h->h_lv2.resize(h->h_lv.size());
-        if (h->dpbmode) {
-            h->gopb = true;
-            h->gorder = gop_coding_order(h->keyint, h->bframes, h->bpyramid);
-            h->gdpb.dpb.configure(p.i_frame_reference, h->bframes, h->bpyramid, h->log2_max_frame_num, h->weightp);
-            xlog(&p, X264_LOG_INFO, "%d GOP slots in lock-step with B pictures (bframes %d, b-pyramid %d, constant quantiser): pictures leave in coding order, %d calls late\n", h->G, h->bframes, h->bpyramid, (h->G - 1) * h->keyint + h->bframes + 1);
-        }
-    }
 }
 
 x264_t *x264_encoder_open(x264_param_t *param)
@@ -898,289 +817,26 @@ int x264_encoder_headers(x264_t *h, x264_nal_t **pp_nal, int *pi_nal)
     return (int)h->out.size();
 }
 
-// the float quantiser as the device takes it: beside its rounding (a quantiser clipped into 1..51 from outside has no fraction to carry: 0 = the integer one)
-static float near_qpm(double qpf, int qp) { const float f = (float)qpf; return f > (float)qp - 1.f && f < (float)qp + 1.f ? f : 0.f; }
-// ---- GOP-parallel mode ------------------------------------------------------------------------------------------------
-// Frame i of the stream belongs to GOP g = i / keyint at position t = i % keyint; GOP g runs on slot g % G of batch g / G.
-// Pictures are uploaded into a position-major device ring, so the G pictures of one position are contiguous = one
-// x264gpu_encode_frames call.  A position is coded when the batch's last GOP delivers it (or at flush with the slots that
-// exist); the G slices are entropy-coded by a thread each.  Frames leave in stream order, one per call.
-static void join_pool(x264_t *h)
+// ---- --threads G > 1 (host/gopslots.hpp): the picture goes to the slots, or the input has ended; then the next coded picture in output order, if there is one ----
+static int encode_gop_slots(x264_t *h, x264_nal_t **pp_nal, int *pi_nal, x264_picture_t *pic_in, x264_picture_t *pic_out, bool resident)
 {
-    for (auto &th : h->pool) th.join();
-    h->pool.clear();
-    // only now do the frames of that position count as coded (the workers never touch the bookkeeping)
-    for (int s = h->pool_slot0; s < h->pool_slot0 + h->pool_nslots; s++) h->slot_have[(size_t)s * h->keyint + h->pool_t] = 1;
-    h->pool_nslots = 0; h->pool_slot0 = 0;
-}
-
-// One coding position of the slots [slot0, slot0 + nslots) on the devices: launch(dc, d) issues device d's encode call for its slots (false: it failed), the
-// records and levels of those slots then land in the download buffers not in use — on the caller's thread when there is one device, else on a host thread per
-// device (the error text is per thread: the first per device is kept).  The CAVLC pool of the position before is joined, it read the other pair.
-// owners_only: devices that own none of the slots sit the position out (GOP slots with B pictures; the I / P mode launches every device).
-// 0 and the buffers the position landed in, or -1 after a GPU failure (the session is then dead: h->failed)
-static int run_devices(x264_t *h, int slot0, int nslots, bool owners_only, const std::function<bool(x264_t::DevCtx &, int)> &launch, x264gpu_mb **hmb_out, int16_t **hlv_out)
-{
-    x264gpu_mb *hmb = h->dl ? h->h_mb2.data() : h->h_mb.data();
-    int16_t *hlv = h->dl ? h->h_lv2.data() : h->h_lv.data();
-    h->dl ^= 1;
-    const int D = (int)h->devs.size();
-    std::vector<std::string> errs((size_t)D);
-    auto run_dev = [&](int d) {
-        x264_t::DevCtx &dc = h->devs[(size_t)d];
-        bool mine = !owners_only;
-        for (int s = slot0; s < slot0 + nslots; s++) mine |= s % D == d;
-        if (!mine) return;                                     // (the stream's last, shorter GOP is coded alone: only its device runs)
-        const bool ok = (D == 1 || x264gpu_set_device(dc.dev) == X264GPU_OK) && launch(dc, d) &&
-                        x264gpu_memcpy_d2h(hmb + (size_t)dc.base * h->nmb, dc.d_mb, (size_t)dc.nsl * h->nmb * sizeof(x264gpu_mb), nullptr) == X264GPU_OK &&
-                        x264gpu_memcpy_d2h(hlv + (size_t)dc.base * h->nmb * X264GPU_MB_LEVELS, dc.d_lv, (size_t)dc.nsl * h->nmb * X264GPU_MB_LEVELS * sizeof(int16_t), nullptr) == X264GPU_OK;
-        if (!ok) errs[(size_t)d] = std::string("device ") + std::to_string(dc.dev) + ": " + x264gpu_last_error();
-    };
-    if (D == 1) run_dev(0);
-    else {
-        std::vector<std::thread> ths;
-        for (int d = 0; d < D; d++) ths.emplace_back(run_dev, d);
-        for (auto &th : ths) th.join();
-    }
-    join_pool(h);
-    for (int d = 0; d < D; d++)
-        if (!errs[(size_t)d].empty()) {
-            xlog(&h->param, X264_LOG_ERROR, "x264_encoder_encode: GPU hot path failed: %s\n", errs[(size_t)d].c_str());
-            h->failed = true;
-            return -1;
-        }
-    *hmb_out = hmb; *hlv_out = hlv;
-    return 0;
-}
-
-// starts the CAVLC pool over the slots [slot0, slot0 + nslots) of position `pos`: work(s) writes slot s' access unit; the threads overlap the GPU work of the next position
-static void start_pool(x264_t *h, int pos, int slot0, int nslots, const std::function<void(int)> &work)
-{
-    const unsigned hw = std::thread::hardware_concurrency();
-    const int nthr = (int)(hw ? (hw < (unsigned)nslots ? hw : (unsigned)nslots) : 1);
-    h->pool_t = pos; h->pool_nslots = nslots; h->pool_slot0 = slot0;
-    for (int th = 0; th < nthr; th++)
-        h->pool.emplace_back([work, th, nthr, slot0, nslots]() { for (int s = slot0 + th; s < slot0 + nslots; s += nthr) work(s); });
-}
-
-// the access unit of GOP `gop`'s picture in `cd` (a pool thread): AUD, the sets in front of an IDR picture (the SEI in the stream's first GOP only), the slices
-static void write_coded(const x264_t *h, x264_t::Coded &cd, int pic_type, long gop, SliceParams sp, const x264gpu_mb *mb, const int16_t *lv)
-{
-    cd.bytes.clear(); cd.off.clear(); cd.types.clear();
-    cd.idr = pic_type == PIC_IDR;
-    begin_access_unit(h, cd.bytes, cd.off, cd.types, pic_type, gop == 0);
-    sp.idr_pic_id = (int)(gop & 0xffff);
-    write_slices(cd.bytes, cd.off, cd.types, sp, h->slices, mb, lv, h->param.b_annexb != 0, cd.idr, nullptr, 1);
-}
-
-// GOP slots with B pictures: coding position c of `order` for the slots [slot0, slot0 + nslots) of batch `batch` — the plan from the DPB model (the
-// same for every slot), one x264gpu_encode_pictures per device that owns one of the slots, the slices written by the pool while the next position runs.
-// 0, or -1 after a GPU failure (the session is then dead, as in code_position).
-static int code_position_b(x264_t *h, int batch, int c, int slot0, int nslots, const std::vector<std::pair<int, int>> &order, x264_t::GopDpb &gd)
-{
-    const x264_param_t &p = h->param;
-    const size_t insz = (size_t)p.i_width * p.i_height * 3 / 2;
-    const int G = h->G, K = h->keyint, disp = order[(size_t)c].first, type = order[(size_t)c].second;
-    // the disposable pictures coded right behind this one (x264_reference_hierarchy_reset looks at them)
-    int fc[16], ff[16], nf = 0;
-    for (size_t i = (size_t)c + 1; i < order.size() && nf < 16 && order[i].second == PIC_B; i++) { fc[nf] = (int)i; ff[nf] = order[i].first; nf++; }
-    const DpbPlan plan = gd.dpb.plan(type, disp, nf, fc, ff, nullptr);
-    x264gpu_pic pic = plan.pic;
-    if ((type == PIC_B || type == PIC_BREF) && h->direct_mode == 2) {
-        // x264 slice_header_init: temporal direct prediction only when the co-located picture's reference 0 is this picture's reference 0
-        const bool temporal = pic.nref[0] && pic.nref[1] && gd.l0ref0poc[pic.slot[1][0]] == plan.list_poc[0][0];
-        pic.direct_temporal = temporal; pic.direct_auto = 0;
-        gd.dpb.set_direct(pic.direct_temporal, 0);
-    }
-    if (plan.nal_ref_idc) gd.l0ref0poc[pic.dst] = pic.nref[0] ? plan.list_poc[0][0] : INT_MIN;
-    // constant quantiser by picture type, a zone shifts it by the picture's display index in the stream (a slot coded along and thrown away: the type's)
-    std::vector<int> qps((size_t)G, h->rc.qp_constant[type]);
-    for (int s = slot0; s < slot0 + nslots; s++) qps[(size_t)s] = h->rc.start(type, (int)(((long)batch * G + s) * K + disp));
-    SliceParams sp = slice_params_base(h);
-    gd.dpb.fill(sp);
-    gd.dpb.commit();
-    const int D = (int)h->devs.size();
-    x264gpu_mb *hmb; int16_t *hlv;
-    auto launch = [&](x264_t::DevCtx &dc, int d) {
-        std::vector<x264gpu_pic> pics((size_t)dc.nsl, pic);
-        for (int l = 0; l < dc.nsl; l++) pics[(size_t)l].qp = qps[(size_t)(l * D + d)];
-        return x264gpu_encode_pictures(dc.gpu, dc.d_ring + (size_t)disp * dc.nsl * insz, pics.data(), dc.d_mb, dc.d_lv, nullptr) == X264GPU_OK;
-    };
-    if (run_devices(h, slot0, nslots, true, launch, &hmb, &hlv) < 0) return -1;
-    const int ref_idc = plan.nal_ref_idc;
-    start_pool(h, c, slot0, nslots, [h, batch, c, disp, type, hmb, hlv, qps, D, sp, ref_idc](int s) {
-        const size_t row = (size_t)h->devs[(size_t)(s % D)].base + (size_t)(s / D);
-        x264_t::Coded &cd = h->slotbuf[(size_t)s * h->keyint + c];
-        cd.ref_idc = ref_idc; cd.disp = disp; cd.i_type = x264_type_of(type);
-        SliceParams sps = sp;
-        sps.qp = qps[(size_t)s];
-        write_coded(h, cd, type, (long)batch * h->G + s, sps, hmb + row * h->nmb, hlv + row * h->nmb * X264GPU_MB_LEVELS);
-    });
-    return 0;
-}
-
-// 0, or -1 after a GPU failure: the session is then dead (h->failed: every later call returns < 0 and nothing counts as delayed,
-// so the caller's flush loop — codec.c:1842-1856 — ends instead of spinning on frames that will never be coded)
-static int code_position(x264_t *h, int batch, int t, int nslots_with_t)
-{
-    const x264_param_t &p = h->param;
-    const size_t insz = (size_t)p.i_width * p.i_height * 3 / 2;
-    const int st = t == 0 ? X264GPU_SLICE_I : X264GPU_SLICE_P, G = h->G;
-    std::vector<int8_t> qps; std::vector<float> qpms;
-    if (h->rc.crf || (!h->rc.abr && !h->rc.zones.empty())) {
-        // CRF: decided when the pictures arrived; constant quantiser with zones: slot s of this batch holds picture (batch * G + s) * keyint + t of the stream
-        qps.assign((size_t)G, (int8_t)(t == 0 ? h->qp_i : h->qp_p)); qpms.assign((size_t)G, 0.f);
-        for (int s = 0; s < nslots_with_t; s++)
-            if (h->rc.crf) { qps[(size_t)s] = h->gop_qp[(size_t)s * h->keyint + t]; qpms[(size_t)s] = h->gop_qpm[(size_t)s * h->keyint + t]; }
-            else qps[(size_t)s] = (int8_t)h->rc.start(t == 0 ? PIC_IDR : PIC_P, (int)(((long)batch * G + s) * h->keyint + t));
-    }
-    // every device codes position t of its slots: GPU + download run while the CAVLC threads of the previous position are still coding from the other buffer pair
-    const int D = (int)h->devs.size();
-    x264gpu_mb *hmb; int16_t *hlv;
-    auto launch = [&](x264_t::DevCtx &dc, int d) {
-        if (!qps.empty()) {
-            std::vector<int8_t> q((size_t)dc.nsl); std::vector<float> qm((size_t)dc.nsl);
-            for (int l = 0; l < dc.nsl; l++) { q[(size_t)l] = qps[(size_t)(l * D + d)]; qm[(size_t)l] = qpms[(size_t)(l * D + d)]; }
-            if (x264gpu_encoder_set_stream_qpms(dc.gpu, q.data(), qm.data()) != X264GPU_OK) return false;
-        }
-        return x264gpu_encode_frames(dc.gpu, dc.d_ring + (size_t)t * dc.nsl * insz, st, dc.d_mb, dc.d_lv, nullptr) == X264GPU_OK;
-    };
-    if (run_devices(h, 0, nslots_with_t, false, launch, &hmb, &hlv) < 0) return -1;
-    start_pool(h, t, 0, nslots_with_t, [h, batch, t, st, hmb, hlv, qps, D](int s) {
-        const x264_param_t &p = h->param;
-        const size_t row = (size_t)h->devs[(size_t)(s % D)].base + (size_t)(s / D);       // where slot s landed in the download buffers
-        const bool idr = t == 0;
-        SliceParams sp = slice_params_base(h);
-        sp.slice_type = st; sp.qp = !qps.empty() ? (int)qps[(size_t)s] : idr ? h->qp_i : h->qp_p;
-        sp.frame_num = t & ((1 << h->log2_max_frame_num) - 1); sp.idr = idr; sp.nal_ref_idc = idr ? 3 : 2;
-        sp.num_ref = t < p.i_frame_reference ? (t > 0 ? t : 1) : p.i_frame_reference;
-        write_coded(h, h->slotbuf[(size_t)s * h->keyint + t], idr ? PIC_IDR : PIC_P, (long)batch * h->G + s, sp, hmb + row * h->nmb, hlv + row * h->nmb * X264GPU_MB_LEVELS);
-    });
-    return 0;
-}
-
-// coded frames move to the ordered output queue once every earlier frame is there.  slotbuf is indexed inside a batch
-// (slot * keyint + position); an entry is reused by the next batch only long after it was drained.
-static void drain_coded(x264_t *h)
-{
-    const long K = h->keyint, per_batch = (long)h->G * K;
-    for (long g = h->emitted + (long)h->ready.size(); g < h->submitted; g++) {
-        const long j = g % per_batch;
-        const size_t idx = (size_t)(j / K) * K + (size_t)(j % K);
-        if (!h->slot_have[idx]) break;                       // not coded yet (or its CAVLC threads have not been joined)
-        h->ready.push_back(std::move(h->slotbuf[idx]));
-        h->slot_have[idx] = 0;
-    }
-}
-
-static int encode_gop_parallel(x264_t *h, x264_nal_t **pp_nal, int *pi_nal, x264_picture_t *pic_in, x264_picture_t *pic_out, bool resident)
-{
-    const x264_param_t &p = h->param;
-    const int G = h->G, K = h->keyint;
-    const size_t insz = (size_t)p.i_width * p.i_height * 3 / 2;
-    const long per_batch = (long)G * K;
-    if (h->failed) return -1;
-    if (pic_in) {
-        if (h->flushed) { xlog(&p, X264_LOG_ERROR, "x264_encoder_encode: pictures after a flush are not supported in GOP-parallel mode\n"); return -1; }
-        const long i = h->submitted, b = i / per_batch, r = i % per_batch;
-        const int s = (int)(r / K), t = (int)(r % K);
-        // a new batch may only start gathering once the previous one is fully coded and drained into the output queue
-        const int D = (int)h->devs.size();
-        x264_t::DevCtx &dc = h->devs[(size_t)(s % D)];
-        uint8_t *dst = dc.d_ring + ((size_t)t * dc.nsl + (size_t)(s / D)) * insz;
-        const void *src = resident ? (const void *)h->d_in : (const void *)h->h_in.data();
-        if ((resident ? x264gpu_memcpy_d2d(dst, src, insz, nullptr) : x264gpu_memcpy_h2d(dst, src, insz, nullptr)) != X264GPU_OK) {
-            xlog(&p, X264_LOG_ERROR, "x264_encoder_encode: upload failed: %s\n", x264gpu_last_error());
-            return -1;
-        }
-        // the lookahead lives on the caller's device: with several devices the picture also goes to the staging buffer there
-        const uint8_t *la_src = dst;
-        if (h->rc.crf && D > 1 && dc.dev != h->device) {
-            if (!resident && x264gpu_memcpy_h2d(h->d_in, src, insz, nullptr) != X264GPU_OK) { xlog(&p, X264_LOG_ERROR, "x264_encoder_encode: upload failed: %s\n", x264gpu_last_error()); return -1; }
-            la_src = h->d_in;
-        }
-        if (h->rc.crf) {
-            // CRF: the picture's quantiser follows from the lookahead costs and the pictures before it, all known now (decided by its display index)
-            int32_t costs[4];
-            if (x264gpu_lookahead_frame_cost(h->la, la_src, i == 0, h->d_la, nullptr, nullptr) != X264GPU_OK ||
-                x264gpu_memcpy_d2h(costs, h->d_la, sizeof(costs), nullptr) != X264GPU_OK) {
-                xlog(&p, X264_LOG_ERROR, "x264_encoder_encode: lookahead failed: %s\n", x264gpu_last_error());
-                return -1;
-            }
-            double qpf;
-            h->gop_qp[(size_t)s * K + t] = (int8_t)h->rc.start(t == 0 ? PIC_IDR : PIC_P, (int)i, costs, nullptr, &qpf);
-            h->gop_qpm[(size_t)s * K + t] = near_qpm(qpf, h->gop_qp[(size_t)s * K + t]);
-        }
-        h->pts.push_back(pic_in->i_pts);
-        if (h->gopb) h->all_pts.push_back(pic_in->i_pts);
-        h->submitted++;
-        if (s == G - 1 && h->gopb) {
-            // every slot holds display picture t now: the coding positions whose picture (and, being in coding order behind their closing picture,
-            // whose references) have arrived
-            if (t == 0) { h->gb_next = 0; }
-            while (h->gb_next < K && h->gorder[(size_t)h->gb_next].first <= t) {
-                if (code_position_b(h, (int)b, h->gb_next, 0, G, h->gorder, h->gdpb) < 0) return -1;
-                h->gb_next++;
-            }
-            h->next_pos = t + 1 == K ? 0 : t + 1;
-        } else
-        if (s == G - 1) {                                      // the batch's last GOP delivers position t: every slot has it
-            if (code_position(h, (int)b, t, G) < 0) return -1;
-            h->next_pos = t + 1 == K ? 0 : t + 1;
-        } else if (!h->pool.empty()) join_pool(h);             // gathering phase: the last position's CAVLC had a whole call to finish
-        drain_coded(h);
-    } else {
-        // flush: code what the partly gathered batch holds, position by position, with the slots that have that position
-        const long i = h->submitted, b = i == 0 ? 0 : (i - 1) / per_batch, r = i - b * per_batch;    // r frames in the last batch
-        if (h->gopb && !h->flushed && r > 0 && !(r == per_batch && h->next_pos == 0)) {
-            // the complete GOPs finish their plan in lock-step; then the stream's last, shorter GOP alone: its own coding order on a DPB model of its own,
-            // from its IDR picture on (what the lock-step rounds coded of it while it was the batch's last slot is coded again: its tail differs)
-            const int full = (int)(r / K), part = (int)(r % K);
-            const bool last_ran = full == G - 1 && part > 0;          // (the partial GOP sat in the last slot: the rounds so far included it)
-            if (!last_ran) h->gb_next = 0;                            // the last slot never delivered: nothing of this batch has been coded yet
-            if (full > 0)
-                for (int c = h->gb_next; c < K; c++)
-                    if (code_position_b(h, (int)b, c, 0, full, h->gorder, h->gdpb) < 0) return -1;
-            if (part > 0) {
-                join_pool(h);
-                x264_t::GopDpb gp;
-                gp.dpb.configure(p.i_frame_reference, h->bframes, h->bpyramid, h->log2_max_frame_num, h->weightp);
-                const std::vector<std::pair<int, int>> po = gop_coding_order(part, h->bframes, h->bpyramid);
-                for (int c = 0; c < part; c++) { h->slot_have[(size_t)full * K + c] = 0; }
-                for (int c = 0; c < part; c++)
-                    if (code_position_b(h, (int)b, c, full, 1, po, gp) < 0) return -1;
-            }
-            h->gb_next = 0; h->next_pos = 0;
-        } else
-        if (!h->flushed && r > 0 && !(r == per_batch && h->next_pos == 0)) {
-            const int full = (int)(r / K), part = (int)(r % K);            // `full` complete GOPs, then `part` frames
-            for (int t = h->next_pos; t < K; t++) {
-                const int nslots = full + (t < part ? 1 : 0);
-                if (nslots <= 0) break;
-                if (code_position(h, (int)b, t, nslots) < 0) return -1;
-            }
-            h->next_pos = 0;
-        }
-        h->flushed = true;
-        join_pool(h);
-        drain_coded(h);
-    }
-    if (h->ready.empty()) return 0;
-    // ---- emit frame h->emitted ----
-    x264_t::Coded c = std::move(h->ready.front());
-    h->ready.pop_front();
+    GopSlots &gs = h->gops;
+    const int rc = pic_in ? gs.put({ h->h_in.data(), h->d_in, resident, h->la, h->d_la }, pic_in->i_pts) : gs.flush();
+    h->failed |= gs.failed;
+    if (rc < 0) return -1;
+    if (pic_in && gs.with_b()) h->all_pts.push_back(pic_in->i_pts);
+    GopSlots::Coded c;
+    if (!gs.pop(c)) return 0;
     h->out = std::move(c.bytes);
     h->nal_off = c.off;
     publish_nals(h, pp_nal, pi_nal, c.types);
-    if (h->gopb) for (size_t i = 0; i < h->nals.size(); i++) if (c.types[i] == 1 || c.types[i] == 5) h->nals[i].i_ref_idc = c.ref_idc;
-    if (h->gopb && pic_out) {
+    if (gs.with_b()) {
+        for (size_t i = 0; i < h->nals.size(); i++) if (c.types[i] == 1 || c.types[i] == 5) h->nals[i].i_ref_idc = c.ref_idc;
         // coding order: the picture's own pts (its display place in its GOP) and x264's dts
-        const long k = h->emitted, gop_base = k - k % K;
+        const long k = c.index, gop_base = k - k % h->keyint;
         const size_t np = h->all_pts.size(), di = (size_t)(gop_base + c.disp);
         fill_pic_out(pic_out, c.i_type, c.idr, h->all_pts[di < np ? di : np - 1], coded_dts(h, k), nullptr);
-    } else fill_pic_out(pic_out, c.idr ? X264_TYPE_IDR : X264_TYPE_P, c.idr, h->pts.front(), h->pts.front(), nullptr);
-    h->pts.pop_front();
-    h->emitted++;
+    } else fill_pic_out(pic_out, c.idr ? X264_TYPE_IDR : X264_TYPE_P, c.idr, c.pts, c.pts, nullptr);
     h->frame_no++;
     return (int)h->out.size();
 }
@@ -1683,7 +1339,7 @@ int x264_encoder_encode(x264_t *h, x264_nal_t **pp_nal, int *pi_nal, x264_pictur
     *pi_nal = 0; *pp_nal = nullptr;
     if (h->failed) return -1;
     if (!pic_in) {      // flush: GOP-parallel batches, or the pictures still waiting in the lookahead queue, one per call
-        if (h->G > 1) return encode_gop_parallel(h, pp_nal, pi_nal, nullptr, pic_out, false);
+        if (h->G > 1) return encode_gop_slots(h, pp_nal, pi_nal, nullptr, pic_out, false);
         if (h->dpbmode) return h->inflight > 1 ? encode_bmode_inflight(h, pp_nal, pi_nal, pic_out, true) : encode_bmode(h, pp_nal, pi_nal, pic_out, true);
         return h->queue.empty() ? 0 : encode_queued(h, pp_nal, pi_nal, pic_out, true);
     }
@@ -1706,7 +1362,7 @@ int x264_encoder_encode(x264_t *h, x264_nal_t **pp_nal, int *pi_nal, x264_pictur
         const uint8_t *src = pic_in->img.plane[pl];
         for (int y = 0; y < ph; y++, dst += pw, src += pic_in->img.i_stride[pl]) memcpy(dst, src, pw);
     }
-    if (h->G > 1) return encode_gop_parallel(h, pp_nal, pi_nal, pic_in, pic_out, resident);
+    if (h->G > 1) return encode_gop_slots(h, pp_nal, pi_nal, pic_in, pic_out, resident);
     PHASE(0);
     // ---- the picture enters the lookahead queue (x264_lookahead_put_frame): upload, frame cost against the previous source picture,
     //      AQ offsets, slice-type decision (keyint / forced type / scenecut) — all causal, so they are taken on arrival ----
@@ -1770,12 +1426,12 @@ int x264_encoder_encode(x264_t *h, x264_nal_t **pp_nal, int *pi_nal, x264_pictur
     return size;
 }
 
-int x264_encoder_delayed_frames(x264_t *h) { return !h || h->failed ? 0 : h->G > 1 ? (int)(h->submitted - h->emitted) : h->dpbmode ? h->slicetype.delayed() + (int)h->fl.size() + (h->defer[0].valid ? 1 : 0) + (h->defer[1].valid ? 1 : 0) : (int)h->queue.size(); }
+int x264_encoder_delayed_frames(x264_t *h) { return !h || h->failed ? 0 : h->G > 1 ? h->gops.delayed() : h->dpbmode ? h->slicetype.delayed() + (int)h->fl.size() + (h->defer[0].valid ? 1 : 0) + (h->defer[1].valid ? 1 : 0) : (int)h->queue.size(); }
 
 void x264_encoder_close(x264_t *h)
 {
     if (!h) return;
-    join_pool(h);
+    h->gops.close();
     join_gpu(h);
     for (auto &d : h->defer) join_deferred(h, d);
     if (getenv("X264GPU_HOST_TIMING") && h->t_phase[5] > 0)
@@ -1800,14 +1456,6 @@ void x264_encoder_close(x264_t *h)
     if (h->d_mb) x264gpu_free(h->d_mb);
     if (h->d_lv) x264gpu_free(h->d_lv);
     if (h->d_q) x264gpu_free(h->d_q);
-    for (auto &dc : h->devs) {
-        if (h->devs.size() > 1) (void)x264gpu_set_device(dc.dev);
-        if (dc.gpu) x264gpu_encoder_destroy(dc.gpu);
-        if (dc.d_mb) x264gpu_free(dc.d_mb);
-        if (dc.d_lv) x264gpu_free(dc.d_lv);
-        if (dc.d_ring) x264gpu_free(dc.d_ring);
-    }
-    if (h->devs.size() > 1) (void)x264gpu_set_device(h->device);
     for (void *blk : h->q_block) if (blk) x264gpu_free(blk);          // the queue's slots (source pictures, lookahead records, AQ and tree offsets) are cuts of these
     if (h->d_tree) x264gpu_free(h->d_tree);
     if (h->la) x264gpu_lookahead_destroy(h->la);

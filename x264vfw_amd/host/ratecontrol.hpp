@@ -96,4 +96,7 @@ private:
     double p2_pick_qscale(int frame) const;
 };
 
+// the float quantiser as the device takes it: beside its rounding (a quantiser clipped into 1..51 from outside has no fraction to carry: 0 = the integer one)
+inline float near_qpm(double qpf, int qp) { const float f = (float)qpf; return f > (float)qp - 1.f && f < (float)qp + 1.f ? f : 0.f; }
+
 }  // namespace x264host
