@@ -107,6 +107,12 @@ int x264gpu_trellis_blocks(const int16_t *d_coefs, int nblk, int cat, int qp, in
  * (or NULL) receives one byte per pass of eight blocks, bit 0 = the levels-of-one loop ran, bit 1 = on 32-bit scores (no such loop is built: always 0). */
 int x264gpu_trellis_blocks_ex(const int16_t *d_coefs, int nblk, int cat, int qp, int intra, const uint8_t *d_states460, int16_t *d_levels, uint8_t *d_nz, int force_general,
                               uint8_t *d_paths, void *stream);
+/* The search with x264's psy-trellis term (--psy-rd a:b; cfg.psy_trellis_q8): d_fenc_dct = the transform of the SOURCE block of every block (no prediction
+ * subtracted), in the layout and scan order of d_coefs; psy_trellis_q8 = x264's i_psy_trellis, 0..640.  In categories 1, 2 and 5, at scan positions above 0, a
+ * candidate level pays d * d * coef_weight2 - coef_weight1 * psy_trellis_q8 * |unquant_abs_level + SIGN(fenc_dct - coef, coef)|; categories 0, 3 and 4 and a
+ * strength of 0 give what x264gpu_trellis_blocks_ex gives (d_fenc_dct is then not read and may be NULL). */
+int x264gpu_trellis_blocks_psy(const int16_t *d_coefs, const int16_t *d_fenc_dct, int nblk, int cat, int qp, int intra, int psy_trellis_q8, const uint8_t *d_states460,
+                               int16_t *d_levels, uint8_t *d_nz, int force_general, uint8_t *d_paths, void *stream);
 int x264gpu_mc_weight(const uint8_t *d_src, size_t bytes, int scale, int denom, int offset, uint8_t *d_out, void *stream);
 /* The level walk of the CABAC size pricing as a primitive ([x264-upstream] encoder/cabac.c coeff_abs_level_minus1 of residual_block_cabac, every block of a
  * macroblock at once — csrc/cabac_rd.hip.h cab_levels_all): n cases; d_levels the macroblocks' levels in x264gpu_mb layout (X264GPU_MB_LEVELS each);
@@ -259,6 +265,10 @@ typedef struct x264gpu_config {
     int dpb;                  /* reference pictures the DPB holds (x264 sps->i_num_ref_frames: max(refs, 4 under --b-pyramid, ...)); 0 = refs.  The encoder
                                * owns dpb + 1 picture slots: x264gpu_encode_pictures names the slot every picture is reconstructed into */
     int weightb;              /* x264 --weightb (default on): implicit weighted bi-prediction, weights from the POC distances (weighted_bipred_idc 2) */
+    int psy_trellis_q8;       /* x264 i_psy_trellis = (int)(--psy-rd's second value / 4 * 256 + 0.5), 0..640 (tune film 10, grain 16, stillimage 45); 0 = none.
+                               * Every luma trellis site that is not a DC block (Intra_16x16 AC, 4x4, 8x8) searches with the psy term against the transform
+                               * of the source block, which the macroblock loop works out once per macroblock.  Non-zero needs trellis, cabac, rd and
+                               * me_method 1 or 2 (the psy search runs in kernel instantiations of its own, built for --me hex / umh) */
 } x264gpu_config;
 
 /* One picture of one stream for x264gpu_encode_pictures: slice type, quantiser and the reference lists as DPB slots — what x264's

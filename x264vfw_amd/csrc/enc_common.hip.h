@@ -96,6 +96,7 @@ struct EncK {
     int slices;               // x264 slice threads: slices per picture (rows split evenly), 1 = one
     int slices_plain;         // x264 --slices N rather than slice threads: the loop filter crosses slice boundaries
     unsigned long long *prof; // MB_PROF builds only: [streams][16] cycle counters of the macroblock loop's phases (null otherwise)
+    int psy_trellis;          // x264 i_psy_trellis (cfg.psy_trellis_q8): non-zero = the psy instantiations of the macroblock loop (last: no other field moves)
 };
 // the slice quantiser of stream s
 __device__ __forceinline__ int slice_qp(const EncK &k, int s) { return k.stream_qp ? (int)k.stream_qp[s] : k.qp; }

@@ -27,6 +27,7 @@ void launch_mb_slice_b_hex(const EncK &k, int streams, hipStream_t st);       //
 void launch_mb_slice_b_dia(const EncK &k, int streams, hipStream_t st);
 void launch_mb_slice_b_umh(const EncK &k, int streams, hipStream_t st);
 void launch_mb_slice_b_esa(const EncK &k, int streams, hipStream_t st);
+void launch_mb_slice_psy(const EncK &k, int streams, int slice_type, hipStream_t st);       // psy-trellis sessions (mb_slice_psy_*.hip): I, P and B slices, --me hex / umh
 int trellis_table_ptrs(const uint16_t **su, const uint8_t **tu, const int **l2);        // prim_kernels.hip
 int cabac_chain_table(const uint32_t **out);                                              // prim_kernels.hip
 int launch_hpel_filter(uint8_t *planes, size_t plane_bytes, int stride, int w, int h, int pad, int batch,
@@ -122,6 +123,8 @@ static int encoder_create_impl(x264gpu_encoder **out, const x264gpu_config *cfg,
     ARG_TRY(cfg->width >= 16 && cfg->height >= 16 && !(cfg->width & 1) && !(cfg->height & 1) && cfg->streams >= 1);
     ARG_TRY(cfg->qp_i >= 0 && cfg->qp_i <= 51 && cfg->qp_p >= 0 && cfg->qp_p <= 51 && cfg->refs >= 1 && cfg->refs <= 5);
     ARG_TRY(cfg->trellis == 0 || (cfg->trellis > 0 && cfg->trellis < 128 && (cfg->trellis & 63) && cfg->rd && cfg->cabac));      // trellis sites (mask; x264 --trellis 1 = 63, --trellis 2 = 63 + 64): RD sessions with CABAC
+    // psy-trellis: the luma trellis sites of the hex / umh instantiations built for it (mb_slice_psy_*.hip)
+    ARG_TRY(cfg->psy_trellis_q8 == 0 || (cfg->psy_trellis_q8 > 0 && cfg->psy_trellis_q8 <= 640 && cfg->trellis && cfg->cabac && cfg->rd && (cfg->me_method == 1 || cfg->me_method == 2)));
     ARG_TRY(!cfg->rd || (cfg->subme >= 6 && cfg->subme <= 9 && cfg->psy_rd_q8 >= 0 && cfg->psy_rd_q8 <= 2560));      // RD: x264's i_mbrd 1 (bit counts of the session's entropy coder)
     // rd > 1: RD refinement of the chosen type (x264 subme 8, i_mbrd 2): bit 0 on + a mask of refinement sites in bits 1..5 (x264 = all five: 63); CABAC, hex / umh
     ARG_TRY(cfg->rd >= 0 && cfg->rd < 128 && (cfg->rd < 2 || (cfg->rd & 1)) && (!(cfg->rd & 62) || (cfg->cabac && cfg->subme >= 8 && (cfg->me_method == 1 || cfg->me_method == 2))));      // bit 6: deblock-aware RD (x264 subme 9)      // (rd 0 with subme >= 8: the sub-pel iteration table of those levels without RD, as before)
@@ -556,6 +559,7 @@ static int encode_core(x264gpu_encoder *e, const uint8_t *d_i420, const x264gpu_
     }
     k.sl_stat = slice_type != X264GPU_SLICE_I && e->sl_stat ? e->sl_stat + (size_t)(!bslice ? 0 : pic.keep ? 1 : 2) * S * (size_t)e->cfg.slices * 4 : nullptr;      // the first guess: the last picture of the same kind
     k.sl_rerun = e->sl_rerun; k.sl_pass = 0;
+    k.psy_trellis = e->cfg.psy_trellis_q8;
     k.trellis = e->cfg.trellis; k.tr_su = nullptr; k.tr_tu = nullptr; k.tr_l2 = nullptr;
     if (k.trellis) { const int rc = trellis_table_ptrs(&k.tr_su, &k.tr_tu, &k.tr_l2); if (rc != X264GPU_OK) return rc; }
     k.ctab = nullptr;
@@ -584,11 +588,11 @@ static int encode_core(x264gpu_encoder *e, const uint8_t *d_i420, const x264gpu_
     mask |= 1;
     STAGE_MARK(1);
     // the macroblock loop: one wavefront per stream, raster order (sub-pel neighbourhood margin 2 px up to subme 7, 5 px above)
-    if (slice_type == X264GPU_SLICE_I) launch_mb_slice_intra(k, S, st);        // (RD instantiations inside, chosen by k.rd)
+    if (slice_type == X264GPU_SLICE_I) { if (k.psy_trellis) launch_mb_slice_psy(k, S, X264GPU_SLICE_I, st); else launch_mb_slice_intra(k, S, st); }        // (RD instantiations inside, chosen by k.rd)
     else {
         const auto launch_b = k.me_method == 0 ? launch_mb_slice_b_dia : k.me_method == 2 ? launch_mb_slice_b_umh : k.me_method == 3 ? launch_mb_slice_b_esa : launch_mb_slice_b_hex;
         const auto launch_p = k.me_method == 0 ? launch_mb_slice_dia : k.me_method == 2 ? launch_mb_slice_umh : k.me_method == 3 ? launch_mb_slice_esa : launch_mb_slice_hex;
-        const auto launch = [&](const EncK &kk, int streams, bool big_margin, hipStream_t s_) { if (bslice) launch_b(kk, streams, s_); else launch_p(kk, streams, big_margin, s_); };
+        const auto launch = [&](const EncK &kk, int streams, bool big_margin, hipStream_t s_) { if (kk.psy_trellis) launch_mb_slice_psy(kk, streams, bslice ? X264GPU_SLICE_B : X264GPU_SLICE_P, s_); else if (bslice) launch_b(kk, streams, s_); else launch_p(kk, streams, big_margin, s_); };
         if (k.sl_stat) hipLaunchKernelGGL(k_slice_priors, dim3((S + 63) / 64), dim3(64), 0, st, k, S, 1);
         launch(k, S, k.subme >= 8, st);
         // --slices N: slice i is final once slices 0..i-1 are, so slices - 1 rounds of "check the assumed counts, run the slices again whose

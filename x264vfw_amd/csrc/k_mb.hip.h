@@ -878,14 +878,31 @@ namespace x264gpu {
 // The trellis sites of a macroblock's FINAL encode (x264 --trellis 1; k.trellis = the mask of sites, 63 = all): what they need to run the
 // search of trellis.hip.h on the slice's live context variables (read only)
 enum { TR_P4 = 1, TR_P8 = 2, TR_C = 4, TR_I16 = 8, TR_I4 = 16, TR_I8 = 32 };
-struct TrCtx { int on; uint32_t r, r8, model; TrellisTab tt; };
-// nblk blocks of category CAT at coefs (scan order, `stride` entries apart), eight per pass; returns the mask of blocks left non-zero
-template <int CAT>
-__device__ __forceinline__ unsigned trellis_run(const TrCtx &tr, int16_t *coefs, int stride, int nblk, int qp, bool intra, int lane)
+struct TrCtx { int on; uint32_t r, r8, model; TrellisTab tt; static constexpr bool is_psy = false; };
+// ... of the psy-trellis instantiations (k_mb_slice's PSY): + the transform of the macroblock's SOURCE samples, worked out once per macroblock (fd4: its
+// sixteen 4x4 blocks, 16 entries each in scan order, the block order of the levels; fd8: its four 8x8 blocks, 64 each), and x264's i_psy_trellis
+struct TrCtxPsy : TrCtx { const int16_t *fd4, *fd8; int psy; static constexpr bool is_psy = true; };
+__device__ __forceinline__ void tr_psy_init(TrCtx &, const int16_t *, int) {}
+__device__ __forceinline__ void tr_psy_init(TrCtxPsy &t, const int16_t *fd, int psy) { t.fd4 = fd; t.fd8 = fd + 256; t.psy = psy; }
+__device__ __forceinline__ const int16_t *tr_fd4(const TrCtx &) { return nullptr; }
+__device__ __forceinline__ const int16_t *tr_fd4(const TrCtxPsy &t) { return t.fd4; }
+__device__ __forceinline__ const int16_t *tr_fd8(const TrCtx &) { return nullptr; }
+__device__ __forceinline__ const int16_t *tr_fd8(const TrCtxPsy &t) { return t.fd8; }
+#define TR_FSTRIDE_SAME 0x7fffffff
+// nblk blocks of category CAT at coefs (scan order, `stride` entries apart), eight per pass; returns the mask of blocks left non-zero.  fd (psy contexts, luma
+// blocks that are not DC blocks): the source transform of the first block, the following ones fstride entries apart (default: like the coefficients)
+template <int CAT, class TR>
+__device__ __forceinline__ unsigned trellis_run(const TR &tr, int16_t *coefs, int stride, int nblk, int qp, bool intra, int lane, const int16_t *fd = nullptr, int fstride = TR_FSTRIDE_SAME)
 {
     unsigned out = 0;
-    for (int b0 = 0; b0 < nblk; b0 += 8)
-        out |= (trellis_blocks<CAT>((lds_i16 *)(coefs + b0 * stride), stride, min(8, nblk - b0), qp, intra, tr.model, tr.tt, CAT == 5 ? tr.r8 : tr.r) & 0xffu) << b0;       // (bit 8: the levels-of-one loop ran)
+    for (int b0 = 0; b0 < nblk; b0 += 8) {
+        if constexpr (TR::is_psy && (CAT == 1 || CAT == 2 || CAT == 5)) {
+            TrellisPsy<true> p;
+            p.fstride = fstride == TR_FSTRIDE_SAME ? stride : fstride; p.fdct = (const lds_i16 *)(fd + b0 * p.fstride); p.q8 = tr.psy;
+            out |= (trellis_blocks<CAT, false, true>((lds_i16 *)(coefs + b0 * stride), stride, min(8, nblk - b0), qp, intra, tr.model, tr.tt, CAT == 5 ? tr.r8 : tr.r, p) & 0xffu) << b0;
+        } else
+            out |= (trellis_blocks<CAT>((lds_i16 *)(coefs + b0 * stride), stride, min(8, nblk - b0), qp, intra, tr.model, tr.tt, CAT == 5 ? tr.r8 : tr.r) & 0xffu) << b0;       // (bit 8: the levels-of-one loop ran)
+    }
     return out;
 }
 __device__ __forceinline__ void load_levels_scan(const int16_t *src, int v[4], int j)
@@ -898,8 +915,8 @@ __device__ __forceinline__ void load_levels_scan(const int16_t *src, int v[4], i
 // Final encode of an Intra_4x4 / Intra_8x8 macroblock of a trellis session (x264: i_skip_intra is 0 under --trellis 1, so the blocks are coded
 // again): the modes of the analysis (L.modes4 / L.modes8), every block predicted from its re-coded neighbours in the tile, transformed,
 // quantised by the trellis search, reconstructed.  Levels go to lvw in their final layout; returns the non-zero flags (R.nnz4 / R.nnz8 form).
-template <int M>
-__device__ __forceinline__ unsigned mb_encode_i4x4_trellis(const EncK &k, MbLds<M> &L, const MbCtx &c, uint32_t cz, uint32_t t4, const Q4 &q4, const TrCtx &trc, int16_t *lvw)
+template <int M, class TR>
+__device__ __forceinline__ unsigned mb_encode_i4x4_trellis(const EncK &k, MbLds<M> &L, const MbCtx &c, uint32_t cz, uint32_t t4, const Q4 &q4, const TR &trc, int16_t *lvw)
 {
     // The blocks in ten rounds along the anti-diagonals x + 2 y instead of sixteen steps in coding order: a block's neighbours (left, top, top left, and the
     // top right one where the coding order makes it available) lie on earlier diagonals, the search of a block reads only the slice's context variables,
@@ -933,7 +950,9 @@ __device__ __forceinline__ unsigned mb_encode_i4x4_trellis(const EncK &k, MbLds<
         lds_sync();
         if (lane < 4 * nb) store_levels_scan(pair + slot * 16, v, j);
         lds_sync();
-        trellis_run<2>(trc, pair, 16, nb, c.qp, true, lane);
+        // (psy: the round's blocks are not neighbours in the block order — the source transform of the second lies idx1 - idx0 blocks from the first's)
+        const int idx0 = blkidx_of(t - 2 * by0, by0), idx1 = nb > 1 ? blkidx_of(t - 2 * (by0 + 1), by0 + 1) : idx0;
+        trellis_run<2>(trc, pair, 16, nb, c.qp, true, lane, tr_fd4(trc) + idx0 * 16, (idx1 - idx0) * 16);
         lds_sync();
         load_levels_scan(pair + slot * 16, v, j);
         if (lane < 4 * nb) store_levels_scan(lvw + my_idx * 16, v, j);
@@ -949,8 +968,8 @@ __device__ __forceinline__ unsigned mb_encode_i4x4_trellis(const EncK &k, MbLds<
     lds_sync();
     return nnz4;
 }
-template <int M>
-__device__ __forceinline__ unsigned mb_encode_i8x8_trellis(const EncK &k, MbLds<M> &L, const MbCtx &c, uint32_t cz, const Q8 &q8, const TrCtx &trc, int16_t *lvw, int &cbp8)
+template <int M, class TR>
+__device__ __forceinline__ unsigned mb_encode_i8x8_trellis(const EncK &k, MbLds<M> &L, const MbCtx &c, uint32_t cz, const Q8 &q8, const TR &trc, int16_t *lvw, int &cbp8)
 {
     const int lane = relane(c.lane), g = lane >> 3, r8 = lane & 7;
     const bool left = c.mbx > 0, top = c.sy > 0, topright = top && c.mbx + 1 < k.mbw;
@@ -981,7 +1000,7 @@ __device__ __forceinline__ unsigned mb_encode_i8x8_trellis(const EncK &k, MbLds<
 #pragma unroll
             for (int i = 0; i < 8; i++) lvw[idx * 64 + c_zigzag8_inv[r8 * 8 + i]] = (int16_t)v[i];
         lds_sync();
-        trellis_run<5>(trc, lvw + idx * 64, 64, 1, c.qp, true, lane);
+        trellis_run<5>(trc, lvw + idx * 64, 64, 1, c.qp, true, lane, tr_fd8(trc) + idx * 64);
         lds_sync();
         unsigned mlo = 0, mhi = 0;
 #pragma unroll
@@ -1022,9 +1041,9 @@ struct IntraRes { int satd_i16, satd_i8, satd_i4, pred16; unsigned nnz4, nnz8; i
                   int dir16[4], dir8v; };
 
 // Needs the neighbour samples in L.tile / L.tile8 / L.nb and the neighbour macroblocks' edge modes in L.nmodes.
-template <int M>
+template <int M, class TR = TrCtx>
 __device__ __forceinline__ void mb_analyse_intra(const EncK &k, MbLds<M> &L, const MbCtx &c, uint32_t cz, uint32_t t4, int parts, int i_satd_inter,
-                                                 bool fast_intra, bool early_term, bool mbrd, const Q4 &q4, const Q8 &q8, IntraRes &R, const TrCtx *tra = nullptr)
+                                                 bool fast_intra, bool early_term, bool mbrd, const Q4 &q4, const Q8 &q8, IntraRes &R, const TR *tra = nullptr)
 {
     const bool RF2 = mbrd && ((k.rd >> 1) & 31) && (k.slice_type != X264GPU_SLICE_B || k.subme >= 9);      // x264's i_mbrd >= 2 (RD refinement, subme >= 8; a B slice analyses one level down)
     const bool every_mode = RF2 || (mbrd && !fast_intra);          // x264: i_mbrd >= 1 + b_fast_intra
@@ -1111,7 +1130,7 @@ __device__ __forceinline__ void mb_analyse_intra(const EncK &k, MbLds<M> &L, con
 #pragma unroll
                     for (int i = 0; i < 8; i++) L.lv8[idx * 64 + c_zigzag8_inv[r8 * 8 + i]] = (int16_t)v[i];
                 lds_sync();
-                trellis_run<5>(*tra, L.lv8 + idx * 64, 64, 1, c.qp, true, lane);
+                trellis_run<5>(*tra, L.lv8 + idx * 64, 64, 1, c.qp, true, lane, tr_fd8(*tra) + idx * 64);
                 lds_sync();
 #pragma unroll
                 for (int i = 0; i < 8; i++) v[i] = L.lv8[idx * 64 + c_zigzag8_inv[r8 * 8 + i]];
@@ -1179,7 +1198,7 @@ __device__ __forceinline__ void mb_analyse_intra(const EncK &k, MbLds<M> &L, con
             if (tra && (tra->on & TR_I4)) {
                 if (lane < 4) store_levels_scan(L.lv4 + idx * 16, v, j);
                 lds_sync();
-                trellis_run<2>(*tra, L.lv4 + idx * 16, 16, 1, c.qp, true, lane);
+                trellis_run<2>(*tra, L.lv4 + idx * 16, 16, 1, c.qp, true, lane, tr_fd4(*tra) + idx * 16);
                 lds_sync();
                 load_levels_scan(L.lv4 + idx * 16, v, j);
                 lds_sync();
@@ -1529,9 +1548,14 @@ __device__ __forceinline__ void b_predict(const EncK &k, const MbCtx &c, const B
 // 4 = 3 + the search in the intra analysis' block encodes and in every RD candidate (x264 --trellis 2);
 // 5 / 6 = 3 / 4 + RD refinement of the chosen type's vectors and intra modes (x264 subme >= 8: k_mb_refine.inc)
 // BS: B slice (PS is set as well: an inter slice) — RD instantiations with CABAC only; its own analysis and candidate order (k_mb_b.inc)
-template <int M, int ME, bool PS, int RD = 0, bool BS = false>
+// PSY: psy-trellis (cfg.psy_trellis_q8 != 0; RD >= 3 only) — instantiations of their own (mb_slice_psy_*.hip): the source transform of every macroblock in
+// LDS (1 KB beside MbLds: these instantiations alone give up the eighth wavefront a CU) and the psy variant of the search at the luma sites
+template <int M, int ME, bool PS, int RD = 0, bool BS = false, bool PSY = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MB_WAVES_PER_EU, 4))) void k_mb_slice(EncK k)
 {
+    static_assert(!PSY || RD >= 3, "psy-trellis: instantiations with the trellis quantiser");
+    using TRC = std::conditional_t<PSY, TrCtxPsy, TrCtx>;
+    __shared__ __attribute__((aligned(16))) int16_t psy_fd[PSY ? 512 : 1];          // (referenced in PSY instantiations only: the others allocate nothing)
     static_assert(!BS || PS, "B slices are inter slices");
     static_assert(RD != 7 || BS, "RD 7: B slices only");
     __shared__ __attribute__((aligned(16))) MbLds<M> L;
@@ -1724,6 +1748,26 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MB_WAVES_PER
         *(uint32_t *)(L.src + zy * 16 + zx) = cz;
         if constexpr (RD == 1) { if (lane < 48) rd_ntc[lane >= 24][lane >= 24 ? lane - 24 : lane] = ntcv; }
         if (lane < 32) *(uint32_t *)(L.csrc + (lane >> 2) * 16 + (lane & 3) * 4) = csv;
+        if constexpr (PSY) {
+            // x264 fenc_dct4 / fenc_dct8: the transform of the source samples themselves, in the scan order and block order of the levels
+            {
+                int e[4];
+                unpack4(cz, e);
+                dct4_quad(e, lane);
+                store_levels_scan(psy_fd + (lane >> 2) * 16, e, j4);
+            }
+            if (k.dct8x8) {
+                uint32_t elo, ehi;
+                z_to_r8(cz, lane, elo, ehi);
+                const int row = lane & 7, i8 = (lane >> 3) & 3;
+                int v[8];
+                unpack8(elo, ehi, v);
+                fwd8_1d(v); transpose8(v, lane); fwd8_1d(v); transpose8(v, lane);
+                if (lane < 32)
+#pragma unroll
+                    for (int i = 0; i < 8; i++) psy_fd[256 + i8 * 64 + c_zigzag8_inv[row * 8 + i]] = (int16_t)v[i];
+            }
+        }
         lds_sync();
 
         x264gpu_mb &recd = L.rec;
@@ -2005,7 +2049,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MB_WAVES_PER
             i_inter_satd = i_satd_inter;
             // the chroma mode depends on the neighbours only: decided here for every macroblock that is analysed (x264 does it here under chroma-ME,
             // otherwise only for macroblocks that end up intra — same mode either way); its cost enters the comparison under chroma-ME only
-            TrCtx tra_ctx;                   // --trellis 2: the analysis' block encodes run the search too
+            TRC tra_ctx;                   // --trellis 2: the analysis' block encodes run the search too
+            if constexpr (PSY) tr_psy_init(tra_ctx, psy_fd, k.psy_trellis);
             tra_ctx.on = 0; tra_ctx.r = 0; tra_ctx.r8 = 0; tra_ctx.model = 0; tra_ctx.tt.size_unary = nullptr; tra_ctx.tt.trans_unary = nullptr; tra_ctx.tt.lambda2 = nullptr;
             if constexpr (TRL2) {
                 if ((k.trellis & 64) && RD && k.rd) { tra_ctx.on = k.trellis & 63; tra_ctx.r = cab.r; tra_ctx.r8 = cab.r8; tra_ctx.model = cab_modelv; tra_ctx.tt.size_unary = k.tr_su; tra_ctx.tt.trans_unary = k.tr_tu; tra_ctx.tt.lambda2 = k.tr_l2; }
@@ -2206,7 +2251,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MB_WAVES_PER
         }
         STATE_UNIFORM();
         nnz = 0; cbp_luma = 0; cbp_chroma = 0;
-        TrCtx trc;                                                // trellis: the final pass of RD sessions with CABAC (x264 --trellis 1)
+        TRC trc;                                                // trellis: the final pass of RD sessions with CABAC (x264 --trellis 1)
+        if constexpr (PSY) tr_psy_init(trc, psy_fd, k.psy_trellis);
         trc.on = 0; trc.r = 0; trc.r8 = 0; trc.model = 0; trc.tt.size_unary = nullptr; trc.tt.trans_unary = nullptr; trc.tt.lambda2 = nullptr;
         if constexpr (RD >= 3) {
             if ((commit || TRL2) && (k.trellis & 63) && rdon) { trc.on = k.trellis & 63; trc.r = cab.r; trc.r8 = cab.r8; trc.model = cab_modelv; trc.tt.size_unary = k.tr_su; trc.tt.trans_unary = k.tr_tu; trc.tt.lambda2 = k.tr_l2; }
@@ -2251,7 +2297,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MB_WAVES_PER
 #pragma unroll
                             for (int i = 0; i < 8; i++) lvw[i8 * 64 + c_zigzag8_inv[row * 8 + i]] = (int16_t)v[i];
                         lds_sync();
-                        trellis_run<5>(trc, lvw, 64, 4, c.qp, false, lane);
+                        trellis_run<5>(trc, lvw, 64, 4, c.qp, false, lane, tr_fd8(trc));
                         lds_sync();
 #pragma unroll
                         for (int i = 0; i < 8; i++) v[i] = lvw[i8 * 64 + c_zigzag8_inv[row * 8 + i]];
@@ -2306,7 +2352,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MB_WAVES_PER
                     if (TRL2 && (trc.on & TR_P4)) {
                         store_levels_scan(lvw + (lane >> 2) * 16, v, j4);
                         lds_sync();
-                        trellis_run<2>(trc, lvw, 16, 16, c.qp, false, lane);
+                        trellis_run<2>(trc, lvw, 16, 16, c.qp, false, lane, tr_fd4(trc));
                         lds_sync();
                         load_levels_scan(lvw + (lane >> 2) * 16, v, j4);
                         lds_sync();
@@ -2419,7 +2465,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MB_WAVES_PER
 #pragma unroll
                         for (int i = 0; i < 8; i++) lvw[idx * 64 + c_zigzag8_inv[r8 * 8 + i]] = (int16_t)v[i];
                     lds_sync();
-                    trellis_run<5>(trc, lvw + idx * 64, 64, 1, c.qp, true, lane);
+                    trellis_run<5>(trc, lvw + idx * 64, 64, 1, c.qp, true, lane, tr_fd8(trc) + idx * 64);
                     lds_sync();
 #pragma unroll
                     for (int i = 0; i < 8; i++) v[i] = lvw[idx * 64 + c_zigzag8_inv[r8 * 8 + i]];
@@ -2567,7 +2613,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MB_WAVES_PER
 #pragma unroll
                             for (int i = 0; i < 8; i++) lvw[i8 * 64 + c_zigzag8_inv[row * 8 + i]] = (int16_t)v[i];
                         lds_sync();
-                        trellis_run<5>(trc, lvw, 64, 4, c.qp, false, lane);
+                        trellis_run<5>(trc, lvw, 64, 4, c.qp, false, lane, tr_fd8(trc));
                         lds_sync();
 #pragma unroll
                         for (int i = 0; i < 8; i++) v[i] = lvw[i8 * 64 + c_zigzag8_inv[row * 8 + i]];
@@ -2630,7 +2676,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MB_WAVES_PER
                     if (TRL && (trc.on & TR_P4)) {
                         store_levels_scan(lvw + (lane >> 2) * 16, v, j4);
                         lds_sync();
-                        trellis_run<2>(trc, lvw, 16, 16, c.qp, false, lane);
+                        trellis_run<2>(trc, lvw, 16, 16, c.qp, false, lane, tr_fd4(trc));
                         lds_sync();
                         load_levels_scan(lvw + (lane >> 2) * 16, v, j4);
                         lds_sync();
@@ -2727,7 +2773,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MB_WAVES_PER
                 if (TRL && (trc.on & TR_I16)) {
                     store_levels_scan(lvw + (lane >> 2) * 16, v, j4);
                     lds_sync();
-                    trellis_run<1>(trc, lvw, 16, 16, c.qp, true, lane);
+                    trellis_run<1>(trc, lvw, 16, 16, c.qp, true, lane, tr_fd4(trc));
                     lds_sync();
                     load_levels_scan(lvw + (lane >> 2) * 16, v, j4);
                     lds_sync();

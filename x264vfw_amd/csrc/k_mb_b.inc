@@ -359,7 +359,7 @@ for (;; rd_ph++) {
             }
             pf.mark(PH_ME_GLUE);
             satd_chroma = mb_intra_chroma_cost(k, L, c, predc);
-            mb_analyse_intra(k, L, c, cz, t4, parts, c.chroma_me ? i_cost - satd_chroma : i_cost, fast_intra, early_term, false, q_li, q8i, IR, nullptr);
+            mb_analyse_intra(k, L, c, cz, t4, parts, c.chroma_me ? i_cost - satd_chroma : i_cost, fast_intra, early_term, false, q_li, q8i, IR, (const TrCtx *)nullptr);
             if (c.chroma_me) { IR.satd_i16 += satd_chroma; IR.satd_i8 += satd_chroma; IR.satd_i4 += satd_chroma; }
             pf.mark(PH_INTRA);
             rd_best = i_cost; rd_i16 = IR.satd_i16; rd_i8 = IR.satd_i8; rd_i4 = IR.satd_i4;
@@ -385,7 +385,8 @@ for (;; rd_ph++) {
         // intra analysis against the inter SATD cost (the chroma mode first: its cost rides along under chroma-ME)
         pf.mark(PH_ME_GLUE);
         satd_chroma = mb_intra_chroma_cost(k, L, c, predc, rf_dirc);
-        TrCtx tra_ctx;                   // --trellis 2: the analysis' block encodes run the search too
+        TRC tra_ctx;                   // --trellis 2: the analysis' block encodes run the search too
+        if constexpr (PSY) tr_psy_init(tra_ctx, psy_fd, k.psy_trellis);
         tra_ctx.on = 0; tra_ctx.r = 0; tra_ctx.r8 = 0; tra_ctx.model = 0; tra_ctx.tt.size_unary = nullptr; tra_ctx.tt.trans_unary = nullptr; tra_ctx.tt.lambda2 = nullptr;
         if constexpr (TRL2) {
             if (k.trellis & 64) { tra_ctx.on = k.trellis & 63; tra_ctx.r = cab.r; tra_ctx.r8 = cab.r8; tra_ctx.model = cab_modelv; tra_ctx.tt.size_unary = k.tr_su; tra_ctx.tt.trans_unary = k.tr_tu; tra_ctx.tt.lambda2 = k.tr_l2; }

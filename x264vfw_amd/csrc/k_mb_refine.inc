@@ -130,7 +130,8 @@ for (;;) {
         // ---- intra_rd_refine: the chosen intra type's modes once more, on RD cost.  rf_st: 0 start, 10 Intra_16x16 modes, 20 chroma modes,
         //      30 Intra_4x4 blocks, 40 Intra_8x8 blocks, 99 done ----
         const int sites = k.rd >> 1;
-        TrCtx tra_ref;                   // --trellis 2: the refinement's block encodes run the search too (x264 b_trellis during the analysis)
+        TRC tra_ref;                   // --trellis 2: the refinement's block encodes run the search too (x264 b_trellis during the analysis)
+        if constexpr (PSY) tr_psy_init(tra_ref, psy_fd, k.psy_trellis);
         tra_ref.on = 0; tra_ref.r = 0; tra_ref.r8 = 0; tra_ref.model = 0; tra_ref.tt.size_unary = nullptr; tra_ref.tt.trans_unary = nullptr; tra_ref.tt.lambda2 = nullptr;
         if constexpr (TRL2) {
             if (k.trellis & 64) { tra_ref.on = k.trellis & 63; tra_ref.r = cab.r; tra_ref.r8 = cab.r8; tra_ref.model = cab_modelv; tra_ref.tt.size_unary = k.tr_su; tra_ref.tt.trans_unary = k.tr_tu; tra_ref.tt.lambda2 = k.tr_l2; }
@@ -217,7 +218,7 @@ for (;;) {
                 if (TRL2 && (tra_ref.on & TR_I4)) {
                     if (lane < 36) store_levels_scan(L.lv8 + (lane >> 2) * 16, v, j4);
                     lds_sync();
-                    trellis_run<2>(tra_ref, L.lv8, 16, 9, c.qp, true, lane);
+                    trellis_run<2>(tra_ref, L.lv8, 16, 9, c.qp, true, lane, tr_fd4(tra_ref) + idx * 16, 0);          // (psy: nine predictions of ONE source block)
                     lds_sync();
                     if (lane < 36) load_levels_scan(L.lv8 + (lane >> 2) * 16, v, j4);
                     lds_sync();

@@ -349,6 +349,41 @@ int trellis_table_ptrs(const uint16_t **su, const uint8_t **tu, const int **l2)
     return rc;
 }
 
+// ... with the psy term (categories 1, 2, 5): the source blocks' transform travels to LDS beside the coefficients
+template <int CAT, bool FORCE_GENERAL>
+__global__ void __launch_bounds__(64) k_trellis_blocks_psy(const int16_t *coefs, const int16_t *fdct, int nblk, int qp, int intra, int psy_q8, const uint8_t *states, TrellisTab tt,
+                                                           int16_t *levels, uint8_t *nz, uint8_t *paths)
+{
+    constexpr int NC = CAT == 5 ? 64 : 16;
+    __shared__ int16_t buf[8 * 64], fbuf[8 * 64];
+    __shared__ uint8_t st[460];
+    const int lane = threadIdx.x;
+    for (int i = lane; i < 460; i += 64) st[i] = states[i];
+    const uint32_t model = cab_model(lane);
+    __syncthreads();
+    const int sig_off = CAT == 1 ? 120 : CAT == 2 ? 134 : 402, last_off = CAT == 1 ? 181 : CAT == 2 ? 195 : 417, abs_off = CAT == 1 ? 237 : CAT == 2 ? 247 : 426;
+    uint32_t reg = 0;
+    for (int ctx = 0; ctx < 460; ctx++) {
+        int rg, ln, sh;
+        if (!cab_locate(ctx, rg, ln, sh) || ln != lane) continue;
+        const bool mine = (ctx >= sig_off && ctx < sig_off + 16) || (ctx >= last_off && ctx < last_off + 16) || (ctx >= abs_off && ctx < abs_off + 10);
+        if (mine && rg == (CAT == 5 ? 2 : 1)) reg |= (uint32_t)st[ctx] << sh;
+    }
+    TrellisPsy<true> psy;
+    psy.fdct = (const lds_i16 *)fbuf; psy.fstride = NC; psy.q8 = psy_q8;
+    for (int b0 = 0; b0 < nblk; b0 += 8) {
+        const int nb = min(8, nblk - b0);
+        for (int i = lane; i < nb * NC; i += 64) { buf[i] = coefs[(size_t)b0 * NC + i]; fbuf[i] = fdct[(size_t)b0 * NC + i]; }
+        __syncthreads();
+        const unsigned m = trellis_blocks<CAT, FORCE_GENERAL, true>((lds_i16 *)buf, NC, nb, qp, intra != 0, model, tt, reg, psy);
+        __syncthreads();
+        for (int i = lane; i < nb * NC; i += 64) levels[(size_t)b0 * NC + i] = buf[i];
+        if (lane < nb) nz[b0 + lane] = (uint8_t)((m >> lane) & 1);
+        if (paths && lane == 0) paths[b0 >> 3] = (uint8_t)((m >> 8) & 3);
+        __syncthreads();
+    }
+}
+
 template <int CAT, bool FORCE_GENERAL>
 __global__ void __launch_bounds__(64) k_trellis_blocks(const int16_t *coefs, int nblk, int qp, int intra, const uint8_t *states, TrellisTab tt, int16_t *levels, uint8_t *nz, uint8_t *paths)
 {
@@ -405,6 +440,31 @@ int x264gpu_trellis_blocks_ex(const int16_t *d_coefs, int nblk, int cat, int qp,
     case 2: TRELLIS_LAUNCH(2); break;
     case 3: TRELLIS_LAUNCH(3); break;
     case 4: TRELLIS_LAUNCH(4); break;
+    default: TRELLIS_LAUNCH(5); break;
+    }
+#undef TRELLIS_LAUNCH
+    HIP_TRY(hipGetLastError());
+    return X264GPU_OK;
+}
+
+int x264gpu_trellis_blocks_psy(const int16_t *d_coefs, const int16_t *d_fenc_dct, int nblk, int cat, int qp, int intra, int psy_trellis_q8, const uint8_t *d_states460,
+                               int16_t *d_levels, uint8_t *d_nz, int force_general, uint8_t *d_paths, void *stream)
+{
+    ARG_TRY(psy_trellis_q8 >= 0 && psy_trellis_q8 <= 640 && cat >= 0 && cat <= 5);
+    // no psy term in DC and chroma blocks, none at strength 0: the plain search
+    if (!psy_trellis_q8 || !(cat == 1 || cat == 2 || cat == 5)) return x264gpu_trellis_blocks_ex(d_coefs, nblk, cat, qp, intra, d_states460, d_levels, d_nz, force_general, d_paths, stream);
+    ARG_TRY(d_coefs && d_fenc_dct && d_states460 && d_levels && d_nz && nblk >= 0 && qp >= 0 && qp <= 51);
+    if (!nblk) return X264GPU_OK;
+    TrellisTab tt;
+    const int rc = trellis_tables(&tt);
+    if (rc != X264GPU_OK) return rc;
+    const hipStream_t st = (hipStream_t)stream;
+#define TRELLIS_LAUNCH(CAT_) \
+    if (force_general) hipLaunchKernelGGL((k_trellis_blocks_psy<CAT_, true>), dim3(1), dim3(64), 0, st, d_coefs, d_fenc_dct, nblk, qp, intra, psy_trellis_q8, d_states460, tt, d_levels, d_nz, d_paths); \
+    else hipLaunchKernelGGL((k_trellis_blocks_psy<CAT_, false>), dim3(1), dim3(64), 0, st, d_coefs, d_fenc_dct, nblk, qp, intra, psy_trellis_q8, d_states460, tt, d_levels, d_nz, d_paths)
+    switch (cat) {
+    case 1: TRELLIS_LAUNCH(1); break;
+    case 2: TRELLIS_LAUNCH(2); break;
     default: TRELLIS_LAUNCH(5); break;
     }
 #undef TRELLIS_LAUNCH

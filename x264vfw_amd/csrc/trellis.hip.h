@@ -72,10 +72,17 @@ template <int N> __device__ __forceinline__ unsigned long long tr_row_shr(unsign
 // The context variables come in `reg`: the role-indexed register of the category (cabac_rd.hip.h: r for categories 0..4 — this category's byte —,
 // r8 for 8x8 blocks).  ONE out-of-line copy per category serves every call site: inlined eight times the search cost the macroblock loop
 // twice the register spills.
+// PSY (x264 --psy-rd a:b, psy-trellis; instantiations of their own): in luma blocks that are not DC blocks (CAT 1, 2, 5), at scan positions above 0, a
+// candidate level pays  d * d * coef_weight2 - coef_weight1 * q8 * |unquant_abs_level + SIGN(fdct - coef, coef)|  where fdct is the transform of the SOURCE
+// block (psy.fdct: in LDS, the scan order of coefs) and q8 = i_psy_trellis.  The term can be negative: scores are kept modulo
+// 2^64 above a bias of 2^50, and 63 coefficients of 2^17 at q8 = 640 stay below 2^41.
 typedef __attribute__((address_space(3))) int16_t lds_i16;
-template <int CAT, bool FORCE_GENERAL = false>
-__device__ __noinline__ unsigned trellis_blocks(lds_i16 *coefs, int stride, int nblk, int qp, bool intra, uint32_t model, TrellisTab tt, uint32_t reg)
+template <bool PSY> struct TrellisPsy {};
+template <> struct TrellisPsy<true> { const lds_i16 *fdct; int fstride; int q8; };      // block b of the call: fdct + b * fstride (its own stride: one source block may serve several candidates)
+template <int CAT, bool FORCE_GENERAL = false, bool PSY = false>
+__device__ __noinline__ unsigned trellis_blocks(lds_i16 *coefs, int stride, int nblk, int qp, bool intra, uint32_t model, TrellisTab tt, uint32_t reg, TrellisPsy<PSY> psy = {})
 {
+    static_assert(!PSY || CAT == 1 || CAT == 2 || CAT == 5, "psy-trellis: luma blocks that are not DC blocks");
     namespace T = x264gpu_cabac;
     const int lane = (int)threadIdx.x & 63;
     constexpr int st_sh = CAT == 5 || CAT == 2 ? 0 : CAT == 1 ? 8 : CAT == 4 ? 16 : 24;
@@ -103,6 +110,17 @@ __device__ __noinline__ unsigned trellis_blocks(lds_i16 *coefs, int stride, int 
         for (int k2 = 1; k2 < NCLS; k2++) r = cl == k2 ? t[k2] : r;
         return r;
     };
+    // coef_weight1 (the square roots of the distortion weights, FIX8) x i_psy_trellis, per class
+    int q_pw[NCLS];
+    const lds_i16 *fmine = nullptr;
+    if constexpr (PSY) {
+        constexpr int w1_4[3] = { 453, 286, 181 }, w1_8[6] = { 256, 227, 410, 241, 324, 305 };      // FIX8(1.76777, 1.11803, 0.70711) / FIX8(1.0000, 0.8859, 1.6000, 0.9415, 1.2651, 1.1910)
+#pragma unroll
+        for (int cl = 0; cl < NCLS; cl++) q_pw[cl] = (CAT == 5 ? w1_8[cl] : w1_4[cl % 3]) * psy.q8;
+        fmine = psy.fdct + g * psy.fstride;
+    }
+    // what a candidate that reconstructs to ua gets back at position i > 0: weight x |ua + SIGN(source - coefficient, coefficient)|
+    auto psy_gain = [&](int pw, int ua, int spred) { return (unsigned long long)(unsigned)pw * (unsigned)abs(ua + spred); };
     auto cls_of = [&](int i) { return DC ? 0 : trellis_class(CAT, i); };
     auto guess = [&](int c, int i) { const int cl = cls_of(i); return ((pick(q_bias, cl) + abs(c)) * pick(q_mf, cl)) >> 16; };      // |level| of the round-to-nearest quantiser
 
@@ -183,7 +201,10 @@ __device__ __noinline__ unsigned trellis_blocks(lds_i16 *coefs, int stride, int 
             const int c = act ? (int)mine[i] : 0, a = abs(c), ua = (un + 128) >> 8;
             auto wsq = [&](int d) { return (unsigned long long)(unsigned)(d * d) * (unsigned)wgt; };
             // level 0 reconstructs to 0 whatever the block (the DC-only term too), so its two distortions agree: ssd0[0] - ssd1[0] = -t0
-            const unsigned long long e0 = wsq(a) + t0i, e1 = wsq(a - ua);
+            unsigned long long e0 = wsq(a) + t0i, e1 = wsq(a - ua);
+            if constexpr (PSY) {
+                if (act && i > 0) { const int pred = (int)fmine[i] - c, spred = c < 0 ? -pred : pred, pw = pick(q_pw, cl); e0 -= psy_gain(pw, 0, spred); e1 -= psy_gain(pw, ua, spred); }
+            }
             unsigned long long e1_first = e1;
             if (!DC) { if (i == 0) e1_first = wsq(c - (((c < 0 ? -ua : ua) + 8) & ~15)); }
             const int l1state = n == 3 ? (int)((cs >> 8) & 255) : ls_l1;
@@ -234,10 +255,15 @@ __device__ __noinline__ unsigned trellis_blocks(lds_i16 *coefs, int stride, int 
         const int c = act ? (int)mine[i] : 0, a = abs(c), q = act ? ((pick(q_bias, cl) + a) * pick(q_mf, cl)) >> 16 : 1;
         // ---- every lane as a source node: its two candidate levels A = q - 1, B = q ----
         unsigned long long ssd0[2], ssd1[2];
+        int spred = 0, pw = 0;
+        if constexpr (PSY) {
+            if (act && i > 0) { const int pred = (int)fmine[i] - c; spred = c < 0 ? -pred : pred; pw = pick(q_pw, cl); }
+        }
         for (int kk = 0; kk < 2; kk++) {
             const int lvl = q - 1 + kk, ua = (int)(((long long)un * lvl + 128) >> 8);
             int d = a - ua;                                                   // |d| < 2^15.5: the square fits 32 bits
             ssd1[kk] = (unsigned long long)(unsigned)(d * d) * (unsigned)wgt;
+            if constexpr (PSY) ssd1[kk] -= psy_gain(pw, ua, spred);          // (pw = 0 at position 0)
             ssd0[kk] = ssd1[kk];
             if (i == 0 && !DC && !ctx_hi) { d = c - (((c < 0 ? -ua : ua) + 8) & ~15); ssd0[kk] = (unsigned long long)(unsigned)(d * d) * (unsigned)wgt; }
         }

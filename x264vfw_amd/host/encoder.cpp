@@ -288,6 +288,7 @@ static void fill_pic_out(x264_picture_t *pic_out, int i_type, bool keyframe, int
 
 extern "C" {
 // ---- x264_encoder_open, step by step (each step logs what it changes or why it fails; a failed step leaves the teardown to x264_encoder_close) ----
+static int psy_trellis_q8(const x264_param_t &p) { return p.analyse.i_trellis ? (int)(p.analyse.f_psy_trellis / 4 * 256 + 0.5f) : 0; }      // h->mb.i_psy_trellis
 static int psy_rd_q8(const x264_param_t &p) { return p.analyse.i_subpel_refine >= 6 ? (int)(p.analyse.f_psy_rd * 256.0f + 0.5f) : 0; }      // h->mb.i_psy_rd
 
 // the toolset: what this pipeline implements of the analysis options, slices and threads (reported back via x264_encoder_parameters)
@@ -326,17 +327,27 @@ static void open_toolset(x264_t *h)
     p.analyse.i_subpel_refine = clampi(p.analyse.i_subpel_refine, 0, 9);
     // trellis 1 = the final encode of every macroblock quantised by x264's trellis search on the slice's CABAC state: on the device where that state
     // lives, i.e. in CABAC sessions with RD (subme >= 6); trellis 2 = also the block encodes of the intra analysis and every RD candidate
+    const int trellis_asked = p.analyse.i_trellis;
     if (p.analyse.i_trellis && (!p.b_cabac || p.analyse.i_subpel_refine < 6)) {
         xlog(&p, X264_LOG_WARNING, "trellis %d needs CABAC and subme >= 6 in the MI355X path (the search reads the CABAC state the device carries for RD): trellis 0\n", p.analyse.i_trellis);
         p.analyse.i_trellis = 0;
     }
-    if (p.analyse.f_psy_trellis > 0) { xlog(&p, X264_LOG_WARNING, "psy-trellis is not implemented in the MI355X path: psy-trellis 0\n"); p.analyse.f_psy_trellis = 0; }
     p.analyse.b_psy = p.analyse.b_psy != 0;
     if (!p.analyse.b_psy) { p.analyse.f_psy_rd = 0; p.analyse.f_psy_trellis = 0; }       // x264 validate_parameters
     p.analyse.f_psy_rd = p.analyse.f_psy_rd < 0 ? 0 : p.analyse.f_psy_rd > 10 ? 10 : p.analyse.f_psy_rd;
+    // psy-trellis (--psy-rd a:b, tune film / grain / stillimage): the search's distortion term that rewards keeping the source's energy, in every luma
+    // trellis site on the device.  x264 drops it silently without psy or trellis; here it also needs what the device's psy search is built for
+    p.analyse.f_psy_trellis = p.analyse.f_psy_trellis < 0 ? 0 : p.analyse.f_psy_trellis > 10 ? 10 : p.analyse.f_psy_trellis;
+    if (!trellis_asked) p.analyse.f_psy_trellis = 0;
+    if (p.analyse.f_psy_trellis > 0) {
+        const char *missing = !p.b_cabac ? "CABAC" : p.analyse.i_subpel_refine < 6 ? "subme >= 6" :
+                              p.analyse.i_me_method != X264_ME_HEX && p.analyse.i_me_method != X264_ME_UMH ? "me hex / umh" : nullptr;
+        if (missing) { xlog(&p, X264_LOG_WARNING, "psy-trellis needs %s in the MI355X path (the psy search is built for CABAC trellis sessions under me hex / umh): psy-trellis 0\n", missing); p.analyse.f_psy_trellis = 0; }
+    }
     // psy RD raises luma quality at chroma's cost, so x264 lowers the chroma quantiser offset to compensate (encoder.c, validate / mb init)
     int eff_chroma_qp_offset = p.analyse.i_chroma_qp_offset;
     if (psy_rd_q8(p)) eff_chroma_qp_offset -= p.analyse.f_psy_rd < 0.25f ? 1 : 2;
+    if (psy_trellis_q8(p)) eff_chroma_qp_offset -= p.analyse.f_psy_trellis < 0.25f ? 1 : 2;
     eff_chroma_qp_offset = clampi(eff_chroma_qp_offset, -12, 12);
     p.analyse.i_chroma_qp_offset = eff_chroma_qp_offset;          // x264 changes the parameter in place too: the PPS carries it
     p.analyse.b_fast_pskip = p.analyse.b_fast_pskip != 0;
@@ -582,6 +593,7 @@ static x264gpu_config open_device_config(x264_t *h)
     cfg.chroma_qp_offset = p.analyse.i_chroma_qp_offset;
     cfg.rd = p.analyse.i_subpel_refine >= 8 ? 63 : p.analyse.i_subpel_refine >= 6; cfg.psy_rd_q8 = psy_rd_q8(p);      // 63: RD + every refinement site (x264's i_mbrd 2)
     if (p.analyse.i_subpel_refine >= 9 && p.b_deblocking_filter) cfg.rd |= 64;          // h->mb.b_deblock_rdo: whole-macroblock RD costs measured after the loop filter
+    cfg.psy_trellis_q8 = psy_trellis_q8(p);
     cfg.trellis = p.analyse.i_trellis == 2 ? 63 + 64 : p.analyse.i_trellis ? 63 : 0;         // every quantiser call of the final encode; + 64: of the analysis too
     cfg.psy = cfg.rd && p.analyse.b_psy;           // x264: the chroma lambda offset table follows b_psy, whatever the psy-rd strength
     cfg.deadzone_inter = p.analyse.i_luma_deadzone[0]; cfg.deadzone_intra = p.analyse.i_luma_deadzone[1];
