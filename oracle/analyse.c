@@ -555,17 +555,29 @@ static void scan4(int16_t *dst, const dctcoef *src) { for (int k = 0; k < 16; k+
  * (e->b_trellis; x264 h->mb.b_trellis under --trellis 1) — the trellis search of trellis.cpp on the slice's live context variables.
  * cat = CABAC block category, qp = the block's quantiser (chroma: the chroma one) */
 int x264o_quant_trellis_cabac(dctcoef *dct, const uint16_t *mf, int qp, int cat, int intra, const uint8_t *state);
+int x264o_quant_trellis_cabac_psy(dctcoef *dct, const uint16_t *mf, int qp, int cat, int intra, const uint8_t *state, int psy, const dctcoef *fenc_dct);
 /* e->b_trellis: the sites of the final encode that use it, as a mask (cfg.trellis; x264's --trellis 1 = all of them = 63): 1 inter luma 4x4,
  * 2 inter luma 8x8, 4 chroma, 8 Intra_16x16, 16 Intra_4x4, 32 Intra_8x8 — the device was brought up site by site against these masks */
 enum { TR_P4 = 1, TR_P8 = 2, TR_C = 4, TR_I16 = 8, TR_I4 = 16, TR_I8 = 32 };
-static int quant_4x4(x264o_encoder *e, dctcoef *d, const uint16_t *mf, const uint16_t *bias, int qp, int cat, int intra)
+/* src: the block of the SOURCE picture (stride e->fs) behind a luma block, NULL for chroma: under psy-trellis (cfg.psy_trellis_q8; x264 h->mb.i_psy_trellis,
+ * fenc_dct4 / fenc_dct8 of x264_psy_trellis_init) the search weighs every level against the source's own transform */
+static const pixel zero_pred[8] = { 0 };
+static int quant_4x4(x264o_encoder *e, dctcoef *d, const uint16_t *mf, const uint16_t *bias, int qp, int cat, int intra, const pixel *src)
 {
     const int site = cat == 4 ? TR_C : cat == 1 ? TR_I16 : intra ? TR_I4 : TR_P4;
-    return (e->b_trellis & site) ? x264o_quant_trellis_cabac(d, mf, qp, cat, intra, e->cabac_state) : x264o_quant_4x4(d, mf, bias);
+    if (!(e->b_trellis & site)) return x264o_quant_4x4(d, mf, bias);
+    if (!src || !e->cfg.psy_trellis_q8) return x264o_quant_trellis_cabac(d, mf, qp, cat, intra, e->cabac_state);
+    dctcoef fd[16];
+    x264o_sub4x4_dct(fd, src, e->fs, zero_pred, 0);
+    return x264o_quant_trellis_cabac_psy(d, mf, qp, cat, intra, e->cabac_state, e->cfg.psy_trellis_q8, fd);
 }
-static int quant_8x8(x264o_encoder *e, dctcoef *d, const uint16_t *mf, const uint16_t *bias, int qp, int intra)
+static int quant_8x8(x264o_encoder *e, dctcoef *d, const uint16_t *mf, const uint16_t *bias, int qp, int intra, const pixel *src)
 {
-    return (e->b_trellis & (intra ? TR_I8 : TR_P8)) ? x264o_quant_trellis_cabac(d, mf, qp, 5, intra, e->cabac_state) : x264o_quant_8x8(d, mf, bias);
+    if (!(e->b_trellis & (intra ? TR_I8 : TR_P8))) return x264o_quant_8x8(d, mf, bias);
+    if (!e->cfg.psy_trellis_q8) return x264o_quant_trellis_cabac(d, mf, qp, 5, intra, e->cabac_state);
+    dctcoef fd[64];
+    x264o_sub8x8_dct8(fd, src, e->fs, zero_pred, 0);
+    return x264o_quant_trellis_cabac_psy(d, mf, qp, 5, intra, e->cabac_state, e->cfg.psy_trellis_q8, fd);
 }
 static int quant_4x4_dc(x264o_encoder *e, dctcoef *d, const uint16_t *mf, const uint16_t *bias, int qp)
 {
@@ -584,7 +596,7 @@ static void encode_luma_inter(x264o_encoder *e, const pixel *fenc, pixel *rec, i
     const uint16_t *mf = e->qt.quant4_mf[X264O_CQM_4PY][qp], *bias = e->qt.quant4_bias[X264O_CQM_4PY][qp];
     for (int b = 0; b < 16; b++) {
         x264o_sub4x4_dct(d[b], fenc + blk_y[b] * 4 * e->fs + blk_x[b] * 4, e->fs, rec + blk_y[b] * 4 * e->rs + blk_x[b] * 4, e->rs);
-        nz[b] = quant_4x4(e, d[b], mf, bias, qp, 2, 0);
+        nz[b] = quant_4x4(e, d[b], mf, bias, qp, 2, 0, fenc + blk_y[b] * 4 * e->fs + blk_x[b] * 4);
         scan4(lv + b * 16, d[b]);
         if (nz[b] && e->cfg.dct_decimate) score8[b >> 2] += x264o_decimate_score(lv + b * 16, 16);
     }
@@ -616,7 +628,7 @@ static void encode_luma_inter8(x264o_encoder *e, const pixel *fenc, pixel *rec, 
     const int b_decimate = e->cfg.dct_decimate && !(e->b_trellis & TR_P8);
     for (int i8 = 0; i8 < 4; i8++) {
         x264o_sub8x8_dct8(d[i8], fenc + (i8 >> 1) * 8 * e->fs + (i8 & 1) * 8, e->fs, rec + (i8 >> 1) * 8 * e->rs + (i8 & 1) * 8, e->rs);
-        keep[i8] = quant_8x8(e, d[i8], mf, bias, qp, 0);
+        keep[i8] = quant_8x8(e, d[i8], mf, bias, qp, 0, fenc + (i8 >> 1) * 8 * e->fs + (i8 & 1) * 8);
         for (int k = 0; k < 64; k++) scan[i8][k] = d[i8][x264o_zigzag8[k]];
         if (keep[i8] && b_decimate) {
             const int sc = x264o_decimate_score(scan[i8], 64);
@@ -688,7 +700,7 @@ static void encode_chroma(x264o_encoder *e, const pixel *fenc_uv, pixel *rec_uv,
             const int o = (i >> 1) * 32 + (i & 1) * 4;
             x264o_sub4x4_dct(d[i], f[c] + o, 8, p[c] + o, 8);
             dc[i] = d[i][0]; d[i][0] = 0;
-            nz[i] = quant_4x4(e, d[i], mf, bias, qpc, 4, !inter);
+            nz[i] = quant_4x4(e, d[i], mf, bias, qpc, 4, !inter, NULL);
             int16_t *l = lv + X264GPU_LV_CHROMA_AC + (c * 4 + i) * 16;
             scan4(l, d[i]);
             if (nz[i]) { nzac = 1; if (b_decimate) score += x264o_decimate_score(l + 1, 15); }
@@ -721,7 +733,7 @@ static int encode_i4x4(x264o_encoder *e, const pixel *f, pixel *r, int qp, int16
 {
     dctcoef d[16];
     x264o_sub4x4_dct(d, f, e->fs, r, e->rs);
-    if (!quant_4x4(e, d, e->qt.quant4_mf[X264O_CQM_4IY][qp], e->qt.quant4_bias[X264O_CQM_4IY][qp], qp, 2, 1)) { memset(l, 0, 32); return 0; }
+    if (!quant_4x4(e, d, e->qt.quant4_mf[X264O_CQM_4IY][qp], e->qt.quant4_bias[X264O_CQM_4IY][qp], qp, 2, 1, f)) { memset(l, 0, 32); return 0; }
     scan4(l, d);
     x264o_dequant_4x4(d, e->qt.dequant4_mf, qp);
     x264o_add4x4_idct(r, e->rs, d);
@@ -731,7 +743,7 @@ static int encode_i8x8(x264o_encoder *e, const pixel *f, pixel *r, int qp, int i
 {
     dctcoef d[64];
     x264o_sub8x8_dct8(d, f, e->fs, r, e->rs);
-    if (!quant_8x8(e, d, e->qt.quant8_mf[X264O_CQM_8IY][qp], e->qt.quant8_bias[X264O_CQM_8IY][qp], qp, 1)) return 0;
+    if (!quant_8x8(e, d, e->qt.quant8_mf[X264O_CQM_8IY][qp], e->qt.quant8_bias[X264O_CQM_8IY][qp], qp, 1, f)) return 0;
     for (int k = 0; k < 64; k++) {
         const int16_t v = d[x264o_zigzag8[k]];
         lv256[(i8 * 4 + (k & 3)) * 16 + (k >> 2)] = v;
@@ -755,7 +767,7 @@ static void encode_i16x16(x264o_encoder *e, const pixel *fenc, pixel *rec, int q
     for (int b = 0; b < 16; b++) {
         x264o_sub4x4_dct(d[b], fenc + blk_y[b] * 4 * e->fs + blk_x[b] * 4, e->fs, rec + blk_y[b] * 4 * e->rs + blk_x[b] * 4, e->rs);
         dc[blk_y[b] * 4 + blk_x[b]] = d[b][0]; d[b][0] = 0;
-        nz[b] = quant_4x4(e, d[b], mf, bias, qp, 1, 1);
+        nz[b] = quant_4x4(e, d[b], mf, bias, qp, 1, 1, fenc + blk_y[b] * 4 * e->fs + blk_x[b] * 4);
         scan4(lv + b * 16, d[b]);
         if (nz[b]) { any_ac = 1; x264o_dequant_4x4(d[b], e->qt.dequant4_mf, qp); if (score < 6) score += x264o_decimate_score(lv + b * 16 + 1, 15); }
     }
@@ -2438,7 +2450,7 @@ static void encode_p8x8(actx *a, int i8, x264gpu_mb *mb, int16_t *lv)
         dctcoef d[64];
         int16_t scan[64];
         x264o_sub8x8_dct8(d, fenc, e->fs, rec, e->rs);
-        int nz = quant_8x8(e, d, e->qt.quant8_mf[X264O_CQM_8PY][qp], e->qt.quant8_bias[X264O_CQM_8PY][qp], qp, 0);
+        int nz = quant_8x8(e, d, e->qt.quant8_mf[X264O_CQM_8PY][qp], e->qt.quant8_bias[X264O_CQM_8PY][qp], qp, 0, fenc);
         if (nz) {
             for (int k = 0; k < 64; k++) scan[k] = d[x264o_zigzag8[k]];
             if (b_decimate && !(e->b_trellis & TR_P8)) nz = x264o_decimate_score(scan, 64) >= 4;      /* (x264: b_decimate && !h->mb.b_trellis) */
@@ -2456,7 +2468,7 @@ static void encode_p8x8(actx *a, int i8, x264gpu_mb *mb, int16_t *lv)
         for (int k = 0; k < 4; k++) {
             const int b = 4 * i8 + k, ox = (k & 1) * 4, oy = (k >> 1) * 4;
             x264o_sub4x4_dct(d[k], fenc + oy * e->fs + ox, e->fs, rec + oy * e->rs + ox, e->rs);
-            nz[k] = quant_4x4(e, d[k], e->qt.quant4_mf[X264O_CQM_4PY][qp], e->qt.quant4_bias[X264O_CQM_4PY][qp], qp, 2, 0);
+            nz[k] = quant_4x4(e, d[k], e->qt.quant4_mf[X264O_CQM_4PY][qp], e->qt.quant4_bias[X264O_CQM_4PY][qp], qp, 2, 0, fenc + oy * e->fs + ox);
             a->nnzc[b] = (uint8_t)(nz[k] != 0);
             if (nz[k]) {
                 scan4(lv + b * 16, d[k]);
@@ -2482,7 +2494,7 @@ static void encode_p8x8(actx *a, int i8, x264gpu_mb *mb, int16_t *lv)
         for (int y = 0; y < 4; y++) for (int x = 0; x < 4; x++) { f[y * 4 + x] = fuv[y * e->fs + 2 * x + c]; p[y * 4 + x] = ruv[y * e->rs + 2 * x + c]; }
         x264o_sub4x4_dct(d, f, 4, p, 4);
         d[0] = 0;
-        const int nz = quant_4x4(e, d, e->qt.quant4_mf[X264O_CQM_4PC][qpc], e->qt.quant4_bias[X264O_CQM_4PC][qpc], qpc, 4, 0);
+        const int nz = quant_4x4(e, d, e->qt.quant4_mf[X264O_CQM_4PC][qpc], e->qt.quant4_bias[X264O_CQM_4PC][qpc], qpc, 4, 0, NULL);
         a->nnzc[16 + c * 4 + i8] = (uint8_t)(nz != 0);
         mb->nnz &= ~(1u << (16 + c * 4 + i8));
         memset(l, 0, 32);

@@ -125,12 +125,16 @@ struct Trellis {
 
 const uint32_t kW4[3] = { 800, 320, 128 };                                  // FIX8(3.125), FIX8(1.25), FIX8(0.5)
 const uint32_t kW8[6] = { 256, 201, 656, 227, 410, 363 };                   // FIX8 of 1.00000, 0.78487, 2.56132, 0.88637, 1.60040, 1.41850
-inline uint32_t weight4(int pos) { return kW4[(pos & 1) + ((pos >> 2) & 1)]; }
-inline uint32_t weight8(int pos)
+const uint32_t kP4[3] = { 453, 286, 181 };                                  // coef_weight1 (psy-trellis): FIX8(1.76777), FIX8(1.11803), FIX8(0.70711)
+const uint32_t kP8[6] = { 256, 227, 410, 241, 324, 305 };                   // FIX8 of 1.0000, 0.8859, 1.6000, 0.9415, 1.2651, 1.1910
+inline int class4(int pos) { return (pos & 1) + ((pos >> 2) & 1); }
+inline int class8(int pos)
 {
     static const uint8_t cls[4][4] = { { 0, 3, 4, 3 }, { 3, 1, 5, 1 }, { 4, 5, 2, 5 }, { 3, 1, 5, 1 } };
-    return kW8[cls[(pos >> 3) & 3][pos & 3]];
+    return cls[(pos >> 3) & 3][pos & 3];
 }
+inline uint32_t weight4(int pos) { return kW4[class4(pos)]; }
+inline uint32_t weight8(int pos) { return kW8[class8(pos)]; }
 int trellis_lambda2(int intra, int qp)
 {
     return (int)((intra ? 0.65 * 0.65 : 0.85 * 0.85) * pow(2.0, qp / 3.0 + 6.0) + 0.5);        // x264_trellis_lambda2_tab: 46, 58, 73, ... / 27, 34, 43, ...
@@ -144,7 +148,15 @@ extern "C" int x264o_unquant8(int qp, int pos);
 // dct: the block's transform coefficients in raster order (chroma DC: the 2x2 in its own order); replaced by the levels.  cat: the CABAC
 // block category (0 luma DC, 1 luma AC, 2 luma 4x4, 3 chroma DC, 4 chroma AC, 5 luma 8x8).  mf: the quantiser row of the block's list at
 // this qp.  state: the slice's 460 context variables (read only).  Returns whether a non-zero level is left.
+// psy / fenc_dct: x264's psy-trellis (--psy-rd a:b; i_psy_trellis 0..640, fenc_dct = the transform of the SOURCE block, raster order like dct): in luma blocks
+// that are not DC blocks, at scan positions above 0, a candidate level pays d * d * coef_weight2 - coef_weight1 * psy * |unquant_abs + SIGN(fenc_dct - coef, coef)|
+// (the scores are unsigned and biased: the subtraction wraps as x264's does).  tests/trellis_psy_ref.py is the same search in Python.
+extern "C" int x264o_quant_trellis_cabac_psy(dctcoef *dct, const uint16_t *mf, int qp, int cat, int intra, const uint8_t *state, int psy, const dctcoef *fenc_dct);
 extern "C" int x264o_quant_trellis_cabac(dctcoef *dct, const uint16_t *mf, int qp, int cat, int intra, const uint8_t *state)
+{
+    return x264o_quant_trellis_cabac_psy(dct, mf, qp, cat, intra, state, 0, nullptr);
+}
+extern "C" int x264o_quant_trellis_cabac_psy(dctcoef *dct, const uint16_t *mf, int qp, int cat, int intra, const uint8_t *state, int psy, const dctcoef *fenc_dct)
 {
     static const int sig_off[6] = { 105, 120, 134, 149, 152, 402 }, last_off[6] = { 166, 181, 195, 210, 213, 417 }, abs_off[6] = { 227, 237, 247, 257, 266, 426 };
     const int num_coefs = cat == 5 ? 64 : cat == 3 ? 4 : 16, b_ac = cat == 1 || cat == 4, dc = cat == 0 || cat == 3, b_chroma = cat == 3 || cat == 4;
@@ -155,6 +167,8 @@ extern "C" int x264o_quant_trellis_cabac(dctcoef *dct, const uint16_t *mf, int q
     auto zz = [&](int i) { return cat == 5 ? (int)x264o_zigzag8[i] : cat == 3 ? i : (int)x264o_zigzag4[i]; };
     auto unq = [&](int i) { return dc ? (x264o_unquant4(qp, 0) << 1) : cat == 5 ? x264o_unquant8(qp, zz(i)) : x264o_unquant4(qp, zz(i)); };
     auto wgt = [&](int i) { return dc ? 256u : cat == 5 ? weight8(zz(i)) : weight4(zz(i)); };
+    const bool b_psy = psy && fenc_dct && !dc && !b_chroma;
+    auto wgt1 = [&](int i) { return cat == 5 ? kP8[class8(zz(i))] : kP4[class4(zz(i))]; };
     memcpy(orig, dct, sizeof(dctcoef) * num_coefs);
     // the guess: round to nearest (quant_bias0 = (1 << 15) / mf), no dead zone
     {
@@ -229,6 +243,10 @@ extern "C" int x264o_quant_trellis_cabac(dctcoef *dct, const uint16_t *mf, int q
             const int abs_level = q - 1 + k, unquant_abs = (unq(i) * abs_level + 128) >> 8;
             int d = i_coef - unquant_abs;
             ssd1[k] = (uint64_t)((int64_t)d * d) * wgt(i);
+            if (b_psy && i) {
+                const int predicted = fenc_dct[zz(i)] - sign_coef;
+                ssd1[k] -= (uint64_t)wgt1(i) * (uint64_t)psy * (uint64_t)abs(unquant_abs + sign_of(predicted, sign_coef));
+            }
             ssd0[k] = ssd1[k];
             if (!i && !dc && !ctx_hi) {
                 d = sign_coef - ((sign_of(unquant_abs, sign_coef) + 8) & ~15);

@@ -12,6 +12,11 @@ from x264vfw_amd.lib import Pic
 from x264vfw_amd.gop import HostDpb, follow_of, schedule  # noqa: E402,F401
 
 
+def pic_qp(pt, qp_i, qp_p, qp_b):
+    """a picture's quantiser under fixed quantisers: a B reference takes the mean of P's and B's, as x264 does"""
+    return qp_i if pt <= 1 else qp_p if pt == 2 else qp_b if pt == 4 else (qp_p + qp_b) // 2
+
+
 def encode_gop(HL, enc, frames, types, cfg, qp_i, qp_p, qp_b, refs, bframes=3, pyramid=1, weightp=0, pics_out=None, weights=None, direct="spatial"):
     """encodes `frames` (display order) with picture types `types` through `enc` (anything with encode_pic(i420, pic) -> mbs, lv and recon());
     returns (annex-B stream, [recon per coding position], coding order, pocs)"""
@@ -25,7 +30,7 @@ def encode_gop(HL, enc, frames, types, cfg, qp_i, qp_p, qp_b, refs, bframes=3, p
     dscore = [0, 0]                  # h->stat.i_direct_score: [0] temporal, [1] spatial
     for k, (disp, pt) in enumerate(order):
         pic, info = dpb.plan(pt, disp, follow_of(order, k), weight=(weights or {}).get(disp) if pt == 2 else None)
-        pic.qp = qp_i if pt <= 1 else qp_p if pt == 2 else qp_b if pt == 4 else (qp_p + qp_b) // 2
+        pic.qp = pic_qp(pt, qp_i, qp_p, qp_b)
         if pt >= 3 and direct != "spatial":
             # --direct temporal; --direct auto: x264's running scores decide (slice_header_init), every macroblock probes both modes
             dpb.set_direct(pic, direct == "temporal" or (direct == "auto" and not dscore[1] > dscore[0]), direct == "auto")

@@ -23,7 +23,8 @@ def describe(mbs_g, mbs_o, i):
     return f"\n gpu {f(mbs_g)}\n cpu {f(mbs_o)}"
 
 
-def run(gpu, w, h, types, seed, streams=1, bframes=3, pyramid=1, weightp=0, weights=None, frames=None, qp_frac=None, direct="spatial", **over):
+def run(gpu, w, h, types, seed, streams=1, bframes=3, pyramid=1, weightp=0, weights=None, frames=None, qp_frac=None, direct="spatial", qps=(20, 23, 25), **over):
+    """qps: the quantisers of I, P and disposable B pictures (a B reference takes the mean of the last two, as x264 does under fixed quantisers)"""
     from gpu_enc import GpuEncoder
     from x264vfw_amd import host_api as HL
     kw = dict(MEDIUM, **over)
@@ -32,14 +33,14 @@ def run(gpu, w, h, types, seed, streams=1, bframes=3, pyramid=1, weightp=0, weig
     og, gg = O.OracleEncoder(cfg), GpuEncoder(O.default_config(w, h, streams=streams, **kw))
     dpb = bgop.HostDpb(HL, kw["refs"], bframes, pyramid, weightp=weightp)
     dupe_used = 0
-    stream = dpb.headers(w, h, 23, cfg.chroma_qp_offset, kw["refs"], cfg.dct8x8, cfg.weightb)
+    stream = dpb.headers(w, h, qps[1], cfg.chroma_qp_offset, kw["refs"], cfg.dct8x8, cfg.weightb)
     order = bgop.schedule(types, pyramid)
     mbw, mbh = (w + 15) // 16, (h + 15) // 16
     recons = []
     dscore, modes = [0, 0], []
     for k, (disp, pt) in enumerate(order):
         pic, _ = dpb.plan(pt, disp, bgop.follow_of(order, k), weight=(weights or {}).get(disp) if pt == 2 else None)
-        pic.qp = 20 if pt <= 1 else 23 if pt == 2 else 25 if pt == 4 else 24
+        pic.qp = bgop.pic_qp(pt, *qps)
         if qp_frac:          # a rate-controlled session's float quantiser: qp + frac / 256 (enters the AQ quantisers before the rounding)
             pic.qpm = pic.qp + qp_frac[k % len(qp_frac)] / 256.0          # (exact in a single float)
         if pt >= 3 and direct != "spatial":          # --direct temporal / auto (the running scores pick the mode as x264's slice_header_init does)
@@ -60,7 +61,7 @@ def run(gpu, w, h, types, seed, streams=1, bframes=3, pyramid=1, weightp=0, weig
             assert np.array_equal(g_lv[s], o_lv), f"picture {k}: levels differ (macroblock {np.nonzero((g_lv[s] != o_lv).any(axis=1))[0][0]})"
             assert np.array_equal(gg.recon(s), og.recon()), f"picture {k}: reconstruction differs"
         assert not kw["rd"] or not kw["cabac"] or pt <= 1 or kw["subme"] < 7 or np.array_equal(gg.cabac_states(0, max(kw.get('slices', 1), 1) - 1)[USED_CTX], og.cabac_states()[USED_CTX]), f"picture {k}: CABAC context variables differ"
-        stream += dpb.slice(mbw, mbh, pic.qp, 23, 0, 0 if cfg.deblock else 1, kw["refs"], cfg.dct8x8, g_mb[0], g_lv[0],
+        stream += dpb.slice(mbw, mbh, pic.qp, qps[1], 0, 0 if cfg.deblock else 1, kw["refs"], cfg.dct8x8, g_mb[0], g_lv[0],
                             slices=(-cfg.slices if cfg.slices_plain else cfg.slices) if cfg.slices > 1 else 1)
         recons.append(gg.recon(0))
         if pic.blind_dupe > 0:

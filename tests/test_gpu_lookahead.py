@@ -98,9 +98,9 @@ def test_aq_offsets_and_mbtree_bitexact(gpu, w, h, n, strength, with_aq):
 
 
 # ---- the lookahead in x264's structure: slicetype_frame_cost(p0, p1, b) for any triple (x264gpu_slicetype_* vs oracle/slicetype.c) ----
-def run_slicetype(w, h, n, seed, triples, streams=1, row_mode=-1, **kw):
+def run_slicetype(w, h, n, seed, triples, streams=1, row_mode=-1, frames=None, **kw):
     from gpu_enc import GpuSlicetype
-    frames = synth_frames(w, h, n, seed=seed)
+    frames = frames if frames is not None else synth_frames(w, h, n, seed=seed)
     og, gg = O.OracleSlicetype(w, h, **kw), GpuSlicetype(w, h, streams=streams, **kw)
     if row_mode >= 0:
         from x264vfw_amd import lib as gpu_lib
@@ -175,10 +175,14 @@ def test_slicetype_costs_one_wavefront_per_stream(gpu, w, h, kw):
     (80, 48, "PBPBBP", True, False, True, 9),
 ])
 def test_mbtree_through_b_pictures_bitexact(gpu, w, h, types, pyramid, b_intra, aq, seed):
+    mbtree_walk_case(w, h, types, pyramid, b_intra, aq, seed)
+
+
+def mbtree_walk_case(w, h, types, pyramid, b_intra, aq, seed, frames=None):
     from gpu_enc import GpuSlicetype
     from mbtree_walk import macroblock_tree
     n = len(types)
-    frames = synth_frames(w, h, n, seed=seed)
+    frames = frames if frames is not None else synth_frames(w, h, n, seed=seed)
     og, gg = O.OracleSlicetype(w, h, slots=n + 1, do_edges=1), GpuSlicetype(w, h, slots=n + 1, do_edges=1)
     for i, f in enumerate(frames):
         og.put(i, f); gg.put(i, [f])

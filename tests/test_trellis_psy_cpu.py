@@ -1,4 +1,4 @@
-"""psy-trellis on the CPU: (1) the pure-Python twin of the trellis search (tests/trellis_psy_ref.py) equals oracle/trellis.cpp at strength 0, block for
+"""psy-trellis on the CPU: (1) the pure-Python twin of the trellis search (tests/trellis_psy_ref.py) equals oracle/trellis.cpp at strength 0 and with the psy term, block for
 block — what makes it the yardstick of the device's psy search (tests/test_gpu_psy_trellis.py); (2) the host's rules for --psy-rd a:b (x264
 validate_parameters: clip, silent zero without psy / trellis, the chroma quantiser offset), over the host-over-oracle stub."""
 import ctypes as C
@@ -51,6 +51,31 @@ def test_twin_equals_oracle_at_strength_0(cat, intra, qp):
         assert np.array_equal(got2, got)
         if kind == "dense":
             assert np.count_nonzero(want) > nblk
+
+
+@pytest.mark.parametrize("psy", [38, 640])
+@pytest.mark.parametrize("qp,intra", [(0, 1), (26, 0), (51, 1)])
+@pytest.mark.parametrize("cat", [0, 1, 2, 3, 4, 5])
+def test_twin_equals_oracle_with_the_psy_term(cat, qp, intra, psy):
+    """oracle/trellis.cpp's own psy-trellis term (x264o_quant_trellis_cabac_psy: what the checker's macroblock loop runs under cfg.psy_trellis_q8, and
+    so what whole pictures of the device are compared with) against the twin, block for block, in every category and kind of input"""
+    f = O.L.x264o_quant_trellis_cabac_psy
+    f.argtypes, f.restype = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p], C.c_int
+    rng = np.random.default_rng(7000 + 100 * cat + 2 * qp + intra + psy)
+    nc, zz = T.ncoef(cat), np.array(T.zigzag(cat))
+    mf = np.array(T.mf_raster(cat, qp), np.uint16)
+    moved = 0
+    for kind in ("dense", "sparse", "escape"):
+        coefs, st = blocks(cat, qp, kind, 6 if cat == 5 else 16, rng), states(rng)
+        fenc = rng.integers(-12000, 12001, coefs.shape).astype(np.int16) if cat == 5 else rng.integers(-4500, 4501, coefs.shape).astype(np.int16)
+        want, _ = T.quant_trellis_blocks(coefs, cat, qp, intra, st, psy, fenc)
+        for b in range(len(coefs)):
+            raster, fr = np.zeros(nc, np.int16), np.zeros(nc, np.int16)
+            raster[zz], fr[zz] = coefs[b], fenc[b]
+            f(raster.ctypes.data, mf.ctypes.data, qp, cat, intra, st.ctypes.data, psy, fr.ctypes.data)
+            assert raster[zz].tolist() == want[b].tolist(), f"{kind} block {b}: coefs {coefs[b].tolist()} fenc {fenc[b].tolist()} oracle {raster[zz].tolist()} twin {want[b].tolist()}"
+        moved += not np.array_equal(want, T.quant_trellis_blocks(coefs, cat, qp, intra, st)[0])
+    assert moved or cat in (0, 3, 4) or psy < 640
 
 
 def test_twin_psy_term_moves_levels_only_in_luma_non_dc_blocks():

@@ -1,11 +1,11 @@
 """Serial restatement of the CABAC trellis quantiser as oracle/TRELLIS_NOTES.md states it ([x264-upstream] encoder/rdo.c quant_trellis_cabac), every
-category, the DC-only shortcut and the escape suffix, WITH the psy-trellis term (--psy-rd a:b) that oracle/trellis.cpp does not have: in luma blocks that
+category, the DC-only shortcut and the escape suffix, with the psy-trellis term (--psy-rd a:b; oracle/trellis.cpp's x264o_quant_trellis_cabac_psy is a third statement of it): in luma blocks that
 are not DC blocks (categories 1, 2, 5), at scan positions i > 0, a candidate level pays
 
     d * d * coef_weight2[zz] - coef_weight1[zz] * i_psy_trellis * abs(unquant_abs_level + SIGN(fenc_dct[zz] - coef, coef))
 
-instead of d * d * coef_weight2[zz] (fenc_dct = the transform of the SOURCE block, coef = the signed residual coefficient).  At strength 0 it is pinned to
-oracle/trellis.cpp block for block (tests/test_trellis_psy_cpu.py); the device's x264gpu_trellis_blocks_psy and the macroblock loop are checked against it.
+instead of d * d * coef_weight2[zz] (fenc_dct = the transform of the SOURCE block, coef = the signed residual coefficient).  It is pinned to
+oracle/trellis.cpp block for block, at strength 0 and above (tests/test_trellis_psy_cpu.py); the device's x264gpu_trellis_blocks_psy and the macroblock loop are checked against it.
 Test infrastructure: pure Python, blocks in SCAN order; the entropy table is csrc/cabac_entropy.inc, the 8x8 context increments host/cabac_tables.hpp."""
 import os
 import re
