@@ -363,6 +363,27 @@ int x264gpu_picture_quality(const uint8_t *d_a, const uint8_t *d_b, int n, int w
  * context's own source planes and the reconstruction in its DPB slot, compared where they lie over the visible width x height (the same device code as the
  * primitive).  Queued on `stream` behind the encode call it needs no host synchronisation; d_out[streams].  EINVAL before any encode call */
 int x264gpu_encoder_quality(x264gpu_encoder *enc, int flags, x264gpu_quality *d_out /* [streams] */, void *stream);
+/* --nr ([x264-upstream] encoder/encoder.c x264_noise_reduction_update, common/quant.c denoise_dct): the transformed residual of INTER blocks loses a per-position
+ * offset before it is quantised.  Categories: 0 = luma 4x4 (16 entries used), 1 = luma 8x8 (64), 2 = chroma 4x4 (16); the index is the raster position in the
+ * block's transform array, as x264gpu_dctq4x4 / x264gpu_dctq8x8 return `coef`.  denoise of a coefficient d at index i: a = |d|, sum[cat][i] += a, a -= off[cat][i],
+ * d = a < 0 ? 0 : sign(d) * a.  off[cat][0] is always 0 (DC is never denoised); entries 16..63 of categories 0 and 2 are 0 and unused. */
+typedef struct x264gpu_nr_offsets { uint16_t off[3][64]; } x264gpu_nr_offsets;
+typedef struct x264gpu_nr_sums { uint64_t sum[3][64]; uint32_t count[3], pad; } x264gpu_nr_sums;
+/* The following encode calls through this launch context denoise every inter residual they transform — final encodes, RD candidates, skip probes — with
+ * d_off[stream], and OVERWRITE d_pic[stream] with the picture's own statistics: the sums of |coefficient| and the block counts of the FINAL encode of its inter
+ * macroblocks that are not P_Skip / B_Skip (an I picture: zeros; a macroblock whose 8x8 transform left no luma level is recorded without transform_size_8x8_flag
+ * and counts as sixteen 4x4 blocks: the statistics follow the records).  The call stays a pure function of its arguments: it never reads d_pic and never writes d_off, so a
+ * re-issued picture is exact.  NULL, NULL returns to the plain kernels.  EINVAL unless the session is what the denoising instantiations of the macroblock loop are
+ * built for: cabac, rd, trellis, subme >= 6, me_method 1 / 2, a DPB-model session (cfg.dpb > 0), no psy-trellis.  Both arrays must stay valid while calls use them. */
+int x264gpu_encoder_set_nr(x264gpu_encoder *enc, const x264gpu_nr_offsets *d_off /* [streams] */, x264gpu_nr_sums *d_pic /* [streams] */);
+/* x264_noise_reduction_update per stream, queued on `stream`: d_state += d_pic (d_pic NULL: the state as it is); per category, a count above 1 << 18 (category 1:
+ * 1 << 16) halves the sums and the count; then, in 64-bit integers, off[cat][i] = min((strength * count + sum / 2) / (sum * weight2[cat][i] / 256 + 1), 32767)
+ * (x264 lets a uint16 wrap; no coefficient exceeds int16, so the clamp zeroes what the true value would zero), off[cat][0] = 0.  weight2: the squared-norm weights
+ * of the transforms (FIX8: 4x4 800 / 320 / 128 by the number of odd coordinates, 8x8 by normAdjust8x8 class).  strength 0..65536. */
+int x264gpu_nr_update(x264gpu_nr_offsets *d_off, x264gpu_nr_sums *d_state, const x264gpu_nr_sums *d_pic, int streams, int strength, void *stream);
+/* primitive (tier 1): the macroblock loop's own denoise function over nblk blocks of category cat (16 coefficients a block, 64 for category 1; raster order), in
+ * place, with d_off[0]; d_out[0] (or NULL) receives the sums of |coefficient| before the offsets and count[cat] = nblk (the other categories 0). */
+int x264gpu_denoise_blocks(int16_t *d_coefs, int nblk, int cat, const x264gpu_nr_offsets *d_off, x264gpu_nr_sums *d_out, void *stream);
 /* Per-stage device timing for bench.py (HIP events on the caller's stream, no host sync in the timed
  * region): profile_begin arms up to max_calls encode_frames calls; profile_end synchronises the stream
  * and returns, per stage, the summed milliseconds and the number of launches that ran. */

@@ -69,6 +69,9 @@ int x264host_last_quality(x264_t *h, double psnr[4] /* Y U V Avg */, double *ssi
  * returns the length without the terminating 0 (the text is cut at cap - 1), -1 when the session runs without the flags */
 int x264host_quality_summary(x264_t *h, char *buf, int cap);
 /* x264_psnr: 100 when ssd / (255^2 n) <= 1e-10, else -10 log10 of it; x264_ssim: 100 when 1 - ssim <= 1e-10, else -10 log10(1 - ssim) */
+/* --nr (analyse.i_noise_reduction): the offsets the NEXT picture of the session will be denoised with, [category 0 luma 4x4, 1 luma 8x8, 2 chroma 4x4][raster index]
+ * (x264gpu_nr_update's, behind every accepted picture; waits for the device).  -1 (and zeros): the session runs nr 0 */
+int x264host_nr_offsets(x264_t *h, uint16_t out[3][64]);
 double x264host_psnr(double ssd, double n);
 double x264host_ssim_db(double ssim);
 

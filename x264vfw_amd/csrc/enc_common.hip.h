@@ -97,6 +97,9 @@ struct EncK {
     int slices_plain;         // x264 --slices N rather than slice threads: the loop filter crosses slice boundaries
     unsigned long long *prof; // MB_PROF builds only: [streams][16] cycle counters of the macroblock loop's phases (null otherwise)
     int psy_trellis;          // x264 i_psy_trellis (cfg.psy_trellis_q8): non-zero = the psy instantiations of the macroblock loop (last: no other field moves)
+    // x264 --nr (x264gpu_encoder_set_nr; behind everything else: no other field moves): non-null = the denoising instantiations of the macroblock loop (mb_slice_nr_*.hip).
+    // nr_off[streams] the offsets they apply, nr_part[streams][slices] the statistics of every slice's final encodes (each slice's wavefront owns its row)
+    const x264gpu_nr_offsets *nr_off; x264gpu_nr_sums *nr_part;
 };
 // the slice quantiser of stream s
 __device__ __forceinline__ int slice_qp(const EncK &k, int s) { return k.stream_qp ? (int)k.stream_qp[s] : k.qp; }

@@ -28,6 +28,8 @@ void launch_mb_slice_b_dia(const EncK &k, int streams, hipStream_t st);
 void launch_mb_slice_b_umh(const EncK &k, int streams, hipStream_t st);
 void launch_mb_slice_b_esa(const EncK &k, int streams, hipStream_t st);
 void launch_mb_slice_psy(const EncK &k, int streams, int slice_type, hipStream_t st);       // psy-trellis sessions (mb_slice_psy_*.hip): I, P and B slices, --me hex / umh
+void launch_mb_slice_nr(const EncK &k, int streams, int slice_type, hipStream_t st);        // --nr (x264gpu_encoder_set_nr; mb_slice_nr_*.hip): P and B slices, --me hex / umh
+void launch_nr_gather(const x264gpu_nr_sums *part, int slices, x264gpu_nr_sums *pic, int streams, hipStream_t st);      // nr_kernels.hip
 int trellis_table_ptrs(const uint16_t **su, const uint8_t **tu, const int **l2);        // prim_kernels.hip
 int cabac_chain_table(const uint32_t **out);                                              // prim_kernels.hip
 int launch_hpel_filter(uint8_t *planes, size_t plane_bytes, int stride, int w, int h, int pad, int batch,
@@ -66,6 +68,8 @@ struct x264gpu_encoder {
     unsigned long long *prof = nullptr;  // MB_PROF builds: phase counters of the last macroblock-loop launch
     int *wf_progress = nullptr;          // [streams][2][WFG_ROWS] row counters of the multi-workgroup wavefront kernels
     void *qslab = nullptr;               // x264gpu_encoder_quality: the workgroup partials of the pass (allocated by the first call)
+    // --nr (x264gpu_encoder_set_nr): the caller's offsets and per-picture statistics ([streams] each; null = the plain kernels), this context's per-slice rows
+    const x264gpu_nr_offsets *nr_off = nullptr; x264gpu_nr_sums *nr_pic = nullptr, *nr_part = nullptr;
     // adaptive quantisation: per-macroblock quantisers and the per-quantiser tables (built when aq_mode != 0)
     uint8_t *mbqp = nullptr;
     const float *ext_off = nullptr;      // quantiser offsets handed in by the caller (lookahead), [streams][nmb] single floats
@@ -310,6 +314,7 @@ void x264gpu_encoder_destroy(x264gpu_encoder *e)
     for (int i = 0; i < 8; i++) (void)hipFree(e->mvr[i]);
     (void)hipFree(e->wf_progress);
     (void)hipFree(e->qslab);
+    (void)hipFree(e->nr_part);
     (void)hipFree(e->tc);
     (void)hipFree(e->amvd);
     (void)hipFree(e->cab_out);
@@ -320,6 +325,21 @@ void x264gpu_encoder_destroy(x264gpu_encoder *e)
 }
 
 int x264gpu_encoder_mb_count(const x264gpu_encoder *e) { return e ? e->k.nmb : 0; }
+// --nr: the following encode calls of this launch context run the denoising instantiations of the macroblock loop (built for what the checks below name)
+int x264gpu_encoder_set_nr(x264gpu_encoder *e, const x264gpu_nr_offsets *d_off, x264gpu_nr_sums *d_pic)
+{
+    ARG_TRY(e && (d_off != nullptr) == (d_pic != nullptr));
+    if (!d_off) { e->nr_off = nullptr; e->nr_pic = nullptr; return X264GPU_OK; }
+    ARG_TRY(e->cfg.cabac && e->cfg.rd && e->cfg.trellis && e->cfg.subme >= 6 && (e->cfg.me_method == 1 || e->cfg.me_method == 2) && e->cfg.dpb > 0 && !e->cfg.psy_trellis_q8);
+    if (!e->nr_part) {
+        const size_t n = (size_t)e->cfg.streams * (e->cfg.slices > 1 ? e->cfg.slices : 1) * sizeof(x264gpu_nr_sums);
+        hipError_t er = hipMalloc((void **)&e->nr_part, n);
+        if (er == hipSuccess) er = hipMemset(e->nr_part, 0, n);
+        if (er != hipSuccess) return set_err(er == hipErrorOutOfMemory ? X264GPU_ENOMEM : X264GPU_EHIP, "nr rows", er);
+    }
+    e->nr_off = d_off; e->nr_pic = d_pic;
+    return X264GPU_OK;
+}
 int x264gpu_encoder_set_debug(x264gpu_encoder *e, void *d_counters) { ARG_TRY(e); e->dbg = (unsigned long long *)d_counters; return X264GPU_OK; }
 int x264gpu_encoder_stage_count(void) { return (int)(sizeof(kStageNames) / sizeof(kStageNames[0])); }
 const char *x264gpu_encoder_stage_name(int i) { return i >= 0 && i < x264gpu_encoder_stage_count() ? kStageNames[i] : ""; }
@@ -560,6 +580,7 @@ static int encode_core(x264gpu_encoder *e, const uint8_t *d_i420, const x264gpu_
     k.sl_stat = slice_type != X264GPU_SLICE_I && e->sl_stat ? e->sl_stat + (size_t)(!bslice ? 0 : pic.keep ? 1 : 2) * S * (size_t)e->cfg.slices * 4 : nullptr;      // the first guess: the last picture of the same kind
     k.sl_rerun = e->sl_rerun; k.sl_pass = 0;
     k.psy_trellis = e->cfg.psy_trellis_q8;
+    k.nr_off = slice_type == X264GPU_SLICE_I ? nullptr : e->nr_off; k.nr_part = e->nr_part;          // (I slices hold no inter residual: the plain kernels)
     k.trellis = e->cfg.trellis; k.tr_su = nullptr; k.tr_tu = nullptr; k.tr_l2 = nullptr;
     if (k.trellis) { const int rc = trellis_table_ptrs(&k.tr_su, &k.tr_tu, &k.tr_l2); if (rc != X264GPU_OK) return rc; }
     k.ctab = nullptr;
@@ -592,7 +613,7 @@ static int encode_core(x264gpu_encoder *e, const uint8_t *d_i420, const x264gpu_
     else {
         const auto launch_b = k.me_method == 0 ? launch_mb_slice_b_dia : k.me_method == 2 ? launch_mb_slice_b_umh : k.me_method == 3 ? launch_mb_slice_b_esa : launch_mb_slice_b_hex;
         const auto launch_p = k.me_method == 0 ? launch_mb_slice_dia : k.me_method == 2 ? launch_mb_slice_umh : k.me_method == 3 ? launch_mb_slice_esa : launch_mb_slice_hex;
-        const auto launch = [&](const EncK &kk, int streams, bool big_margin, hipStream_t s_) { if (kk.psy_trellis) launch_mb_slice_psy(kk, streams, bslice ? X264GPU_SLICE_B : X264GPU_SLICE_P, s_); else if (bslice) launch_b(kk, streams, s_); else launch_p(kk, streams, big_margin, s_); };
+        const auto launch = [&](const EncK &kk, int streams, bool big_margin, hipStream_t s_) { if (kk.nr_off) launch_mb_slice_nr(kk, streams, bslice ? X264GPU_SLICE_B : X264GPU_SLICE_P, s_); else if (kk.psy_trellis) launch_mb_slice_psy(kk, streams, bslice ? X264GPU_SLICE_B : X264GPU_SLICE_P, s_); else if (bslice) launch_b(kk, streams, s_); else launch_p(kk, streams, big_margin, s_); };
         if (k.sl_stat) hipLaunchKernelGGL(k_slice_priors, dim3((S + 63) / 64), dim3(64), 0, st, k, S, 1);
         launch(k, S, k.subme >= 8, st);
         // --slices N: slice i is final once slices 0..i-1 are, so slices - 1 rounds of "check the assumed counts, run the slices again whose
@@ -604,6 +625,11 @@ static int encode_core(x264gpu_encoder *e, const uint8_t *d_i420, const x264gpu_
                 launch(k, S, k.subme >= 8, st);
             }
         k.sl_pass = 0;
+    }
+    // --nr: the picture's statistics — the sum of the rows its slices' last passes left; an I picture has none
+    if (e->nr_pic) {
+        if (k.nr_off) launch_nr_gather(e->nr_part, k.slices > 1 ? k.slices : 1, e->nr_pic, S, st);
+        else HIP_TRY(hipMemsetAsync(e->nr_pic, 0, (size_t)S * sizeof(x264gpu_nr_sums), st));
     }
     if (e->cfg.dpb > 0 && pic.keep) hipLaunchKernelGGL(k_col_from_records, dim3((k.nmb * 4 + 255) / 256, S), dim3(256), 0, st, k);
     mask |= 2;

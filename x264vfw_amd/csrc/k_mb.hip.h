@@ -873,6 +873,7 @@ __device__ __forceinline__ int pick_intra_mode(F raw, int avail, int pm, int lam
 }  // namespace x264gpu
 #include "cabac_rd.hip.h"          // needs the motion cache and the intra-mode helpers above
 #include "trellis.hip.h"
+#include "nr.hip.h"
 namespace x264gpu {
 
 // The trellis sites of a macroblock's FINAL encode (x264 --trellis 1; k.trellis = the mask of sites, 63 = all): what they need to run the
@@ -1249,8 +1250,11 @@ __device__ __forceinline__ int mb_intra_chroma_cost(const EncK &k, MbLds<M> &L, 
 // 4x4 block = (lane >> 2) & 3, row = lane & 3.
 // ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ uint32_t mb_chroma_residual(uint32_t enc, uint32_t pred, const Q4 &q, bool inter, bool decimate, int lane, int16_t *lv,
-                                                       unsigned &nnz_bits, int &cbp_chroma, const TrCtx *tr = nullptr)
+                                                       unsigned &nnz_bits, int &cbp_chroma, const TrCtx *tr = nullptr,
+                                                       const uint16_t *nro = nullptr, uint16_t *nr_pend = nullptr)
 {
+    // nro (the denoising instantiations, inter macroblocks only): the stream's offsets in LDS — the blocks are denoised before the 2x2 DC is taken out (its
+    // offset is 0); nr_pend (the final encode): the blocks' |coefficient| values go there first (nr.hip.h nr_stash4)
     const bool trellis = tr && (tr->on & TR_C);          // final encode of a trellis session: both quantisers below are the search (lv = LDS)
     lane = relane(lane);
     const int c = (lane >> 4) & 1, i = (lane >> 2) & 3, j = lane & 3;
@@ -1270,6 +1274,10 @@ __device__ __forceinline__ uint32_t mb_chroma_residual(uint32_t enc, uint32_t pr
         et_drop_dc = sq <= thresh;
     }
     dct4_quad(v, lane);
+    if (nro) {
+        if (nr_pend) nr_stash4<32>(v, lane, nr_pend);
+        nr_denoise4(v, nro + NR_OC, lane);
+    }
     int dcs[4];
 #pragma unroll
     for (int b = 0; b < 4; b++) dcs[b] = __shfl(v[0], (lane & 48) + 4 * b);
@@ -1389,7 +1397,8 @@ __device__ __forceinline__ void mb_store_chroma(uint8_t *ruv, int rs, int lane, 
 // x264_macroblock_probe_skip_internal (oracle probe_skip_pred): would the residual of this prediction code to nothing?  pred: this lane's luma row
 // (Z layout); cenc / cpred: lanes 0..31 = chroma plane (lane >> 4) & 1, 4x4 block (lane >> 2) & 3, row lane & 3
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ bool mb_probe_skip_pred(const MbCtx &c, uint32_t cz, uint32_t pred, uint32_t cenc, uint32_t cpred, const Q4 &ql, const Q4 &qc)
+// nro (the denoising instantiations): the stream's offsets in LDS — both residuals are denoised before they are quantised
+__device__ __forceinline__ bool mb_probe_skip_pred(const MbCtx &c, uint32_t cz, uint32_t pred, uint32_t cenc, uint32_t cpred, const Q4 &ql, const Q4 &qc, const uint16_t *nro = nullptr)
 {
     const int lane = relane(c.lane), j = lane & 3;
     bool ok;
@@ -1399,6 +1408,7 @@ __device__ __forceinline__ bool mb_probe_skip_pred(const MbCtx &c, uint32_t cz, 
 #pragma unroll
         for (int i = 0; i < 4; i++) v[i] = e[i] - p[i];
         dct4_quad(v, lane);
+        if (nro) nr_denoise4(v, nro + NR_O4, lane);
         quant4_row(v, ql, j);
         const unsigned mask = (unsigned)quad_or((int)scan_mask(v, j));
         const int big = quad_or(any_big(v) ? 1 : 0);
@@ -1414,6 +1424,7 @@ __device__ __forceinline__ bool mb_probe_skip_pred(const MbCtx &c, uint32_t cz, 
         const int thresh = (c_lambda2_tab[qc.qp] + 32) >> 6;
         const int ssd = row16_sum(v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3]);
         dct4_quad(v, lane);
+        if (nro) nr_denoise4(v, nro + NR_OC, lane);
         int dcs[4];
 #pragma unroll
         for (int b = 0; b < 4; b++) dcs[b] = __shfl(v[0], (lane & 48) + 4 * b);
@@ -1436,7 +1447,7 @@ __device__ __forceinline__ bool mb_probe_skip_pred(const MbCtx &c, uint32_t cz, 
 }
 
 // x264_macroblock_probe_pskip (oracle probe_pskip): would the macroblock code to nothing at the skip vector?
-__device__ __forceinline__ bool mb_probe_pskip(const EncK &k, const MbCtx &c, uint32_t cz, int pmx, int pmy, const Q4 &ql, const Q4 &qc)
+__device__ __forceinline__ bool mb_probe_pskip(const EncK &k, const MbCtx &c, uint32_t cz, int pmx, int pmy, const Q4 &ql, const Q4 &qc, const uint16_t *nro = nullptr)
 {
     const int lane = relane(c.lane), j = lane & 3, zx = z_x0(lane), zy = z_y(lane);
     const int mvx = clampi(pmx, c.mvmin0, c.mvmax0), mvy = clampi(pmy, c.mvmin1, c.mvmax1);
@@ -1447,7 +1458,7 @@ __device__ __forceinline__ bool mb_probe_pskip(const EncK &k, const MbCtx &c, ui
     mc_chroma_row4(ref_chroma00(k, c.s, 0), k.rs, c.mbx * 8 + cx0, c.mby * 8 + cyy, mvx, mvy, pu, pv);
     if (k.wc_any) { if (k.wc0[0] >> 24) pu = wp4(pu, k.wc0[0]); if (k.wc0[1] >> 24) pv = wp4(pv, k.wc0[1]); }
     const uint2 fe = *(const uint2 *)(c.fuv + (size_t)cyy * k.fs + 2 * cx0);
-    return mb_probe_skip_pred(c, cz, pred, nv12_pick(fe.x, fe.y, pl), pl ? pv : pu, ql, qc);
+    return mb_probe_skip_pred(c, cz, pred, nv12_pick(fe.x, fe.y, pl), pl ? pv : pu, ql, qc, nro);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1550,10 +1561,18 @@ __device__ __forceinline__ void b_predict(const EncK &k, const MbCtx &c, const B
 // BS: B slice (PS is set as well: an inter slice) — RD instantiations with CABAC only; its own analysis and candidate order (k_mb_b.inc)
 // PSY: psy-trellis (cfg.psy_trellis_q8 != 0; RD >= 3 only) — instantiations of their own (mb_slice_psy_*.hip): the source transform of every macroblock in
 // LDS (1 KB beside MbLds: these instantiations alone give up the eighth wavefront a CU) and the psy variant of the search at the luma sites
-template <int M, int ME, bool PS, int RD = 0, bool BS = false, bool PSY = false>
+// NR: x264 --nr (x264gpu_encoder_set_nr; RD >= 3 inter slices without PSY) — instantiations of their own (mb_slice_nr_*.hip): every inter residual the loop
+// transforms (final encodes, RD candidates, sub-block encodes of the refinement, skip probes) is denoised with the stream's offsets before it is quantised.  The
+// offsets in use are staged once per slice (96 of them, 192 B of LDS: with them the loop still fits eight wavefronts a CU).  Statistics take the FINAL encode of the inter macroblocks
+// that do not end as skips: a macroblock's |coefficient| values wait in L.lv4 / L.lv8 (the intra analysis' levels, dead once an inter macroblock is being
+// committed) until its type is known, then lanes add their sums per index into the slice's own row of k.nr_part — 64-bit sums (a coefficient is below 2^15 and the largest picture,
+// 4096x2304, has 589 824 4x4 luma blocks: a sum stays below 2^35; 32 bits would wrap), no atomics: a row has one writer, entry i always through lane i, and a
+// repeated slice pass of --slices N starts its row again, so a macroblock's final encode counts exactly once
+template <int M, int ME, bool PS, int RD = 0, bool BS = false, bool PSY = false, bool NR = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MB_WAVES_PER_EU, 4))) void k_mb_slice(EncK k)
 {
     static_assert(!PSY || RD >= 3, "psy-trellis: instantiations with the trellis quantiser");
+    static_assert(!NR || (RD >= 3 && PS && !PSY), "nr: inter slices of trellis sessions, without psy-trellis");
     using TRC = std::conditional_t<PSY, TrCtxPsy, TrCtx>;
     __shared__ __attribute__((aligned(16))) int16_t psy_fd[PSY ? 512 : 1];          // (referenced in PSY instantiations only: the others allocate nothing)
     static_assert(!BS || PS, "B slices are inter slices");
@@ -1598,8 +1617,21 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MB_WAVES_PER
     int intra_count = intra_prior, cost_qp = -1;          // intra macroblocks so far: of the slice (slice threads), of the picture (--slices N)
     // RD instantiation: levels of the candidate being costed (and of the final macroblock, before they go out), total_coeff of the left / top
     // macroblocks' blocks for the nC of the bit counts; the quantiser the previous coded macroblock left (mb_qp_delta bits)
-    __shared__ __attribute__((aligned(16))) int16_t rd_lvs[RD ? X264GPU_MB_LEVELS : 1];
+    __shared__ __attribute__((aligned(16))) int16_t rd_lvs[RD ? X264GPU_MB_LEVELS + (NR ? NR_OFF_N : 0) : 1];          // (NR: + the stream's offsets behind the levels, below)
     __shared__ uint8_t rd_ntc[2][RD == 1 ? 24 : 1];
+    const uint16_t *nro = nullptr;          // NR: the stream's offsets in LDS (nr.hip.h NR_O4 / NR_OC / NR_O8), what the helpers above take
+    x264gpu_nr_sums *nr_row = nullptr;      // ... and this slice's row of statistics: lane i owns sum[.][i], lanes 0..2 the counts
+    if constexpr (NR) {
+        // (behind the level buffer, not an LDS variable of their own: one more variable moves the others in the kernel's LDS block, and the P instantiations then
+        //  need 256 registers and spill 10 - 100 of them where their plain siblings need 226 - 233 and spill none; profiles/nr.md)
+        nro = (const uint16_t *)(rd_lvs + X264GPU_MB_LEVELS);
+        const uint32_t *src = (const uint32_t *)(k.nr_off + s);
+        if (lane < NR_OFF_N / 2) ((uint32_t *)(rd_lvs + X264GPU_MB_LEVELS))[lane] = src[nr_stage_src(lane)];
+        nr_row = k.nr_part + (size_t)s * nsl + blockIdx.y;
+        nr_row->sum[0][lane] = 0; nr_row->sum[1][lane] = 0; nr_row->sum[2][lane] = 0;
+        if (lane < 4) (&nr_row->count[0])[lane] = 0;          // (count[3] and the padding behind it)
+    }
+    if constexpr (NR) lds_sync();
 #ifdef X264GPU_POISON
     for (int i = lane; i < (RD ? X264GPU_MB_LEVELS : 1); i += 64) rd_lvs[i] = (int16_t)0xCDCD;
     __builtin_amdgcn_s_waitcnt(0); __builtin_amdgcn_wave_barrier();
@@ -1815,7 +1847,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MB_WAVES_PER
             if (k.fast_pskip) {
                 if (c.subme >= 3) try_skip = true;
                 else if (type_left == X264GPU_MB_P_SKIP || type_top == X264GPU_MB_P_SKIP || type_tl == X264GPU_MB_P_SKIP || type_tr == X264GPU_MB_P_SKIP)
-                    pskip = mb_probe_pskip(k, c, cz, pskx, psky, q_lp, q_cp);
+                    pskip = mb_probe_pskip(k, c, cz, pskx, psky, q_lp, q_cp, nro);
             }
             pf.mark(PH_PSKIP);
             if (pskip) {
@@ -1956,7 +1988,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MB_WAVES_PER
                         mo[0] = (int16_t)mvx; mo[1] = (int16_t)mvy;
                     }
                     wl(S.mvcx, lane, r * 5, mvx); wl(S.mvcy, lane, r * 5, mvy);
-                    if (r == 0 && try_skip && cost - cost_mv < 300 * c.lambda && abs(mvx - pskx) + abs(mvy - psky) <= 1 && mb_probe_pskip(k, c, cz, pskx, psky, q_lp, q_cp)) {
+                    if (r == 0 && try_skip && cost - cost_mv < 300 * c.lambda && abs(mvx - pskx) + abs(mvy - psky) <= 1 && mb_probe_pskip(k, c, cz, pskx, psky, q_lp, q_cp, nro)) {
                         pskip = true; done = true;
                         if (lane >= 1 && lane < c.nref) { int16_t *m = k.mvr[lane] + ((size_t)s * k.nmb + mbi) * 2; m[0] = 0; m[1] = 0; }
                         continue;
@@ -2288,6 +2320,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MB_WAVES_PER
 #pragma unroll
                     for (int i = 0; i < 8; i++) v[i] = e[i] - p[i];
                     fwd8_1d(v); transpose8(v, lane); fwd8_1d(v); transpose8(v, lane);
+                    if constexpr (NR) nr_denoise8(v, nro + NR_O8, lane);
                     int mf[4], bs[4], dq[4];
                     q8_row(q8p, row, mf, bs, dq);
                     unsigned mlo = 0, mhi = 0, big = 0;
@@ -2349,6 +2382,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MB_WAVES_PER
 #pragma unroll
                     for (int i = 0; i < 4; i++) v[i] = e[i] - p[i];
                     dct4_quad(v, lane);
+                    if constexpr (NR) nr_denoise4(v, nro + NR_O4, lane);
                     if (TRL2 && (trc.on & TR_P4)) {
                         store_levels_scan(lvw + (lane >> 2) * 16, v, j4);
                         lds_sync();
@@ -2403,6 +2437,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MB_WAVES_PER
 #pragma unroll
                     for (int t = 0; t < 4; t++) v[t] = act ? e[t] - p[t] : 0;
                     dct4_quad(v, lane);
+                    if constexpr (NR) nr_denoise4(v, nro + NR_OC, lane);
                     if (j4 == 0) v[0] = 0;
                     int16_t *l = lvw + X264GPU_LV_CHROMA_AC + (pl * 4 + ci) * 16;
                     if (TRL2 && (trc.on & TR_C)) {
@@ -2604,6 +2639,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MB_WAVES_PER
 #pragma unroll
                     for (int i = 0; i < 8; i++) v[i] = e[i] - p[i];
                     fwd8_1d(v); transpose8(v, lane); fwd8_1d(v); transpose8(v, lane);
+                    if constexpr (NR) { if (commit) nr_stash8(v, lane, (uint16_t *)L.lv4); nr_denoise8(v, nro + NR_O8, lane); }
                     int mf[4], bs[4], dq[4];
                     q8_row(q8p, row, mf, bs, dq);
                     unsigned mlo = 0, mhi = 0, big = 0;
@@ -2673,6 +2709,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MB_WAVES_PER
 #pragma unroll
                     for (int i = 0; i < 4; i++) v[i] = e[i] - p[i];
                     dct4_quad(v, lane);
+                    if constexpr (NR) { if (commit) nr_stash4<64>(v, lane, (uint16_t *)L.lv4); nr_denoise4(v, nro + NR_O4, lane); }
                     if (TRL && (trc.on & TR_P4)) {
                         store_levels_scan(lvw + (lane >> 2) * 16, v, j4);
                         lds_sync();
@@ -2713,7 +2750,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MB_WAVES_PER
                 pf.mark2(25);
                 const uint2 fe = *(const uint2 *)(L.csrc + cyy * 16 + 2 * cx0);
                 const uint32_t cenc = nv12_pick(fe.x, fe.y, pl);
-                const uint32_t crec = mb_chroma_residual(cenc, cpred, q_cp, true, k.dct_decimate != 0, lane, lvw, nnz, cbp_chroma, TRL ? &trc : nullptr);
+                uint16_t *nr_pend = nullptr;
+                if constexpr (NR) nr_pend = commit ? (uint16_t *)L.lv8 : nullptr;
+                const uint32_t crec = mb_chroma_residual(cenc, cpred, q_cp, true, k.dct_decimate != 0, lane, lvw, nnz, cbp_chroma, TRL ? &trc : nullptr, nro, nr_pend);
                 pf.mark2(26);
                 if (commit) mb_store_chroma(ruv, k.rs, lane, crec);
                 if constexpr (RD) { if (lane < 32) ssd_c = ssd4_u8(cenc, crec); }
@@ -2726,6 +2765,30 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MB_WAVES_PER
                     rec_type = X264GPU_MB_P_SKIP;
                 // B_DIRECT with nothing coded: B_SKIP
                 if (BS && e_type == X264GPU_MB_B_DIRECT && !(cbp_luma | cbp_chroma)) rec_type = X264GPU_MB_B_SKIP;
+                if constexpr (NR) {
+                    // the statistics of a final encode that stays an inter macroblock: what waited in L.lv4 / L.lv8 joins the slice's row (lane i entry i, as every time)
+                    if (commit && rec_type != X264GPU_MB_P_SKIP && rec_type != X264GPU_MB_B_SKIP) {
+                        // (the statistics are a function of the coded picture: a macroblock whose 8x8 transform left no luma level is recorded — and decoded —
+                        //  without transform_size_8x8_flag, so it counts as sixteen 4x4 blocks of the same residual)
+                        const bool s8 = t8 && cbp_luma != 0;
+                        if (t8 && !s8) {
+                            int e[4], p[4], v[4];
+                            unpack4(enc, e); unpack4(pred, p);
+#pragma unroll
+                            for (int i = 0; i < 4; i++) v[i] = e[i] - p[i];
+                            dct4_quad(v, lane);
+                            lds_sync();
+                            nr_stash4<64>(v, lane, (uint16_t *)L.lv4);
+                        }
+                        lds_sync();
+                        const uint16_t *pl = (const uint16_t *)L.lv4, *pc = (const uint16_t *)L.lv8;
+                        const int ln = relane(lane0);          // (afresh: see nr.hip.h)
+                        if (s8) nr_row->sum[1][ln] += nr_pend_sum(pl, ln, 4, 64);
+                        else if (ln < 16) nr_row->sum[0][ln] += nr_pend_sum(pl, ln, 16, 16);
+                        if (ln < 16) nr_row->sum[2][ln] += nr_pend_sum(pc, ln, 8, 16);
+                        if (ln < 3) nr_row->count[ln] += ln == 2 ? 8u : ln == (s8 ? 1 : 0) ? (s8 ? 4u : 16u) : 0u;
+                    }
+                }
             }
             pf.mark(PH_ENC_INTER);
         } else {

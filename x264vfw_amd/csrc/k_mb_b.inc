@@ -141,7 +141,7 @@ for (;; rd_ph++) {
             if (!d_avail) continue;
             b_predict(k, c, dcfg, biwv, dpred, dcpred);
             if (k.direct_auto) {
-                probed = mb_probe_skip_pred(c, cz, dpred, b_cenc, dcpred, q_lp, q_cp);
+                probed = mb_probe_skip_pred(c, cz, dpred, b_cenc, dcpred, q_lp, q_cp, nro);
                 if (probed) { if (tmp) ds_t++; else ds_s++; }
             }
         }
@@ -153,7 +153,7 @@ for (;; rd_ph++) {
             // also wants both lists' first 16x16 searches to land on the direct vectors (try_skip), below it the probe decides
             // (--direct auto: the probe of the slice's mode above stands and decides alone; no direct prediction: no skip)
             bool b_skip_now = false;
-            if (d_avail && !k.direct_auto) { try_skip = mb_probe_skip_pred(c, cz, dpred, b_cenc, dcpred, q_lp, q_cp); b_skip_now = c.subme < 3 && try_skip; }
+            if (d_avail && !k.direct_auto) { try_skip = mb_probe_skip_pred(c, cz, dpred, b_cenc, dcpred, q_lp, q_cp, nro); b_skip_now = c.subme < 3 && try_skip; }
             else if (d_avail) b_skip_now = probed;
             pf.mark(PH_PSKIP);
             if (b_skip_now) {

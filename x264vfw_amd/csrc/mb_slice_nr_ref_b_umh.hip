@@ -1,0 +1,12 @@
+// mb_slice_nr_ref_b_umh.hip — the macroblock-loop kernel (k_mb.hip.h) with noise reduction (x264gpu_encoder_set_nr: the NR instantiations, which denoise every inter
+// residual they transform with the stream's offsets and gather the statistics of the final encodes), B slices under --me umh at --subme 9 (RD refinement), trellis 1 (RD 5) and trellis 2 (RD 6); a translation unit of its own so
+// that the instantiations build in parallel.  The selection mirrors the psy units'.
+#include "k_mb.hip.h"
+
+namespace x264gpu {
+void launch_mb_slice_nr_ref_b_umh(const EncK &k, int streams, hipStream_t st)
+{
+    if (k.trellis & 64) mb_launch(k_mb_slice<5, 2, true, 6, true, false, true>, k, streams, st);
+    else mb_launch(k_mb_slice<5, 2, true, 5, true, false, true>, k, streams, st);
+}
+}  // namespace x264gpu

@@ -4,6 +4,8 @@
 // condition variable; whoever changes what they look at (launched, closed, a session's hurry flag) notifies under the group's lock.
 #include "batch.hpp"
 #include "quality.hpp"
+#include "noisereduction.hpp"
+#include <string.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <algorithm>
@@ -27,6 +29,8 @@ struct BatchGroup {
     // (~10 % at medium; dense, 2048 members x 7 MB a round were what the first rounds waited for: fresh pages of the download buffers, 15 GB a round over the link)
     bool pack = false; x264gpu_level_index *d_ix = nullptr, *d_ix2 = nullptr;
     int qflags = 0; x264gpu_quality *d_q = nullptr, *d_q2 = nullptr;          // --psnr / --ssim of the members (all alike): one statistic per stream behind every round, two buffers as d_mb / d_mb2
+    // --nr of the members (one strength a group): per stream the offsets, the last round's statistics and the running state; the update is queued behind every round
+    int nr = 0; x264gpu_nr_offsets *d_nr_off = nullptr; x264gpu_nr_sums *d_nr_pic = nullptr, *d_nr_state = nullptr;
     std::vector<void *> up_streams;          // the members' uploads: a handful of streams dealt round-robin (a stream per member was 0.7 ms to create and 0.6 ms to destroy, x 2048, serialised in the runtime)
     long ev_round[2] = { 0, 0 }, ev_done[2] = { 0, 0 }; bool ev_waiting[2] = { false, false }; std::string ev_err;      // per buffer pair: the round recorded behind it (1-based), the last one known complete, a member is waiting for the event
     long launched = 0;            // rounds whose kernels have been issued: the helper threads start entropy coding round k once round k + 1 is on the device (or when asked to hurry),
@@ -84,6 +88,9 @@ void batch_destroy(BatchGroup *g)
     if (g->d_ix2) x264gpu_free(g->d_ix2);
     if (g->d_q) x264gpu_free(g->d_q);
     if (g->d_q2) x264gpu_free(g->d_q2);
+    if (g->d_nr_off) x264gpu_free(g->d_nr_off);
+    if (g->d_nr_pic) x264gpu_free(g->d_nr_pic);
+    if (g->d_nr_state) x264gpu_free(g->d_nr_state);
     for (int i = 0; i < 2; i++) if (g->ev[i]) x264gpu_event_destroy(g->ev[i]);
     if (g->dl_stream) x264gpu_stream_destroy(g->dl_stream);
     for (void *st : g->up_streams) x264gpu_stream_destroy(st);
@@ -106,6 +113,8 @@ void batch_run_round(BatchGroup *g, std::unique_lock<std::mutex> &lk)
         }
         const bool second = g->overlap && (g->round & 1);          // the output buffers of this round (the other pair may still be downloading)
         if (!g->round_rc && x264gpu_encode_pictures(g->gpu, g->d_in, g->pics.data(), second ? g->d_mb2 : g->d_mb, second ? g->d_lv2 : g->d_lv, g->async ? g->cs : nullptr) != X264GPU_OK) { g->round_rc = -1; g->err = x264gpu_last_error(); }
+        // --nr: a batch session's picture is accepted as it is coded (no VBV in a group): every stream's statistics join its state, its next offsets follow, in front of the next round
+        if (!g->round_rc && g->nr && nr_update_queue(g->d_nr_off, g->d_nr_state, g->d_nr_pic, g->N, g->nr, g->async ? g->cs : nullptr) != X264GPU_OK) { g->round_rc = -1; g->err = x264gpu_last_error(); }
         if (!g->round_rc && g->qflags && quality_queue(g->gpu, g->qflags, second ? g->d_q2 : g->d_q, g->async ? g->cs : nullptr) != X264GPU_OK) { g->round_rc = -1; g->err = x264gpu_last_error(); }
         if (!g->round_rc && g->pack && x264gpu_pack_levels(second ? g->d_lv2 : g->d_lv, g->N, (int)g->nmb, second ? g->d_ix2 : g->d_ix, nullptr, g->cs) != X264GPU_OK) { g->round_rc = -1; g->err = x264gpu_last_error(); }
         if (!g->round_rc && g->async) {
@@ -134,7 +143,7 @@ void batch_run_round(BatchGroup *g, std::unique_lock<std::mutex> &lk)
 
 }  // namespace
 
-bool Batch::join(const x264gpu_config &cfg1, int N, size_t insz, size_t nmb, int qflags)
+bool Batch::join(const x264gpu_config &cfg1, int N, size_t insz, size_t nmb, int qflags, int nr)
 {
     std::lock_guard<std::mutex> lk(g_batch_mu);
     int dev = 0;
@@ -142,7 +151,7 @@ bool Batch::join(const x264gpu_config &cfg1, int N, size_t insz, size_t nmb, int
     for (BatchGroup *og : g_batch_groups) {
         x264gpu_config a = og->cfg, b = cfg1;
         a.streams = b.streams = 0;
-        if (og->N == N && og->device == dev && og->joined < N && !og->closed && og->qflags == qflags && !memcmp(&a, &b, sizeof(a))) {
+        if (og->N == N && og->device == dev && og->joined < N && !og->closed && og->qflags == qflags && og->nr == nr && !memcmp(&a, &b, sizeof(a))) {
             std::lock_guard<std::mutex> lg(og->m);
             g = og; s = og->joined++; og->active++; og->member[(size_t)s] = 1;
             og->cv.notify_all();
@@ -151,13 +160,18 @@ bool Batch::join(const x264gpu_config &cfg1, int N, size_t insz, size_t nmb, int
     }
     if (!g) {
         BatchGroup *ng = new BatchGroup();
-        ng->cfg = cfg1; ng->cfg.streams = N; ng->N = N; ng->device = dev; ng->insz = insz; ng->nmb = nmb; ng->qflags = qflags;
+        ng->cfg = cfg1; ng->cfg.streams = N; ng->N = N; ng->device = dev; ng->insz = insz; ng->nmb = nmb; ng->qflags = qflags; ng->nr = nr;
         ng->member.assign((size_t)N, 0); ng->arrived.assign((size_t)N, 0); ng->pics.resize((size_t)N);
         if (x264gpu_encoder_create(&ng->gpu, &ng->cfg) != X264GPU_OK ||
             x264gpu_malloc((void **)&ng->d_in, (size_t)N * insz) != X264GPU_OK ||
             x264gpu_malloc((void **)&ng->d_mb, (size_t)N * nmb * sizeof(x264gpu_mb)) != X264GPU_OK ||
             x264gpu_malloc((void **)&ng->d_lv, (size_t)N * nmb * X264GPU_MB_LEVELS * sizeof(int16_t)) != X264GPU_OK ||
             (qflags && (x264gpu_malloc((void **)&ng->d_q, (size_t)N * sizeof(x264gpu_quality)) != X264GPU_OK || x264gpu_malloc((void **)&ng->d_q2, (size_t)N * sizeof(x264gpu_quality)) != X264GPU_OK))) { batch_destroy(ng); return false; }
+        if (nr && (x264gpu_malloc((void **)&ng->d_nr_off, (size_t)N * sizeof(x264gpu_nr_offsets)) != X264GPU_OK || x264gpu_malloc((void **)&ng->d_nr_pic, (size_t)N * sizeof(x264gpu_nr_sums)) != X264GPU_OK ||
+                   x264gpu_malloc((void **)&ng->d_nr_state, (size_t)N * sizeof(x264gpu_nr_sums)) != X264GPU_OK ||
+                   x264gpu_memset(ng->d_nr_off, 0, (size_t)N * sizeof(x264gpu_nr_offsets), nullptr) != X264GPU_OK || x264gpu_memset(ng->d_nr_pic, 0, (size_t)N * sizeof(x264gpu_nr_sums), nullptr) != X264GPU_OK ||
+                   x264gpu_memset(ng->d_nr_state, 0, (size_t)N * sizeof(x264gpu_nr_sums), nullptr) != X264GPU_OK || x264gpu_stream_sync(nullptr) != X264GPU_OK ||
+                   nr_set(ng->gpu, ng->d_nr_off, ng->d_nr_pic) != X264GPU_OK)) { batch_destroy(ng); return false; }
         const char *oe = getenv("X264GPU_BATCH_OVERLAP");
         if (!(oe && oe[0] == '0') && !getenv("X264GPU_DUMP_RECORDS") &&
             x264gpu_malloc((void **)&ng->d_mb2, (size_t)N * nmb * sizeof(x264gpu_mb)) == X264GPU_OK &&
@@ -248,6 +262,16 @@ int Batch::download(int buf, x264gpu_mb *h_mb, int16_t *h_lv, std::string &err, 
     }
     if (x264gpu_memcpy_d2h(h_mb, dm + (size_t)s * g->nmb, g->nmb * sizeof(x264gpu_mb), st) != X264GPU_OK ||
         x264gpu_memcpy_d2h(h_lv, dl + (size_t)s * g->nmb * X264GPU_MB_LEVELS, g->nmb * X264GPU_MB_LEVELS * sizeof(int16_t), st) != X264GPU_OK) { err = x264gpu_last_error(); return -1; }
+    return 0;
+}
+
+int Batch::nr_offsets(uint16_t out[3][64])
+{
+    memset(out, 0, 3 * 64 * sizeof(uint16_t));
+    if (!g || !g->nr) return -1;
+    // (the update is queued on the stream the rounds run on: wait for it, then for the copy)
+    void *st = g->async ? g->cs : nullptr;
+    if (x264gpu_stream_sync(st) != X264GPU_OK || x264gpu_memcpy_d2h(out, g->d_nr_off + s, sizeof(x264gpu_nr_offsets), st) != X264GPU_OK || x264gpu_stream_sync(st) != X264GPU_OK) return -1;
     return 0;
 }
 

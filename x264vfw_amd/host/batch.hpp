@@ -21,7 +21,9 @@ struct Batch {
     int want = 0;                        // the group size the session asks for (X264GPU_BATCH=N of a session whose picture structure is fixed; 0: it runs on its own)
 
     // joins (or starts) the group of N sessions with this device configuration; false: setup failed (the device's last error set)
-    bool join(const x264gpu_config &cfg, int N, size_t insz, size_t nmb, int qflags);
+    // nr: the session's noise-reduction strength (0: none) — part of what a group's members have in common: every stream of the group's encoder then has its own
+    // offsets, statistics and state, moved on behind every round
+    bool join(const x264gpu_config &cfg, int N, size_t insz, size_t nmb, int qflags, int nr = 0);
     // the registry lock, then the group's: the last member to go takes the group with it; a round the others were only waiting for this session to join is run first
     void leave();
     bool joined() const { return g != nullptr; }
@@ -40,6 +42,9 @@ struct Batch {
     // the session's records and levels of the round whose results lie in buffer pair `buf`
     // (h_ix: the group packs its levels — the member's index; h_lv then receives only the kept groups)
     int download(int buf, x264gpu_mb *h_mb, int16_t *h_lv, std::string &err, x264gpu_level_index *h_ix = nullptr, x264gpu_quality *h_q = nullptr);
+
+    // --nr: the offsets the session's next picture will be denoised with (waits for the group's rounds on the device); -1 and zeros in a group without nr
+    int nr_offsets(uint16_t out[3][64]);
 
     // ---- the helper thread of a session in an overlapping group: it downloads round k and writes its slices once round k + 1 is on the device, so that the host
     //      cores are the callers' while the next pictures are uploaded and submitted ----

@@ -10,6 +10,7 @@
 #include "batch.hpp"
 #include "gopslots.hpp"
 #include "quality.hpp"
+#include "noisereduction.hpp"
 #include "ratecontrol.hpp"
 #include "slicetype.hpp"
 #include <limits.h>
@@ -57,6 +58,8 @@ struct x264_t {
     //      its host copies (two: the pipelined I / P session downloads one picture's while the one before is coded) ----
     Quality ql;
     x264gpu_quality *d_q = nullptr, hq[2] = {};
+    int cqo_without_psy_trellis = 0;     // the chroma quantiser offset as it is without psy-trellis' share (what remains when psy-trellis gives way to nr, open_quantisers)
+    NoiseReduction nr;                   // host/noisereduction.hpp: --nr — the session's state on the device, moved on behind every accepted picture
     // ---- lookahead-driven decisions (threads 1 only): scenecut and CRF, both fed by x264gpu_lookahead_frame_cost ----
     x264gpu_lookahead *la = nullptr;
     int32_t *d_la = nullptr;             // device: the four sums of the last picture
@@ -332,6 +335,7 @@ static void open_toolset(x264_t *h)
         xlog(&p, X264_LOG_WARNING, "trellis %d needs CABAC and subme >= 6 in the MI355X path (the search reads the CABAC state the device carries for RD): trellis 0\n", p.analyse.i_trellis);
         p.analyse.i_trellis = 0;
     }
+    NoiseReduction::check_toolset(p);          // --nr: inter residuals denoised in the macroblock loop (host/noisereduction.hpp); the toolset's share of its rules; psy-trellis gives way to it once the session's mode has passed too (open_quantisers)
     p.analyse.b_psy = p.analyse.b_psy != 0;
     if (!p.analyse.b_psy) { p.analyse.f_psy_rd = 0; p.analyse.f_psy_trellis = 0; }       // x264 validate_parameters
     p.analyse.f_psy_rd = p.analyse.f_psy_rd < 0 ? 0 : p.analyse.f_psy_rd > 10 ? 10 : p.analyse.f_psy_rd;
@@ -347,6 +351,7 @@ static void open_toolset(x264_t *h)
     // psy RD raises luma quality at chroma's cost, so x264 lowers the chroma quantiser offset to compensate (encoder.c, validate / mb init)
     int eff_chroma_qp_offset = p.analyse.i_chroma_qp_offset;
     if (psy_rd_q8(p)) eff_chroma_qp_offset -= p.analyse.f_psy_rd < 0.25f ? 1 : 2;
+    h->cqo_without_psy_trellis = clampi(eff_chroma_qp_offset, -12, 12);
     if (psy_trellis_q8(p)) eff_chroma_qp_offset -= p.analyse.f_psy_trellis < 0.25f ? 1 : 2;
     eff_chroma_qp_offset = clampi(eff_chroma_qp_offset, -12, 12);
     p.analyse.i_chroma_qp_offset = eff_chroma_qp_offset;          // x264 changes the parameter in place too: the PPS carries it
@@ -512,7 +517,13 @@ static void open_quantisers(x264_t *h)
         h->vbv = false; p.rc.i_vbv_max_bitrate = 0; p.rc.i_vbv_buffer_size = 0; p.i_nal_hrd = X264_NAL_HRD_NONE;
     }
     rc.vbv = h->vbv; rc.filler = h->vbv && p.i_nal_hrd == X264_NAL_HRD_CBR;
-    if (p.analyse.i_noise_reduction) { xlog(&p, X264_LOG_WARNING, "nr (noise reduction) is not implemented in the MI355X path: nr 0\n"); p.analyse.i_noise_reduction = 0; }
+    NoiseReduction::check_modes(p, h->dpbmode);
+    if (p.analyse.i_noise_reduction && p.analyse.f_psy_trellis > 0) {
+        // nr runs (toolset and mode have passed; from here on only a device failure stops it, and that fails the open): psy-trellis gives way, with its share of the
+        // chroma quantiser offset (the macroblock loop has psy instantiations and denoising instantiations, none with both: the build would double again)
+        xlog(&p, X264_LOG_WARNING, "psy-trellis is not run beside noise reduction in the MI355X path (nr %d wins): psy-trellis 0\n", p.analyse.i_noise_reduction);
+        p.analyse.f_psy_trellis = 0; p.analyse.i_chroma_qp_offset = h->cqo_without_psy_trellis;
+    }
     if (p.i_slice_max_size > 0 || p.i_slice_max_mbs > 0) { xlog(&p, X264_LOG_WARNING, "slice-max-size / slice-max-mbs are not implemented in the MI355X path (slices are cut by --slices N or slice threads only)\n"); p.i_slice_max_size = p.i_slice_max_mbs = 0; }
     if (p.b_fake_interlaced || p.b_pic_struct) { xlog(&p, X264_LOG_WARNING, "fake-interlaced / pic-struct are not implemented in the MI355X path: off\n"); p.b_fake_interlaced = p.b_pic_struct = 0; }
     if (p.b_bluray_compat) { xlog(&p, X264_LOG_WARNING, "bluray-compat is not implemented in the MI355X path: off\n"); p.b_bluray_compat = 0; }
@@ -617,7 +628,9 @@ static x264gpu_config open_device_config(x264_t *h)
     p.analyse.i_mv_range = clampi(p.analyse.i_mv_range, 32, 512);
     cfg.mv_range = p.analyse.i_mv_range;
     h->inflight = 1;
-    if (h->dpbmode && p.i_bframe > 0 && h->G == 1 && !h->batch.want && !h->rc.reads_sizes() && h->direct_mode != 3) {
+    if (p.analyse.i_noise_reduction && h->dpbmode && p.i_bframe > 0 && getenv("X264GPU_INFLIGHT"))
+        xlog(&p, X264_LOG_INFO, "nr: one picture in flight (X264GPU_INFLIGHT is not used: the session has one noise-reduction state, moved on in coding order)\n");
+    if (h->dpbmode && p.i_bframe > 0 && h->G == 1 && !h->batch.want && !h->rc.reads_sizes() && h->direct_mode != 3 && !p.analyse.i_noise_reduction) {
         // (--direct auto chooses a B picture's mode from the skip counts of the one before, ABR and 2-pass a picture's quantiser from the sizes of the ones before:
         //  those sessions code one picture at a time)
         const char *ie = getenv("X264GPU_INFLIGHT");
@@ -651,13 +664,14 @@ static bool open_device(x264_t *h)
         return h->gops.open(p, cfg, h->rc, { h->G, h->keyint, h->nmb, h->qp_i, h->qp_p, h->bframes, h->bpyramid, h->weightp, h->log2_max_frame_num, h->direct_mode, h->dpbmode,
                                              h->device, slice_params_base(h), write_coded });
     } else if (ok_setup && h->batch.want) {
-        ok_setup = h->batch.join(cfg, h->batch.want, insz, (size_t)h->nmb, h->ql.flags);
+        ok_setup = h->batch.join(cfg, h->batch.want, insz, (size_t)h->nmb, h->ql.flags, p.analyse.i_noise_reduction);
         if (ok_setup) xlog(&p, X264_LOG_INFO, "X264GPU_BATCH: stream %d of a batch of %d sessions%s\n", h->batch.index(), h->batch.size(), h->batch.queued() ? " (rounds queued: uploads overlap the device)" : "");
     } else if (ok_setup) {
         ok_setup = x264gpu_encoder_create(&h->gpu, &cfg) == X264GPU_OK &&
                    x264gpu_malloc((void **)&h->d_mb, (size_t)h->nmb * sizeof(x264gpu_mb)) == X264GPU_OK &&
                    x264gpu_malloc((void **)&h->d_lv, (size_t)h->nmb * X264GPU_MB_LEVELS * sizeof(int16_t)) == X264GPU_OK &&
                    (!h->ql.flags || x264gpu_malloc((void **)&h->d_q, sizeof(x264gpu_quality)) == X264GPU_OK);
+        ok_setup = ok_setup && h->nr.open(p, h->gpu);
         if (ok_setup && h->inflight > 1) {
             h->lctx.resize((size_t)h->inflight);
             ok_setup = x264gpu_event_create(&h->ev_la) == X264GPU_OK;
@@ -1241,6 +1255,8 @@ static int encode_bmode(x264_t *h, x264_nal_t **pp_nal, int *pi_nal, x264_pictur
         if (f.nal_ref_idc) h->rc.kept(f.pic.dst, f.qpf, f.pl.type);
         h->last_vbv.attempts++;
     }
+    // --nr: the picture is accepted (the VBV guard is through with it) — its statistics join the session's state, the next picture's offsets follow
+    if (h->nr.accepted(nullptr) != X264GPU_OK) { xlog(&p, X264_LOG_ERROR, "x264_encoder_encode: nr update failed: %s\n", x264gpu_last_error()); h->failed = true; return -1; }
     BPHASE(2);
     if (const char *dd = getenv("X264GPU_DUMP_RECORDS")) {          // debugging aid: the records and levels of every coded picture, and what was asked of the device
         char fn[512];
@@ -1463,6 +1479,7 @@ void x264_encoder_close(x264_t *h)
     h->lctx.clear();
     if (h->ev_la) x264gpu_event_destroy(h->ev_la);
     h->batch.leave();
+    h->nr.close();
     if (h->gpu) x264gpu_encoder_destroy(h->gpu);
     if (h->d_in) x264gpu_free(h->d_in);
     if (h->d_mb) x264gpu_free(h->d_mb);
@@ -1700,6 +1717,13 @@ int x264host_last_quality(x264_t *h, double psnr[4], double *ssim, uint64_t ssd[
     if (ssim) *ssim = h->ql.last_ssim;
     if (ssd) memcpy(ssd, h->ql.last_ssd, sizeof(h->ql.last_ssd));
     return 0;
+}
+
+int x264host_nr_offsets(x264_t *h, uint16_t out[3][64])
+{
+    if (!h || !out) return -1;
+    if (h->batch.joined()) return h->batch.nr_offsets(out);
+    return h->nr.offsets(out);
 }
 
 int x264host_quality_summary(x264_t *h, char *buf, int cap)

@@ -61,6 +61,16 @@ class Quality(C.Structure):
     _fields_ = [("ssd", C.c_uint64 * 3), ("ssim_sum", C.c_double), ("ssim_cnt", C.c_uint32), ("pad", C.c_uint32)]
 
 
+class NrOffsets(C.Structure):
+    """Mirror of struct x264gpu_nr_offsets (384 bytes)."""
+    _fields_ = [("off", (C.c_uint16 * 64) * 3)]
+
+
+class NrSums(C.Structure):
+    """Mirror of struct x264gpu_nr_sums (1552 bytes)."""
+    _fields_ = [("sum", (C.c_uint64 * 64) * 3), ("count", C.c_uint32 * 3), ("pad", C.c_uint32)]
+
+
 def make_pic(slice_type, qp, poc, dst, keep, l0=(), l1=()):
     p = Pic(slice_type=slice_type, qp=qp, poc=poc, dst=dst, keep=keep, blind_dupe=-1)
     p.nref[0], p.nref[1] = len(l0), len(l1)
@@ -135,6 +145,9 @@ _SIGS = {
     "x264gpu_trellis_blocks": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "x264gpu_trellis_blocks_ex": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp]),
     "x264gpu_trellis_blocks_psy": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp]),
+    "x264gpu_encoder_set_nr": (_i, [_vp, _vp, _vp]),
+    "x264gpu_nr_update": (_i, [_vp, _vp, _vp, _i, _i, _vp]),
+    "x264gpu_denoise_blocks": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
     "x264gpu_cabac_level_walk": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "x264gpu_encoder_deblock_pictures": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "x264gpu_get_device": (_i, [_vp]),
