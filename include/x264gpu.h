@@ -514,6 +514,12 @@ int  x264gpu_lookahead_aq_offsets_mode(x264gpu_lookahead *la, const uint8_t *d_i
  * strength = 5.0f * (1.0f - qcomp).  Feed it to x264gpu_encoder_set_mb_qp_offsets.  x264's C expressions in single floats throughout. */
 int  x264gpu_lookahead_mbtree(x264gpu_lookahead *la, const int32_t *const *d_info, const float *const *d_aq, int n, float strength,
                               float *d_out, void *stream);
+/* The macroblock-tree statistics file's number format ([x264-upstream] common/mc.c mbtree_fix8_pack / _unpack): a picture's quantiser offsets to and from the
+ * file's big-endian 8.8 fixed-point words, where the offsets live.  One launch on `stream`, no synchronisation; EINVAL for null pointers or n <= 0.
+ * x264 mbtree_fix8_pack: d_out[i] = big-endian int16( trunc-toward-zero( d_offsets[i] * 256.0f ) ), saturated to [-32768, 32767], NaN -> 0 */
+int  x264gpu_mbtree_pack  (const float *d_offsets, int n, uint16_t *d_out, void *stream);
+/* x264 mbtree_fix8_unpack: d_offsets[i] = (float)(int16 of the big-endian word d_in[i]) * (1.0f / 256.0f) */
+int  x264gpu_mbtree_unpack(const uint16_t *d_in, int n, float *d_offsets, void *stream);
 
 #ifdef __cplusplus
 }

@@ -72,6 +72,11 @@ int x264host_quality_summary(x264_t *h, char *buf, int cap);
 /* --nr (analyse.i_noise_reduction): the offsets the NEXT picture of the session will be denoised with, [category 0 luma 4x4, 1 luma 8x8, 2 chroma 4x4][raster index]
  * (x264gpu_nr_update's, behind every accepted picture; waits for the device).  -1 (and zeros): the session runs nr 0 */
 int x264host_nr_offsets(x264_t *h, uint16_t out[3][64]);
+/* the per-macroblock quantiser offsets (x264gpu_encoder_set_mb_qp_offsets: AQ - macroblock-tree, the AQ offsets alone, or what the second pass read from the
+ * macroblock-tree statistics file) the picture whose NAL units the last call returned was coded with, downloaded on request (waits for the device): n = the
+ * picture's macroblock count.  Returns n; 0 when the picture had none (dst untouched), -1 on a wrong n or a device failure.  Sessions on the DPB model, one
+ * picture in flight or several */
+int x264host_last_mb_qp_offsets(x264_t *h, float *dst, int n);
 double x264host_psnr(double ssd, double n);
 double x264host_ssim_db(double ssim);
 

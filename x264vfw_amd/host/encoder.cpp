@@ -11,6 +11,7 @@
 #include "gopslots.hpp"
 #include "quality.hpp"
 #include "noisereduction.hpp"
+#include "mbtreestats.hpp"
 #include "ratecontrol.hpp"
 #include "slicetype.hpp"
 #include <limits.h>
@@ -60,6 +61,8 @@ struct x264_t {
     x264gpu_quality *d_q = nullptr, hq[2] = {};
     int cqo_without_psy_trellis = 0;     // the chroma quantiser offset as it is without psy-trellis' share (what remains when psy-trellis gives way to nr, open_quantisers)
     NoiseReduction nr;                   // host/noisereduction.hpp: --nr — the session's state on the device, moved on behind every accepted picture
+    MbTreeStats tstats;                  // host/mbtreestats.hpp: the macroblock-tree statistics file of a 2-pass encode (X264GPU_MBTREE_STATS=1), written or read
+    const float *last_offsets = nullptr; // device: the per-macroblock quantiser offsets of the picture handed back last (x264host_last_mb_qp_offsets; nullptr: none)
     // ---- lookahead-driven decisions (threads 1 only): scenecut and CRF, both fed by x264gpu_lookahead_frame_cost ----
     x264gpu_lookahead *la = nullptr;
     int32_t *d_la = nullptr;             // device: the four sums of the last picture
@@ -508,7 +511,17 @@ static void open_quantisers(x264_t *h)
     if (p.rc.i_rc_method != X264_RC_CQP && !rc.by_cost() && !rc.pass2) xlog(&p, X264_LOG_WARNING, "this rate control mode is not implemented yet (ABR with --threads > 1): constant qp %d\n", qp);
     if (qp < 1) { xlog(&p, X264_LOG_WARNING, "lossless is not supported: qp 1\n"); qp = 1; }
     if (!rc.by_cost() && !rc.pass2) p.rc.i_rc_method = X264_RC_CQP;
-    if ((rc.pass1 || rc.pass2) && p.rc.b_mb_tree) { xlog(&p, X264_LOG_INFO, "2-pass: the macroblock-tree statistics file is not implemented in the MI355X path: mbtree 0 in both passes\n"); p.rc.b_mb_tree = 0; }
+    if ((rc.pass1 || rc.pass2) && p.rc.b_mb_tree) {
+        if (!MbTreeStats::opted_in()) { xlog(&p, X264_LOG_INFO, "2-pass: the macroblock-tree statistics file is not implemented in the MI355X path: mbtree 0 in both passes\n"); p.rc.b_mb_tree = 0; }
+        else if (rc.pass2) {
+            // the second pass has no future pictures: no lookahead, no tree of its own — kept pictures take the offsets the first pass' tree left in <stats>.mbtree,
+            // the plan takes the tree's RCEQ.  The session is set up as the tree-less one (rc-lookahead 0) and reports mbtree 1 (x264_encoder_open, once every part is open).
+            // Needs what 2-pass needs (threads 1, the DPB-model path, no X264GPU_BATCH: rc.pass2 says so); VBV and zones in a second pass stay as they are
+            h->tstats.reading = rc.tree_read = h->tstats.check_read(p, p.rc.psz_stat_in, h->nmb);
+            p.rc.b_mb_tree = 0;
+        }
+        // (a first pass keeps its tree: the single-pass CRF / ABR + tree session plus the statistics; whether the tree really runs is settled below)
+    }
     rc.parse_zones(p);
     if (!rc.zones.empty()) xlog(&p, X264_LOG_INFO, "%d zone%s (quantiser / bitrate factor per range of pictures)\n", (int)rc.zones.size(), rc.zones.size() > 1 ? "s" : "");
     if (!rc.zones.empty() && rc.pass2) xlog(&p, X264_LOG_WARNING, "zones are not applied to the second pass' plan in the MI355X path (the first pass and single-pass sessions honour them)\n");
@@ -533,6 +546,7 @@ static void open_quantisers(x264_t *h)
     if (p.rc.i_rc_method == X264_RC_CQP || p.rc.i_lookahead <= 0) p.rc.b_mb_tree = 0;
     if (p.rc.b_mb_tree && p.i_threads > 1) { xlog(&p, X264_LOG_INFO, "mbtree needs threads 1 (GOPs in lock-step are coded before what follows them is seen): mbtree 0\n"); p.rc.b_mb_tree = 0; }
     p.rc.b_mb_tree = p.rc.b_mb_tree != 0;
+    h->tstats.writing = rc.tree_write = rc.pass1 && p.rc.b_mb_tree && MbTreeStats::opted_in();
     // (VBV plans over the lookahead too, with or without the tree: x264's vbv_lookahead; rc-lookahead 0 leaves it the reactive algorithm)
     { const int cap = p.i_keyint_max < 250 ? (p.i_keyint_max > 1 ? p.i_keyint_max : 1) : 250;
       p.rc.i_lookahead = p.rc.b_mb_tree ? clampi(p.rc.i_lookahead, 1, cap) : h->vbv ? clampi(p.rc.i_lookahead, 0, cap) : 0; }
@@ -699,7 +713,7 @@ static bool open_lookahead(x264_t *h)
 {
     x264_param_t &p = h->param;
     const size_t insz = (size_t)p.i_width * p.i_height * 3 / 2;
-    if ((p.i_scenecut_threshold > 0 && !h->dpbmode) || h->rc.by_cost() || h->aq_mode >= 2) {       // (sessions on the DPB model take scene cuts from x264's own analysis below)
+    if ((p.i_scenecut_threshold > 0 && !h->dpbmode) || h->rc.by_cost() || h->aq_mode >= 2 || h->tstats.reading) {       // (sessions on the DPB model take scene cuts from x264's own analysis below; a second pass over the tree file: the AQ kernel only)
         if (x264gpu_lookahead_create(&h->la, p.i_width, p.i_height, 1, p.analyse.i_me_range, p.analyse.i_subpel_refine) != X264GPU_OK ||
             x264gpu_malloc((void **)&h->d_la, 4 * sizeof(int32_t)) != X264GPU_OK) {
             xlog(&p, X264_LOG_ERROR, "GPU lookahead setup failed: %s\n", x264gpu_last_error());
@@ -748,7 +762,7 @@ static bool open_lookahead(x264_t *h)
         // one device block per array, cut into the queue's slots (an allocation and a release each cost a fraction of a millisecond: thousands of sessions open and close)
         bool ok = true;
         const size_t Q = (size_t)h->Q, insz_al = (insz + 255) & ~(size_t)255, nmbf = ((size_t)h->nmb * sizeof(float) + 255) & ~(size_t)255, ninfo = ((size_t)h->nmb * 4 * sizeof(int32_t) + 255) & ~(size_t)255;
-        const bool want_aq = h->mbtree || h->slicetype.aq_costs || h->aq_mode >= 2, want_tree = h->mbtree && h->dpbmode;
+        const bool want_aq = h->mbtree || h->slicetype.aq_costs || h->aq_mode >= 2 || h->tstats.reading, want_tree = (h->mbtree && h->dpbmode) || h->tstats.reading;
         if (!h->q_raw[0]) ok = x264gpu_malloc((void **)&h->q_block[0], Q * insz_al) == X264GPU_OK;
         if (ok && h->mbtree) ok = x264gpu_malloc((void **)&h->q_block[1], Q * ninfo) == X264GPU_OK;
         if (ok && want_aq) ok = x264gpu_malloc((void **)&h->q_block[2], Q * nmbf) == X264GPU_OK;
@@ -802,7 +816,9 @@ x264_t *x264_encoder_open(x264_param_t *param)
     open_vbv(h);
     open_modes(h);
     open_quantisers(h);
-    if (!open_device(h) || !open_lookahead(h) || !h->rc.open(p, h->mbw, h->mbh, h->bframes, h->qp_i, h->qp_p)) { x264_encoder_close(h); return nullptr; }
+    if (!open_device(h) || !open_lookahead(h) || !h->rc.open(p, h->mbw, h->mbh, h->bframes, h->qp_i, h->qp_p) ||
+        !h->tstats.open(p, p.rc.psz_stat_in, p.rc.psz_stat_out, h->nmb)) { x264_encoder_close(h); return nullptr; }
+    if (h->tstats.reading) p.rc.b_mb_tree = 1;          // reported back: the second pass codes with the first pass' tree (every reader of the flag has run)
     open_host_buffers(h);
     xlog(&p, X264_LOG_INFO, "MI355X hot path: %dx%d, %d MBs, CQP I:%d P:%d, keyint %d, level %d\n", p.i_width, p.i_height, h->nmb,
          h->qp_i, h->qp_p, h->keyint, h->level_idc);
@@ -1049,9 +1065,16 @@ static void bmode_plan(x264_t *h, x264_t::PicPlan &f, x264gpu_encoder *gpu, long
     f.d_offsets = nullptr;
     if (h->slicetype.analyses() && h->mbtree)          // P / I / B-reference pictures: what the tree left (AQ - tree); other B pictures: the AQ offsets alone (x264 f_qp_offset_aq)
         f.d_offsets = pl.type == PIC_B ? h->q_aq[(size_t)pl.e.slot] : h->q_tree[(size_t)pl.e.slot];
+    else if (h->tstats.reading) {
+        // a second pass over the macroblock-tree statistics file: a kept picture's record, unpacked into its slot; every other picture the AQ offsets alone
+        const int got = h->tstats.read_record(h->param, coded_index, pl.type, h->q_tree[(size_t)pl.e.slot], nullptr);
+        if (got < 0) h->failed = true;
+        f.d_offsets = got > 0 ? h->q_tree[(size_t)pl.e.slot] : h->aq_strength != 0.f ? h->q_aq[(size_t)pl.e.slot] : nullptr;
+    }
     else if (h->aq_mode >= 2 && h->aq_strength != 0.f) f.d_offsets = h->q_aq[(size_t)pl.e.slot];      // --aq-mode 2 / 3: the offsets computed when the picture arrived
-    // (the serial path names a buffer only when there is one; a launch context is always told, "none" included)
-    if (f.d_offsets || !serial) x264gpu_encoder_set_mb_qp_offsets(gpu, f.d_offsets);
+    // (the serial path names a buffer only when there is one; a launch context is always told, "none" included — and so is a second pass over the tree file,
+    //  whose pictures take turns between two kinds of offsets or none)
+    if (f.d_offsets || !serial || h->tstats.reading) x264gpu_encoder_set_mb_qp_offsets(gpu, f.d_offsets);
     if (plan.nal_ref_idc) h->rc.kept(pic.dst, f.qpf, pl.type);
     if (plan.nal_ref_idc) h->slot_l0ref0poc[pic.dst] = pic.nref[0] ? plan.list_poc[0][0] : INT_MIN;
     f.direct_char = is_b ? (pic.direct_temporal ? 't' : 's') : '-';
@@ -1066,7 +1089,7 @@ static bool bmode_open_au(x264_t *h, x264_t::PicPlan &f, std::vector<int> &types
 {
     const SliceType::Pic &pl = f.pl;
     h->last_direct_char = f.direct_char;
-    h->last_scenecut = pl.e.scenecut; h->last_qp = f.pic.qp; h->last_qpm = f.pic.qpm;
+    h->last_scenecut = pl.e.scenecut; h->last_qp = f.pic.qp; h->last_qpm = f.pic.qpm; h->last_offsets = f.d_offsets;
     memcpy(h->last_costs, pl.e.costs, sizeof(pl.e.costs));
     h->out.clear(); h->nal_off.clear();
     AuTiming tm;
@@ -1213,6 +1236,7 @@ static int encode_bmode(x264_t *h, x264_nal_t **pp_nal, int *pi_nal, x264_pictur
     if (!decided) return flushing ? publish_deferred(h, h->defer[h->defer_cur ^ 1].valid ? h->defer[h->defer_cur ^ 1] : h->defer[h->defer_cur], pp_nal, pi_nal, pic_out) : 0;
     x264_t::PicPlan f;
     bmode_plan(h, f, h->gpu, h->coded_count, true);
+    if (h->failed) return -1;          // (the macroblock-tree statistics file: a record of another picture type, said in the log)
     std::vector<int> vbv_types; bool vbv_sets = false, vbv_written = false;          // VBV: the access unit is written (and the picture coded again) before it is finished
     // launch: the group's round (its results downloaded here unless a helper thread does it: deferred), or this session's encoder and two downloads on the default stream
     const uint8_t *d_src = h->q_raw[(size_t)f.pl.e.slot];
@@ -1255,6 +1279,9 @@ static int encode_bmode(x264_t *h, x264_nal_t **pp_nal, int *pi_nal, x264_pictur
         if (f.nal_ref_idc) h->rc.kept(f.pic.dst, f.qpf, f.pl.type);
         h->last_vbv.attempts++;
     }
+    // a first pass that writes the macroblock-tree statistics file: the record of a kept picture, packed behind the picture on its stream (tree sessions name
+    // q_tree for every kept picture; 2 bytes a macroblock come down)
+    if (h->tstats.writing && f.nal_ref_idc && f.pl.type != PIC_B && !h->tstats.write_record(p, f.pl.type, f.d_offsets, nullptr)) { h->failed = true; return -1; }
     // --nr: the picture is accepted (the VBV guard is through with it) — its statistics join the session's state, the next picture's offsets follow
     if (h->nr.accepted(nullptr) != X264GPU_OK) { xlog(&p, X264_LOG_ERROR, "x264_encoder_encode: nr update failed: %s\n", x264gpu_last_error()); h->failed = true; return -1; }
     BPHASE(2);
@@ -1406,13 +1433,19 @@ int x264_encoder_encode(x264_t *h, x264_nal_t **pp_nal, int *pi_nal, x264_pictur
     e.pts = pic_in->i_pts; e.slot = slot; e.img = pic_in->img;
     bool idr = h->la_count == 0 || h->la_gop >= h->keyint || pic_in->i_type == X264_TYPE_IDR || pic_in->i_type == X264_TYPE_KEYFRAME, intra_pic = false;
     if (h->la) {
+        if (h->tstats.reading) {          // (no frame costs: this session's lookahead object runs the AQ kernel alone)
+            if (h->aq_strength != 0.f && x264gpu_lookahead_aq_offsets_mode(h->la, d_raw, h->aq_mode >= 2 ? h->aq_mode : 1, h->aq_strength, h->q_aq[(size_t)slot], nullptr) != X264GPU_OK) {
+                xlog(&p, X264_LOG_ERROR, "x264_encoder_encode: lookahead failed: %s\n", x264gpu_last_error());
+                return -1;
+            }
+        } else
         if (x264gpu_lookahead_frame_cost(h->la, d_raw, h->la_count == 0, h->d_la, h->mbtree ? h->q_info[(size_t)slot] : nullptr, nullptr) != X264GPU_OK ||
             ((h->mbtree || h->slicetype.aq_costs || h->aq_mode >= 2) && h->aq_strength != 0.f && x264gpu_lookahead_aq_offsets_mode(h->la, d_raw, h->aq_mode >= 2 ? h->aq_mode : 1, h->aq_strength, h->q_aq[(size_t)slot], nullptr) != X264GPU_OK) ||
             x264gpu_memcpy_d2h(e.costs, h->d_la, sizeof(e.costs), nullptr) != X264GPU_OK) {
             xlog(&p, X264_LOG_ERROR, "x264_encoder_encode: lookahead failed: %s\n", x264gpu_last_error());
             return -1;
         }
-        if (!idr && p.i_scenecut_threshold > 0 && h->la_count > 0) {
+        if (!idr && p.i_scenecut_threshold > 0 && h->la_count > 0 && !h->tstats.reading) {
             // scenecut_internal: the bias grows with the distance from the last keyframe.  A cut at or beyond min-keyint becomes
             // an IDR picture, one inside min-keyint an I picture that keeps the references (x264_slicetype_decide).
             const int gop = h->la_gop, kmin = h->keyint_min, kmax = h->keyint;
@@ -1470,6 +1503,7 @@ void x264_encoder_close(x264_t *h)
                 1e3 * h->t_b[0] / h->t_b[4], 1e3 * h->t_b[1] / h->t_b[4], 1e3 * h->t_b[2] / h->t_b[4], 1e3 * h->t_b[3] / h->t_b[4]);
     h->ql.log_summary(h->param);
     h->rc.close();
+    h->tstats.close(h->param);
     for (size_t i = 0; i < h->lctx.size(); i++) {
         x264_t::LaunchCtx &c = h->lctx[i];
         if (c.stream) { x264gpu_stream_sync(c.stream); x264gpu_stream_destroy(c.stream); }
@@ -1724,6 +1758,14 @@ int x264host_nr_offsets(x264_t *h, uint16_t out[3][64])
     if (!h || !out) return -1;
     if (h->batch.joined()) return h->batch.nr_offsets(out);
     return h->nr.offsets(out);
+}
+
+int x264host_last_mb_qp_offsets(x264_t *h, float *dst, int n)
+{
+    if (!h || !dst || n != h->nmb) return -1;
+    if (!h->last_offsets) return 0;
+    if (x264gpu_stream_sync(nullptr) != X264GPU_OK || x264gpu_memcpy_d2h(dst, h->last_offsets, (size_t)n * sizeof(float), nullptr) != X264GPU_OK) return -1;
+    return n;
 }
 
 int x264host_quality_summary(x264_t *h, char *buf, int cap)

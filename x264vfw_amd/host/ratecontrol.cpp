@@ -50,7 +50,7 @@ bool RateControl::open(const x264_param_t &param, int mbw_, int mbh_, int bframe
 {
     p = &param;
     mbw = mbw_; mbh = mbh_; nmb = mbw * mbh;
-    mbtree = p->rc.b_mb_tree != 0;
+    mbtree = p->rc.b_mb_tree != 0 || tree_read;
     // x264_ratecontrol_init_reconfigurable: ip_offset = 6.0 * log2f( f_ip_factor ), pb_offset = 6.0 * log2f( f_pb_factor )
     ip_factor = fabs(p->rc.f_ip_factor) > 0 ? fabs(p->rc.f_ip_factor) : 1.0; pb_factor = fabs(p->rc.f_pb_factor) > 0 ? fabs(p->rc.f_pb_factor) : 1.0;
     ip_offset = 6.0 * log2f((float)ip_factor); pb_offset = 6.0 * log2f((float)pb_factor);
@@ -94,6 +94,10 @@ bool RateControl::open(const x264_param_t &param, int mbw_, int mbh_, int bframe
         level_mbps = 0; level_mincr = 2;
         for (int i = 0; x264_levels[i].level_idc; i++) if (x264_levels[i].level_idc == p->i_level_idc) { level_mbps = x264_levels[i].mbps; level_mincr = x264_levels[i].mincr; }
     }
+    if (pass2 && mbtree) {          // as single-pass tree sessions have them (pb_factor stays the session's there, and here)
+        qcompress = 1.0;
+        dur_ratio = clampd(p->i_fps_num ? (double)p->i_fps_den / p->i_fps_num : 0.04, 0.01, 1.0) / 0.04;
+    }
     if (pass2) {
         if (!p2_load(p->rc.psz_stat_in) || !p2_init()) return false;
         xlog(p, X264_LOG_INFO, "2-pass: %d pictures planned from the first pass' statistics, %.1f kbit expected before the last one\n", (int)p2.size(), p2_final_bits / 1000.0);
@@ -104,9 +108,11 @@ bool RateControl::open(const x264_param_t &param, int mbw_, int mbh_, int bframe
         // x264 writes <stats>.temp and renames it when the encoder closes; the first line names the options the second pass must agree with
         stat_file = fopen((std::string(p->rc.psz_stat_out) + ".temp").c_str(), "wb");
         if (!stat_file) { xlog(p, X264_LOG_ERROR, "ratecontrol_init: can't open stats file\n"); return false; }
-        fprintf(stat_file, "#options: %dx%d fps=%u/%u timebase=%u/%u bitdepth=8 cabac=%d ref=%d bframes=%d b_pyramid=%d b_adapt=%d weightp=%d keyint=%d rc=%s\n", p->i_width, p->i_height,
+        fprintf(stat_file, "#options: %dx%d fps=%u/%u timebase=%u/%u bitdepth=8 cabac=%d ref=%d bframes=%d b_pyramid=%d b_adapt=%d weightp=%d keyint=%d rc=%s", p->i_width, p->i_height,
                 p->i_fps_num, p->i_fps_den, p->i_fps_den, p->i_fps_num, p->b_cabac, p->i_frame_reference, p->i_bframe, p->i_bframe_pyramid, p->i_bframe_adaptive,
                 p->analyse.i_weighted_pred, p->i_keyint_max, p->rc.i_rc_method == X264_RC_ABR ? "abr" : p->rc.i_rc_method == X264_RC_CRF ? "crf" : "cqp");
+        if (tree_write && pass1) fprintf(stat_file, " mbtree=1 rc_lookahead=%d", p->rc.i_lookahead);          // a first pass that writes <stats>.mbtree beside them
+        fprintf(stat_file, "\n");
     }
     return true;
 }
@@ -370,8 +376,8 @@ void RateControl::close()
     else if (!out.empty() && rename((out + ".temp").c_str(), out.c_str())) xlog(p, X264_LOG_ERROR, "failed to rename \"%s.temp\" to \"%s\"\n", out.c_str(), out.c_str());
 }
 
-// ---- 2-pass (x264_ratecontrol_new's statistics parser, init_pass2, get_qscale / get_diff_limited_q, qscale2bits; no VBV, no zones, no macroblock-tree file: the tree
-//      is off in these sessions) ----
+// ---- 2-pass (x264_ratecontrol_new's statistics parser, init_pass2, get_qscale / get_diff_limited_q, qscale2bits; no VBV, no zones.  The tree is off in these
+//      sessions unless the macroblock-tree statistics file is switched on and usable: tree_read, host/mbtreestats.hpp) ----
 bool RateControl::p2_load(const char *path)
 {
     FILE *f = fopen(path, "rb");
@@ -409,7 +415,8 @@ bool RateControl::p2_init()
     for (auto &e : E) duration += e.dur;
     duration /= fps * E[0].dur;                               // (durations are in ticks of one picture here: constant frame rate, codec.c:1476-1480)
     const double all_available_bits = p->rc.i_bitrate * 1000.0 * duration;
-    const double qblur = p->rc.f_qblur, cplxblur = p->rc.f_complexity_blur, qcomp = p->rc.f_qcompress;
+    // (under the macroblock-tree statistics file rc->qcompress is 1, as in single-pass tree sessions: the tree has done the complexity weighting)
+    const double qblur = p->rc.f_qblur, cplxblur = p->rc.f_complexity_blur, qcomp = tree_read ? qcompress : p->rc.f_qcompress;
     const int filter_size = (int)(qblur * 4) | 1;
     const double base_cplx = (double)nmb * (p->i_bframe ? 120 : 80);
     const double qstep = pow(2.0, p->rc.i_qp_step / 6.0);
@@ -445,7 +452,8 @@ bool RateControl::p2_init()
     double last_q[3], acc_p_qp = 0, acc_p_norm = 0, last_acc_p_norm = 1;
     int last_non_b = -1;
     auto get_qscale = [&](const Pass2Entry &e, double rate_factor) {
-        double q = pow(e.blurred, 1 - qcomp);
+        // the RCEQ value; under the tree the frame-duration term alone (pick_qp's expression for single-pass tree sessions)
+        double q = tree_read ? pow(1.0 / dur_ratio, 1.0 - p->rc.f_qcompress) : pow(e.blurred, 1 - qcomp);
         if (!std::isfinite(q) || e.tex + e.mv == 0) q = last_q[p2_kind(e.type)];
         else q /= rate_factor;
         return q;

@@ -14,6 +14,9 @@ struct RateControl {
     // which rate control the session runs (session policy: set by x264_encoder_open before open()); none: constant quantiser
     bool crf = false, abr = false;       // single pass: the quantisers follow the lookahead's frame costs (ABR: and the coded sizes)
     bool pass1 = false, pass2 = false;   // a statistics line per coded picture; every quantiser planned from the first pass' statistics
+    // the macroblock-tree statistics file (host/mbtreestats.hpp; session policy as well): a first pass that writes it says so in the statistics' header; a second
+    // pass that reads it plans with the tree's RCEQ
+    bool tree_write = false, tree_read = false;
     bool by_cost() const { return crf || abr; }
     bool reads_sizes() const { return abr || pass1 || pass2 || vbv; }          // end() feeds start(): such a session codes one picture at a time
     // VBV (session policy as well: x264_encoder_open validates --vbv-maxrate / --vbv-bufsize / --vbv-init / --nal-hrd and leaves the effective values in the parameters)

@@ -131,6 +131,7 @@ def last_vbv(h, cap=80):
 _sig("x264host_last_quality", _i, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint64)])
 _sig("x264host_quality_summary", _i, [C.c_void_p, C.c_char_p, _i])
 _sig("x264host_nr_offsets", _i, [C.c_void_p, C.c_void_p])
+_sig("x264host_last_mb_qp_offsets", _i, [C.c_void_p, C.c_void_p, _i])
 _sig("x264host_psnr", C.c_double, [C.c_double, C.c_double])
 _sig("x264host_ssim_db", C.c_double, [C.c_double])
 LEVELS = (Level * 21).in_dll(H, "x264_levels")

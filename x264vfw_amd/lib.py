@@ -180,6 +180,8 @@ _SIGS = {
     "x264gpu_slicetype_propagate": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp]),
     "x264gpu_slicetype_finish": (_i, [_vp, _i, C.c_float, C.c_float, _vp, _vp]),
     "x264gpu_slicetype_propagate_cost": (_vp, [_vp, _i]),
+    "x264gpu_mbtree_pack": (_i, [_vp, _i, _vp, _vp]),
+    "x264gpu_mbtree_unpack": (_i, [_vp, _i, _vp, _vp]),
 }
 
 EXPORTS = tuple(_SIGS)
