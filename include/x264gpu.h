@@ -393,6 +393,11 @@ int  x264gpu_encoder_profile_begin(x264gpu_encoder *enc, int max_calls);
 /* diagnostics (NULL = off, the default): d_counters = [streams][16 waves][16] uint64 cycle counters written by the
  * wavefront kernels: {intra wait, work, MBs, total, deblock wait, work, MBs, total, 5 intra section sums, 3 spare} */
 int  x264gpu_encoder_set_debug(x264gpu_encoder *enc, void *d_counters);
+/* diagnostics: the instantiations of the macroblock loop (k_mb_slice<M, ME, PS, RD, BS, PSY, NR>) this process has launched since the last reset, whichever
+ * encoder launched them: up to `max` distinct ids into ids[] in the order of their first launch (ids may be NULL with max 0), the return value is their
+ * number; reset != 0 empties the set afterwards.  An id spells the template tuple in hex digits: M << 12 | ME << 8 | RD << 4 | PS << 3 | BS << 2 | PSY << 1 | NR.
+ * Host side only (a launch notes its id before it is queued); thread-safe. */
+int  x264gpu_mb_kernels_seen(uint32_t *ids, int max, int reset);
 int  x264gpu_encoder_profile_end(x264gpu_encoder *enc, void *stream, double *ms_sum, int *launches);
 /* Quantisers of the following x264gpu_encode_frames calls (every stream of the call shares them): what x264_ratecontrol_start
  * hands the slice ([x264-upstream] encoder/ratecontrol.c; CRF / scenecut sessions change it per picture). */

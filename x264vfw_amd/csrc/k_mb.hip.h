@@ -3256,9 +3256,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MB_WAVES_PER
 
 // The launch of the macroblock loop: one workgroup of one wavefront per stream and slice.  (The single workgroups of several streams' launches — a session's pictures
 // in flight — run side by side at a lone picture's rate, 1.0 - 1.1 s against 0.97 s: the dispatcher does not stack them on one SIMD; profiles/r06_inflight_kernel_timeline.txt)
-static inline void mb_launch(void (*kern)(EncK), const EncK &k, int streams, hipStream_t st)
+// Every launch notes on the host which instantiation it is (mb_kernels_seen.hip; x264gpu_mb_kernels_seen hands the set out), so that a test can prove which of the
+// compiled kernels it ran: the id spells the template tuple in hex digits, 0x<M><ME><RD><PS BS PSY NR> (tests/mb_instantiations.py packs the same way).
+void mb_kernel_note(uint32_t id);
+template <int M, int ME, bool PS, int RD = 0, bool BS = false, bool PSY = false, bool NR = false>
+static inline void mb_launch(const EncK &k, int streams, hipStream_t st)
 {
-    hipLaunchKernelGGL(kern, dim3(streams, k.slices > 1 ? k.slices : 1), dim3(64), 0, st, k);
+    static_assert(M < 16 && ME < 16 && RD < 16, "the id holds one hex digit each");
+    mb_kernel_note((uint32_t)(M << 12 | ME << 8 | RD << 4 | PS << 3 | BS << 2 | PSY << 1 | (int)NR));
+    hipLaunchKernelGGL((k_mb_slice<M, ME, PS, RD, BS, PSY, NR>), dim3(streams, k.slices > 1 ? k.slices : 1), dim3(64), 0, st, k);
 }
 
 }  // namespace x264gpu

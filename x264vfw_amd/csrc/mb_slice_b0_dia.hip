@@ -6,7 +6,7 @@ namespace x264gpu {
 void launch_mb_slice_b0_dia(const EncK &k, int streams, hipStream_t st)
 {
     // (with the trellis quantiser the final encode reads the slice's CABAC state: the instantiation that carries it)
-    if (k.rd && k.cabac && k.trellis) mb_launch(k_mb_slice<2, 0, true, 7, true>, k, streams, st);
-    else mb_launch(k_mb_slice<2, 0, true, 0, true>, k, streams, st);
+    if (k.rd && k.cabac && k.trellis) mb_launch<2, 0, true, 7, true>(k, streams, st);
+    else mb_launch<2, 0, true, 0, true>(k, streams, st);
 }
 }  // namespace x264gpu

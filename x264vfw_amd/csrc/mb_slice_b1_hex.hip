@@ -5,6 +5,6 @@
 namespace x264gpu {
 void launch_mb_slice_b1_hex(const EncK &k, int streams, hipStream_t st)
 {
-    mb_launch(k_mb_slice<2, 1, true, 1, true>, k, streams, st);
+    mb_launch<2, 1, true, 1, true>(k, streams, st);
 }
 }  // namespace x264gpu

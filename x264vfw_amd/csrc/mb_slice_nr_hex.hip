@@ -13,8 +13,8 @@ void launch_mb_slice_nr_ref_b_hex(const EncK &k, int streams, hipStream_t st);
 void launch_mb_slice_nr_ref_b_umh(const EncK &k, int streams, hipStream_t st);
 void launch_mb_slice_nr_hex(const EncK &k, int streams, hipStream_t st)
 {
-    if (k.trellis & 64) mb_launch(k_mb_slice<2, 1, true, 4, false, false, true>, k, streams, st);
-    else mb_launch(k_mb_slice<2, 1, true, 3, false, false, true>, k, streams, st);
+    if (k.trellis & 64) mb_launch<2, 1, true, 4, false, false, true>(k, streams, st);
+    else mb_launch<2, 1, true, 3, false, false, true>(k, streams, st);
 }
 // nr sessions are RD sessions with CABAC and the trellis quantiser under --me hex / umh (x264gpu_encoder_set_nr checks); I slices run the plain kernels
 void launch_mb_slice_nr(const EncK &k, int streams, int slice_type, hipStream_t st)

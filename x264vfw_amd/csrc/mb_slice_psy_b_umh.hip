@@ -6,8 +6,8 @@
 namespace x264gpu {
 void launch_mb_slice_psy_b_umh(const EncK &k, int streams, hipStream_t st)
 {
-    if (k.subme < 7) mb_launch(k_mb_slice<2, 2, true, 7, true, true>, k, streams, st);
-    else if (k.trellis & 64) mb_launch(k_mb_slice<2, 2, true, 4, true, true>, k, streams, st);
-    else mb_launch(k_mb_slice<2, 2, true, 3, true, true>, k, streams, st);
+    if (k.subme < 7) mb_launch<2, 2, true, 7, true, true>(k, streams, st);
+    else if (k.trellis & 64) mb_launch<2, 2, true, 4, true, true>(k, streams, st);
+    else mb_launch<2, 2, true, 3, true, true>(k, streams, st);
 }
 }  // namespace x264gpu

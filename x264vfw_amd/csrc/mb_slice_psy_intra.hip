@@ -18,10 +18,10 @@ void launch_mb_slice_psy(const EncK &k, int streams, int slice_type, hipStream_t
     const bool umh = k.me_method == 2;
     if (slice_type == X264GPU_SLICE_I) {
         if ((k.rd >> 1) & 63) {          // RD refinement (subme 8)
-            if (k.trellis & 64) mb_launch(k_mb_slice<2, 1, false, 6, false, true>, k, streams, st);
-            else mb_launch(k_mb_slice<2, 1, false, 5, false, true>, k, streams, st);
-        } else if (k.trellis & 64) mb_launch(k_mb_slice<2, 1, false, 4, false, true>, k, streams, st);
-        else mb_launch(k_mb_slice<2, 1, false, 3, false, true>, k, streams, st);
+            if (k.trellis & 64) mb_launch<2, 1, false, 6, false, true>(k, streams, st);
+            else mb_launch<2, 1, false, 5, false, true>(k, streams, st);
+        } else if (k.trellis & 64) mb_launch<2, 1, false, 4, false, true>(k, streams, st);
+        else mb_launch<2, 1, false, 3, false, true>(k, streams, st);
     } else if (slice_type == X264GPU_SLICE_B) {
         if (k.subme >= 9 || (k.rd & 64)) (umh ? launch_mb_slice_psy_ref_b_umh : launch_mb_slice_psy_ref_b_hex)(k, streams, st);
         else (umh ? launch_mb_slice_psy_b_umh : launch_mb_slice_psy_b_hex)(k, streams, st);

@@ -6,7 +6,7 @@
 namespace x264gpu {
 void launch_mb_slice_psy_ref_b_umh(const EncK &k, int streams, hipStream_t st)
 {
-    if (k.trellis & 64) mb_launch(k_mb_slice<5, 2, true, 6, true, true>, k, streams, st);
-    else mb_launch(k_mb_slice<5, 2, true, 5, true, true>, k, streams, st);
+    if (k.trellis & 64) mb_launch<5, 2, true, 6, true, true>(k, streams, st);
+    else mb_launch<5, 2, true, 5, true, true>(k, streams, st);
 }
 }  // namespace x264gpu

@@ -6,7 +6,7 @@
 namespace x264gpu {
 void launch_mb_slice_psy_ref_hex(const EncK &k, int streams, hipStream_t st)
 {
-    if (k.trellis & 64) mb_launch(k_mb_slice<5, 1, true, 6, false, true>, k, streams, st);
-    else mb_launch(k_mb_slice<5, 1, true, 5, false, true>, k, streams, st);
+    if (k.trellis & 64) mb_launch<5, 1, true, 6, false, true>(k, streams, st);
+    else mb_launch<5, 1, true, 5, false, true>(k, streams, st);
 }
 }  // namespace x264gpu

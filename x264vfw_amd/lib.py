@@ -133,7 +133,8 @@ _SIGS = {
     "x264gpu_encoder_stage_name": (C.c_char_p, [_i]),
     "x264gpu_encoder_profile_begin": (_i, [_vp, _i]),
     "x264gpu_encoder_set_debug": (_i, [_vp, _vp]),
-    "x264gpu_encoder_profile_end": (_i, [_vp, _vp, C.POINTER(C.c_double), C.POINTER(_i)]),
+    "x264gpu_mb_kernels_seen": (_i, [C.POINTER(C.c_uint32), _i, _i]),
+    "x264gpu_encoder_profile_end":(_i, [_vp, _vp, C.POINTER(C.c_double), C.POINTER(_i)]),
     "x264gpu_encoder_set_qp": (_i, [_vp, _i, _i]),
     "x264gpu_encoder_set_mb_qp_offsets": (_i, [_vp, _vp]),
     "x264gpu_encoder_set_stream_qpms": (_i, [_vp, _vp, _vp]),
