@@ -114,6 +114,13 @@ int x264gpu_trellis_blocks_ex(const int16_t *d_coefs, int nblk, int cat, int qp,
 int x264gpu_trellis_blocks_psy(const int16_t *d_coefs, const int16_t *d_fenc_dct, int nblk, int cat, int qp, int intra, int psy_trellis_q8, const uint8_t *d_states460,
                                int16_t *d_levels, uint8_t *d_nz, int force_general, uint8_t *d_paths, void *stream);
 int x264gpu_mc_weight(const uint8_t *d_src, size_t bytes, int scale, int denom, int offset, uint8_t *d_out, void *stream);
+/* Rows that lie anywhere in device memory into one contiguous array, in one launch on `stream`: row r of d_dst ([rows][row_bytes]) becomes a copy of the row_bytes
+ * bytes at d_rows[r]; a NULL d_rows[r] gives a row of zeros.  d_rows itself is a DEVICE array of `rows` device pointers, read when the kernel runs.  Any row_bytes
+ * and any alignment of sources and destination (16-byte vectors where a source and its destination row sit alike within 16 bytes, dwords or bytes otherwise, and
+ * bytes at a row's unaligned ends); no byte outside [d_dst, d_dst + rows * row_bytes) is written, none outside a source row is read.  The sources must not overlap
+ * d_dst.  EINVAL for a null d_rows / d_dst, rows < 1 or row_bytes == 0.  The host's cross-session batcher builds the [streams][mb_count] arrays of
+ * x264gpu_encoder_set_mb_qp_offsets / _set_lowres_mvs / _set_lowres_mvs1 from its members' own arrays with it (host/batch.cpp). */
+int x264gpu_gather_rows(const void *const *d_rows, size_t row_bytes, void *d_dst, int rows, void *stream);
 /* The level walk of the CABAC size pricing as a primitive ([x264-upstream] encoder/cabac.c coeff_abs_level_minus1 of residual_block_cabac, every block of a
  * macroblock at once — csrc/cabac_rd.hip.h cab_levels_all): n cases; d_levels the macroblocks' levels in x264gpu_mb layout (X264GPU_MB_LEVELS each);
  * d_what five ints a case: luma category (2 = 4x4, 5 = 8x8, 1 = Intra_16x16 AC, -1 none), mask of luma blocks, of chroma AC blocks (plane * 4 + block), of

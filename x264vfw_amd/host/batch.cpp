@@ -13,6 +13,9 @@
 #include <condition_variable>
 #include <mutex>
 
+// The gather entry is resolved weakly: with a device library without it (an older build; the tests' CPU stand-in) the group copies row by row instead.
+#pragma weak x264gpu_gather_rows
+
 namespace x264host {
 
 struct BatchGroup {
@@ -31,6 +34,14 @@ struct BatchGroup {
     int qflags = 0; x264gpu_quality *d_q = nullptr, *d_q2 = nullptr;          // --psnr / --ssim of the members (all alike): one statistic per stream behind every round, two buffers as d_mb / d_mb2
     // --nr of the members (one strength a group): per stream the offsets, the last round's statistics and the running state; the update is queued behind every round
     int nr = 0; x264gpu_nr_offsets *d_nr_off = nullptr; x264gpu_nr_sums *d_nr_pic = nullptr, *d_nr_state = nullptr;
+    // the members' side inputs (Batch::SideInputs; side: which arrays the members' lookaheads produce, and what else they agree in): per member the pointers handed in
+    // with this round's picture; per array two generations of the gathered [N][nmb] rows, used in turn as the output buffers are (round k + 2 is launched only after
+    // every member has round k's results: nothing of round k reads its generation any more); two generations of the device table of [3][N] row pointers the gather
+    // reads, with its host image; the "absent" row that stands in for a member without vectors (first entry 0x7fff: x264gpu_encoder_set_lowres_mvs); the event that
+    // tells the compute stream where the default stream — the members' lookaheads — stood when the round was complete
+    Batch::Side side; std::vector<Batch::SideInputs> side_in; std::vector<const void *> side_tab;
+    uint8_t *d_side[3][2] = { { nullptr, nullptr }, { nullptr, nullptr }, { nullptr, nullptr } }; const void **d_side_tab[2] = { nullptr, nullptr };
+    int16_t *d_mv_absent = nullptr; void *ev_side = nullptr;
     std::vector<void *> up_streams;          // the members' uploads: a handful of streams dealt round-robin (a stream per member was 0.7 ms to create and 0.6 ms to destroy, x 2048, serialised in the runtime)
     long ev_round[2] = { 0, 0 }, ev_done[2] = { 0, 0 }; bool ev_waiting[2] = { false, false }; std::string ev_err;      // per buffer pair: the round recorded behind it (1-based), the last one known complete, a member is waiting for the event
     long launched = 0;            // rounds whose kernels have been issued: the helper threads start entropy coding round k once round k + 1 is on the device (or when asked to hurry),
@@ -91,11 +102,52 @@ void batch_destroy(BatchGroup *g)
     if (g->d_nr_off) x264gpu_free(g->d_nr_off);
     if (g->d_nr_pic) x264gpu_free(g->d_nr_pic);
     if (g->d_nr_state) x264gpu_free(g->d_nr_state);
+    for (int a = 0; a < 3; a++) for (int i = 0; i < 2; i++) if (g->d_side[a][i]) x264gpu_free(g->d_side[a][i]);
+    for (int i = 0; i < 2; i++) if (g->d_side_tab[i]) x264gpu_free((void *)g->d_side_tab[i]);
+    if (g->d_mv_absent) x264gpu_free(g->d_mv_absent);
+    if (g->ev_side) x264gpu_event_destroy(g->ev_side);
     for (int i = 0; i < 2; i++) if (g->ev[i]) x264gpu_event_destroy(g->ev[i]);
     if (g->dl_stream) x264gpu_stream_destroy(g->dl_stream);
     for (void *st : g->up_streams) x264gpu_stream_destroy(st);
     if (g->cs) x264gpu_stream_destroy(g->cs);
     delete g;
+}
+
+// in front of a round of a group whose members have lookaheads: their quantiser offsets and low-resolution vectors of this round's pictures become the device
+// encoder's [N][nmb] arrays — on the stream the round runs on, behind what the members' lookaheads wrote on the default stream.  first: a member that arrived
+// (a stream whose session has gone takes its rows: coded along, thrown away).  false: g->err says why
+bool batch_side_inputs(BatchGroup *g, int first)
+{
+    const size_t N = (size_t)g->N, row = g->nmb * 4;          // a float, or a vector of two int16, a macroblock
+    const int gen = (int)(g->round & 1);
+    void *const st = g->async ? g->cs : nullptr;
+    bool any[3] = { false, false, false };
+    for (size_t s = 0; s < N; s++) {
+        const Batch::SideInputs &in = g->side_in[g->arrived[s] ? s : (size_t)first];
+        const void *p[3] = { in.d_offsets, in.d_mvs0, in.d_mvs1 };
+        for (int a = 0; a < 3; a++) { g->side_tab[(size_t)a * N + s] = p[a]; any[a] = any[a] || p[a]; }
+    }
+    for (int a = 0; a < 3; a++) if (any[a] && !g->d_side[a][gen]) { g->err = "X264GPU_BATCH: a session handed in side inputs its group was not opened for"; return false; }
+    // (a member without vectors among members with them: "absent" is a row that says so, not a row of zero vectors)
+    for (int a = 1; a < 3; a++) if (any[a]) for (size_t s = 0; s < N; s++) if (!g->side_tab[(size_t)a * N + s]) g->side_tab[(size_t)a * N + s] = g->d_mv_absent;
+    bool ok = true;
+    if (any[0] || any[1] || any[2]) {
+        if (g->async) ok = x264gpu_event_record(g->ev_side, nullptr) == X264GPU_OK && x264gpu_stream_wait_event(st, g->ev_side) == X264GPU_OK;
+        if (ok && x264gpu_gather_rows) {
+            // the table goes up on an upload stream, not on the compute stream: x264gpu_memcpy_h2d waits for its stream, and the compute stream still runs the round before
+            ok = x264gpu_memcpy_h2d((void *)g->d_side_tab[gen], g->side_tab.data(), 3 * N * sizeof(void *), g->up_streams.empty() ? nullptr : g->up_streams[0]) == X264GPU_OK;
+            for (int a = 0; a < 3 && ok; a++) if (any[a]) ok = x264gpu_gather_rows(g->d_side_tab[gen] + (size_t)a * N, row, g->d_side[a][gen], g->N, st) == X264GPU_OK;
+        } else
+            for (int a = 0; a < 3 && ok; a++) if (any[a]) for (size_t s = 0; s < N && ok; s++) {
+                const void *src = g->side_tab[(size_t)a * N + s];
+                ok = (src ? x264gpu_memcpy_d2d(g->d_side[a][gen] + s * row, src, row, st) : x264gpu_memset(g->d_side[a][gen] + s * row, 0, row, st)) == X264GPU_OK;
+            }
+    }
+    ok = ok && x264gpu_encoder_set_mb_qp_offsets(g->gpu, any[0] ? (const float *)g->d_side[0][gen] : nullptr) == X264GPU_OK &&
+         x264gpu_encoder_set_lowres_mvs(g->gpu, any[1] ? (const int16_t *)g->d_side[1][gen] : nullptr) == X264GPU_OK &&
+         x264gpu_encoder_set_lowres_mvs1(g->gpu, any[2] ? (const int16_t *)g->d_side[2][gen] : nullptr) == X264GPU_OK;
+    if (!ok) g->err = x264gpu_last_error();
+    return ok;
 }
 
 // the launch of a complete round; g->m is held through lk (released while an overlapping group waits for its kernels)
@@ -112,6 +164,7 @@ void batch_run_round(BatchGroup *g, std::unique_lock<std::mutex> &lk)
                 memcmp(a.slot, b.slot, sizeof(a.slot)) || a.blind_dupe != b.blind_dupe) { g->round_rc = -1; g->err = "the sessions of a batch must submit pictures of the same structure (same picture count, keyint, bframes, forced types)"; }
         }
         const bool second = g->overlap && (g->round & 1);          // the output buffers of this round (the other pair may still be downloading)
+        if (!g->round_rc && (g->side.offsets || g->side.mvs) && !batch_side_inputs(g, first)) g->round_rc = -1;
         if (!g->round_rc && x264gpu_encode_pictures(g->gpu, g->d_in, g->pics.data(), second ? g->d_mb2 : g->d_mb, second ? g->d_lv2 : g->d_lv, g->async ? g->cs : nullptr) != X264GPU_OK) { g->round_rc = -1; g->err = x264gpu_last_error(); }
         // --nr: a batch session's picture is accepted as it is coded (no VBV in a group): every stream's statistics join its state, its next offsets follow, in front of the next round
         if (!g->round_rc && g->nr && nr_update_queue(g->d_nr_off, g->d_nr_state, g->d_nr_pic, g->N, g->nr, g->async ? g->cs : nullptr) != X264GPU_OK) { g->round_rc = -1; g->err = x264gpu_last_error(); }
@@ -143,7 +196,7 @@ void batch_run_round(BatchGroup *g, std::unique_lock<std::mutex> &lk)
 
 }  // namespace
 
-bool Batch::join(const x264gpu_config &cfg1, int N, size_t insz, size_t nmb, int qflags, int nr)
+bool Batch::join(const x264gpu_config &cfg1, int N, size_t insz, size_t nmb, int qflags, int nr, const Side &side)
 {
     std::lock_guard<std::mutex> lk(g_batch_mu);
     int dev = 0;
@@ -151,7 +204,8 @@ bool Batch::join(const x264gpu_config &cfg1, int N, size_t insz, size_t nmb, int
     for (BatchGroup *og : g_batch_groups) {
         x264gpu_config a = og->cfg, b = cfg1;
         a.streams = b.streams = 0;
-        if (og->N == N && og->device == dev && og->joined < N && !og->closed && og->qflags == qflags && og->nr == nr && !memcmp(&a, &b, sizeof(a))) {
+        if (og->N == N && og->device == dev && og->joined < N && !og->closed && og->qflags == qflags && og->nr == nr &&
+            og->side.offsets == side.offsets && og->side.mvs == side.mvs && og->side.key == side.key && !memcmp(&a, &b, sizeof(a))) {
             std::lock_guard<std::mutex> lg(og->m);
             g = og; s = og->joined++; og->active++; og->member[(size_t)s] = 1;
             og->cv.notify_all();
@@ -160,8 +214,8 @@ bool Batch::join(const x264gpu_config &cfg1, int N, size_t insz, size_t nmb, int
     }
     if (!g) {
         BatchGroup *ng = new BatchGroup();
-        ng->cfg = cfg1; ng->cfg.streams = N; ng->N = N; ng->device = dev; ng->insz = insz; ng->nmb = nmb; ng->qflags = qflags; ng->nr = nr;
-        ng->member.assign((size_t)N, 0); ng->arrived.assign((size_t)N, 0); ng->pics.resize((size_t)N);
+        ng->cfg = cfg1; ng->cfg.streams = N; ng->N = N; ng->device = dev; ng->insz = insz; ng->nmb = nmb; ng->qflags = qflags; ng->nr = nr; ng->side = side;
+        ng->member.assign((size_t)N, 0); ng->arrived.assign((size_t)N, 0); ng->pics.resize((size_t)N); ng->side_in.resize((size_t)N); ng->side_tab.assign(3 * (size_t)N, nullptr);
         if (x264gpu_encoder_create(&ng->gpu, &ng->cfg) != X264GPU_OK ||
             x264gpu_malloc((void **)&ng->d_in, (size_t)N * insz) != X264GPU_OK ||
             x264gpu_malloc((void **)&ng->d_mb, (size_t)N * nmb * sizeof(x264gpu_mb)) != X264GPU_OK ||
@@ -172,6 +226,19 @@ bool Batch::join(const x264gpu_config &cfg1, int N, size_t insz, size_t nmb, int
                    x264gpu_memset(ng->d_nr_off, 0, (size_t)N * sizeof(x264gpu_nr_offsets), nullptr) != X264GPU_OK || x264gpu_memset(ng->d_nr_pic, 0, (size_t)N * sizeof(x264gpu_nr_sums), nullptr) != X264GPU_OK ||
                    x264gpu_memset(ng->d_nr_state, 0, (size_t)N * sizeof(x264gpu_nr_sums), nullptr) != X264GPU_OK || x264gpu_stream_sync(nullptr) != X264GPU_OK ||
                    nr_set(ng->gpu, ng->d_nr_off, ng->d_nr_pic) != X264GPU_OK)) { batch_destroy(ng); return false; }
+        if (side.offsets || side.mvs) {
+            // the gathered arrays and the tables of row pointers, two generations each; the vectors' "absent" row
+            const size_t rows = (size_t)N * nmb * 4;
+            bool ok = x264gpu_event_create(&ng->ev_side) == X264GPU_OK;
+            for (int i = 0; i < 2 && ok; i++) {
+                ok = x264gpu_malloc((void **)&ng->d_side_tab[i], 3 * (size_t)N * sizeof(void *)) == X264GPU_OK && (!side.offsets || x264gpu_malloc((void **)&ng->d_side[0][i], rows) == X264GPU_OK) &&
+                     (!side.mvs || (x264gpu_malloc((void **)&ng->d_side[1][i], rows) == X264GPU_OK && x264gpu_malloc((void **)&ng->d_side[2][i], rows) == X264GPU_OK));
+            }
+            const int16_t absent = 0x7fff;
+            ok = ok && (!side.mvs || (x264gpu_malloc((void **)&ng->d_mv_absent, nmb * 4) == X264GPU_OK && x264gpu_memset(ng->d_mv_absent, 0, nmb * 4, nullptr) == X264GPU_OK &&
+                                      x264gpu_stream_sync(nullptr) == X264GPU_OK && x264gpu_memcpy_h2d(ng->d_mv_absent, &absent, sizeof(absent), nullptr) == X264GPU_OK));
+            if (!ok) { batch_destroy(ng); return false; }
+        }
         const char *oe = getenv("X264GPU_BATCH_OVERLAP");
         if (!(oe && oe[0] == '0') && !getenv("X264GPU_DUMP_RECORDS") &&
             x264gpu_malloc((void **)&ng->d_mb2, (size_t)N * nmb * sizeof(x264gpu_mb)) == X264GPU_OK &&
@@ -190,18 +257,20 @@ bool Batch::join(const x264gpu_config &cfg1, int N, size_t insz, size_t nmb, int
 }
 
 int Batch::size() const { return g ? g->N : 0; }
+bool Batch::carries_offsets() const { return g && g->side.offsets; }
+bool Batch::carries_mvs() const { return g && g->side.mvs; }
 bool Batch::overlap() const { return g && g->overlap; }
 bool Batch::queued() const { return g && g->async; }
 bool Batch::packed() const { return g && g->pack; }
 
-int Batch::submit(const uint8_t *d_src, const x264gpu_pic &pic, int *buf, std::string &err)
+int Batch::submit(const uint8_t *d_src, const x264gpu_pic &pic, const SideInputs &side, int *buf, std::string &err)
 {
     // (async: on the group's compute stream, i.e. behind the round before — which may still be reading d_in — and in front of this round's launch)
     if (x264gpu_memcpy_d2d(g->d_in + (size_t)s * g->insz, d_src, g->insz, g->async ? g->cs : nullptr) != X264GPU_OK) { err = x264gpu_last_error(); return -1; }
     std::unique_lock<std::mutex> lk(g->m);
     // every member must have been opened before the first picture is coded: a late joiner would be a picture behind for good
     if (!g->cv.wait_for(lk, std::chrono::seconds(60), [&] { return g->joined == g->N; })) { err = "X264GPU_BATCH: fewer sessions were opened than the batch size"; return -1; }
-    g->pics[(size_t)s] = pic; g->arrived[(size_t)s] = 1; g->n_arrived++;
+    g->pics[(size_t)s] = pic; g->side_in[(size_t)s] = side; g->arrived[(size_t)s] = 1; g->n_arrived++;
     const long my_round = g->round;
     *buf = g->overlap ? (int)(my_round & 1) : 0;
     const long t0 = g->timing ? us_now() : 0;

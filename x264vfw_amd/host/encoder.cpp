@@ -137,6 +137,7 @@ struct x264_t {
     // a picture of a session on the DPB model between plan and finish: what was decided for it, what the device is told, what the slice writer is told;
     // with several pictures in flight also its launch context and the DPB slots it reads or writes
     struct PicPlan { SliceType::Pic pl; x264gpu_pic pic; SliceParams sp; int nal_ref_idc = 0; double qpf = 0; const float *d_offsets = nullptr; bool direct_auto_write = false; char direct_char = '-';
+                     const int16_t *d_mvs[2] = { nullptr, nullptr };          // the lookahead's vectors towards reference 0 of each list (nullptr: none)
                      int ctx = 0; unsigned slots_used = 0; bool last_minigop_b = false; };
     void *ev_la = nullptr;               // the default stream's position when a picture is issued: its upload, offsets and lowres vectors are complete behind it
     std::vector<LaunchCtx> lctx; std::deque<PicPlan> fl; int inflight = 1; int slot_writer[8] = { -1, -1, -1, -1, -1, -1, -1, -1 }; int last_retired_slot = -1;
@@ -455,7 +456,8 @@ static void open_modes(x264_t *h)
         if (p.i_bframe < 2) p.i_bframe_pyramid = 0;
         if (p.b_open_gop) { xlog(&p, X264_LOG_WARNING, "open-gop is not implemented in the MI355X path: closed GOPs\n"); p.b_open_gop = 0; }
         if (p.analyse.i_direct_mv_pred < 1 || p.analyse.i_direct_mv_pred > 3) { xlog(&p, X264_LOG_INFO, "direct %d -> spatial (B macroblocks without direct prediction are not in the MI355X path)\n", p.analyse.i_direct_mv_pred); p.analyse.i_direct_mv_pred = 1; }
-        if (p.analyse.i_direct_mv_pred != 1 && getenv("X264GPU_BATCH")) { xlog(&p, X264_LOG_INFO, "direct temporal / auto: not in cross-session batches: spatial\n"); p.analyse.i_direct_mv_pred = 1; }
+        // (temporal direct prediction is a flag a stream of the group's encoder; auto's choice needs the probe counts read back behind every B picture, which would serialise queued rounds)
+        if (p.analyse.i_direct_mv_pred == 3 && getenv("X264GPU_BATCH")) { xlog(&p, X264_LOG_INFO, "direct auto: not in cross-session batches (its choice waits for every B picture's probe counts): spatial\n"); p.analyse.i_direct_mv_pred = 1; }
     } else { p.i_bframe_pyramid = 0; p.analyse.b_weighted_bipred = 0; }
     h->bframes = p.i_bframe; h->bpyramid = p.i_bframe_pyramid ? 1 : 0;
     h->direct_mode = p.i_bframe ? p.analyse.i_direct_mv_pred : 1;
@@ -475,9 +477,9 @@ static void open_modes(x264_t *h)
         // cross-session batcher: this session joins (or starts) a group of N sessions coded in lock-step, if its picture structure is fixed
         const int bn = atoi(be);
         if (bn >= 2) {
-            const bool tree = p.rc.b_mb_tree && p.rc.i_rc_method != X264_RC_CQP && p.rc.i_lookahead > 0;
+            // (macroblock-tree, --aq-mode 2 / 3 and --direct temporal leave every picture's type alone: the member's lookahead runs them, the group carries what it decides)
             const char *why = p.i_threads > 1 ? "threads 1" : h->slices > 1 || p.b_sliced_threads ? "one slice per picture" : p.i_scenecut_threshold > 0 ? "scenecut 0" :
-                              (h->bframes && p.i_bframe_adaptive) ? "b-adapt 0" : tree ? "no-mbtree" : p.rc.i_rc_method == X264_RC_ABR ? "constant-quantiser or CRF rate control" : nullptr;
+                              (h->bframes && p.i_bframe_adaptive) ? "b-adapt 0" : p.rc.i_rc_method == X264_RC_ABR ? "constant-quantiser or CRF rate control" : nullptr;
             if (why) xlog(&p, X264_LOG_WARNING, "X264GPU_BATCH needs %s (picture k must have the same type in every session of a batch): this session runs on its own\n", why);
             else { h->batch.want = bn; h->dpbmode = true; }
         }
@@ -551,8 +553,8 @@ static void open_quantisers(x264_t *h)
     { const int cap = p.i_keyint_max < 250 ? (p.i_keyint_max > 1 ? p.i_keyint_max : 1) : 250;
       p.rc.i_lookahead = p.rc.b_mb_tree ? clampi(p.rc.i_lookahead, 1, cap) : h->vbv ? clampi(p.rc.i_lookahead, 0, cap) : 0; }
     p.rc.i_aq_mode = clampi(p.rc.i_aq_mode, 0, 3);
-    if (p.rc.i_aq_mode > X264_AQ_VARIANCE && (!h->dpbmode || getenv("X264GPU_BATCH"))) {
-        xlog(&p, X264_LOG_WARNING, "aq-mode %d needs B-frames or weightp 2 (the DPB-model path, one session a device encoder) in the MI355X path: aq-mode 1\n", p.rc.i_aq_mode); p.rc.i_aq_mode = X264_AQ_VARIANCE;
+    if (p.rc.i_aq_mode > X264_AQ_VARIANCE && !h->dpbmode) {
+        xlog(&p, X264_LOG_WARNING, "aq-mode %d needs B-frames or weightp 2 (the DPB-model path) in the MI355X path: aq-mode 1\n", p.rc.i_aq_mode); p.rc.i_aq_mode = X264_AQ_VARIANCE;
     }
     p.rc.i_qp_constant = clampi(qp, 1, 51);
     p.rc.i_qp_min = clampi(p.rc.i_qp_min, 1, 51); p.rc.i_qp_max = clampi(p.rc.i_qp_max, p.rc.i_qp_min, 51);
@@ -678,8 +680,19 @@ static bool open_device(x264_t *h)
         return h->gops.open(p, cfg, h->rc, { h->G, h->keyint, h->nmb, h->qp_i, h->qp_p, h->bframes, h->bpyramid, h->weightp, h->log2_max_frame_num, h->direct_mode, h->dpbmode,
                                              h->device, slice_params_base(h), write_coded });
     } else if (ok_setup && h->batch.want) {
-        ok_setup = h->batch.join(cfg, h->batch.want, insz, (size_t)h->nmb, h->ql.flags, p.analyse.i_noise_reduction);
-        if (ok_setup) xlog(&p, X264_LOG_INFO, "X264GPU_BATCH: stream %d of a batch of %d sessions%s\n", h->batch.index(), h->batch.size(), h->batch.queued() ? " (rounds queued: uploads overlap the device)" : "");
+        // what the session's own lookahead will hand the group with every picture (bmode_plan): offsets from the tree or --aq-mode 2 / 3, vectors from the lookahead object
+        // the tree (or a VBV plan) opens; sessions that differ in any of it, or in what shapes it, form groups of their own
+        Batch::Side side;
+        const bool la_object = p.rc.b_mb_tree || (h->vbv && p.rc.i_lookahead > 0);
+        side.offsets = p.rc.b_mb_tree || (p.rc.i_aq_mode >= 2 && p.rc.f_aq_strength > 0);
+        side.mvs = la_object;
+        side.key = (p.rc.b_mb_tree ? 1 : 0) | p.rc.i_aq_mode << 1 | h->direct_mode << 4 | p.rc.i_lookahead << 8;
+        ok_setup = h->batch.join(cfg, h->batch.want, insz, (size_t)h->nmb, h->ql.flags, p.analyse.i_noise_reduction, side);
+        if (ok_setup) xlog(&p, X264_LOG_INFO, "X264GPU_BATCH: stream %d of a batch of %d sessions%s%s\n", h->batch.index(), h->batch.size(), h->batch.queued() ? " (rounds queued: uploads overlap the device)" : "",
+                           side.offsets && side.mvs ? "; the group carries each member's quantiser offsets and lookahead vectors" : side.offsets ? "; the group carries each member's quantiser offsets" :
+                           side.mvs ? "; the group carries each member's lookahead vectors" : "");
+        if (ok_setup && la_object && h->weightp)
+            xlog(&p, X264_LOG_INFO, "weightp %d in a batch: a fade's explicit weights are not coded (the streams of a device call share them; the lookahead still weighs fades for its costs)\n", h->weightp);
     } else if (ok_setup) {
         ok_setup = x264gpu_encoder_create(&h->gpu, &cfg) == X264GPU_OK &&
                    x264gpu_malloc((void **)&h->d_mb, (size_t)h->nmb * sizeof(x264gpu_mb)) == X264GPU_OK &&
@@ -1022,7 +1035,8 @@ static void bmode_plan(x264_t *h, x264_t::PicPlan &f, x264gpu_encoder *gpu, long
     // the disposable pictures coded right behind this one (x264_reference_hierarchy_reset looks at them)
     int fc[16], ff[16], nf = 0;
     for (size_t i = 0; i < behind.size() && nf < 16 && behind[i].type == PIC_B; i++) { fc[nf] = (int)(coded_index + 1 + (long)i); ff[nf] = behind[i].e.frame; nf++; }
-    const DpbPlan plan = h->dpb.plan(pl.type, pl.e.frame, nf, fc, ff, pl.type == PIC_P && pl.e.w.on ? &pl.e.w : nullptr);
+    // (the explicit weights of a picture are the same in every stream of a device call: a member of a batch group, whose lookahead would find its own, codes fades unweighted)
+    const DpbPlan plan = h->dpb.plan(pl.type, pl.e.frame, nf, fc, ff, pl.type == PIC_P && pl.e.w.on && !h->batch.joined() ? &pl.e.w : nullptr);
     f.nal_ref_idc = plan.nal_ref_idc;
     x264gpu_pic &pic = f.pic;
     pic = plan.pic;
@@ -1059,8 +1073,8 @@ static void bmode_plan(x264_t *h, x264_t::PicPlan &f, x264gpu_encoder *gpu, long
     if (h->slicetype.analyses()) {
         // x264_mb_predict_mv_ref16x16: the lookahead's vectors towards reference 0 of each list as search candidates, when that search ran
         const int dist0 = pic.nref[0] ? (pic.poc - plan.list_poc[0][0]) / 2 : 0, dist1 = pic.nref[1] ? (plan.list_poc[1][0] - pic.poc) / 2 : 0;
-        x264gpu_encoder_set_lowres_mvs(gpu, h->slicetype.lowres_mvs(pl.e.slot, 0, dist0));
-        x264gpu_encoder_set_lowres_mvs1(gpu, h->slicetype.lowres_mvs(pl.e.slot, 1, dist1));
+        f.d_mvs[0] = h->slicetype.lowres_mvs(pl.e.slot, 0, dist0); f.d_mvs[1] = h->slicetype.lowres_mvs(pl.e.slot, 1, dist1);
+        if (gpu) { x264gpu_encoder_set_lowres_mvs(gpu, f.d_mvs[0]); x264gpu_encoder_set_lowres_mvs1(gpu, f.d_mvs[1]); }
     }
     f.d_offsets = nullptr;
     if (h->slicetype.analyses() && h->mbtree)          // P / I / B-reference pictures: what the tree left (AQ - tree); other B pictures: the AQ offsets alone (x264 f_qp_offset_aq)
@@ -1073,8 +1087,9 @@ static void bmode_plan(x264_t *h, x264_t::PicPlan &f, x264gpu_encoder *gpu, long
     }
     else if (h->aq_mode >= 2 && h->aq_strength != 0.f) f.d_offsets = h->q_aq[(size_t)pl.e.slot];      // --aq-mode 2 / 3: the offsets computed when the picture arrived
     // (the serial path names a buffer only when there is one; a launch context is always told, "none" included — and so is a second pass over the tree file,
-    //  whose pictures take turns between two kinds of offsets or none)
-    if (f.d_offsets || !serial || h->tstats.reading) x264gpu_encoder_set_mb_qp_offsets(gpu, f.d_offsets);
+    //  whose pictures take turns between two kinds of offsets or none).  A member of a batch group has no encoder of its own (gpu == nullptr): its vectors and offsets go
+    //  to the group with the picture (Batch::submit), which tells the group's encoder for all streams at once
+    if (gpu && (f.d_offsets || !serial || h->tstats.reading)) x264gpu_encoder_set_mb_qp_offsets(gpu, f.d_offsets);
     if (plan.nal_ref_idc) h->rc.kept(pic.dst, f.qpf, pl.type);
     if (plan.nal_ref_idc) h->slot_l0ref0poc[pic.dst] = pic.nref[0] ? plan.list_poc[0][0] : INT_MIN;
     f.direct_char = is_b ? (pic.direct_temporal ? 't' : 's') : '-';
@@ -1244,7 +1259,7 @@ static int encode_bmode(x264_t *h, x264_nal_t **pp_nal, int *pi_nal, x264_pictur
     const bool deferred = h->batch.overlap();
     if (h->batch.joined()) {
         std::string berr;
-        if (h->batch.submit(d_src, f.pic, &bbuf, berr) ||
+        if (h->batch.submit(d_src, f.pic, { f.d_offsets, f.d_mvs[0], f.d_mvs[1] }, &bbuf, berr) ||
             (!deferred && h->batch.download(bbuf, h->h_mb.data(), h->h_lv.data(), berr, nullptr, &h->hq[0]))) {
             xlog(&p, X264_LOG_ERROR, "x264_encoder_encode: GPU hot path failed: %s\n", berr.c_str());
             h->failed = true;
