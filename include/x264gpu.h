@@ -127,6 +127,13 @@ int x264gpu_gather_rows(const void *const *d_rows, size_t row_bytes, void *d_dst
  * chroma DC planes, luma DC flag; d_r / d_r8 the role-indexed context registers (64 lanes a case, csrc/cabac_layout.hip.h) in, d_r_out / d_r8_out out;
  * d_bits the bits in 1/256 (sign and escape bypass bins included).  tests/test_gpu_prims.py checks it against a serial restatement. */
 int x264gpu_cabac_level_walk(const int16_t *d_levels, const int32_t *d_what, int n, const uint32_t *d_r, const uint32_t *d_r8, uint32_t *d_r_out, uint32_t *d_r8_out, int32_t *d_bits, void *stream);
+/* The other part of that pricing as a primitive: the macroblock layer's own bins (mb_type .. mb_qp_delta, coded_block_flags; contexts 0..104 and
+ * 399..401), which the device collects as one bit string per context and walks through the chain table at the end (csrc/cabac_rd.hip.h cab_put /
+ * cab_walk_a — this runs those two and nothing else).  n cases; case i codes the triples d_first[i] .. d_first[i + 1] - 1 of d_triples (three ints each:
+ * context, bin, how many times, in coding order; a triple on another context is passed over) on the 460 context variables d_states[460 i ..]
+ * ((pStateIdx << 1) | valMPS); d_states_out the variables afterwards, d_bits the bits in 1/256.  tests/test_gpu_cabac_bins.py checks it against a
+ * serial restatement. */
+int x264gpu_cabac_bins_walk(const int32_t *d_triples, const int32_t *d_first, int n, const uint8_t *d_states, uint8_t *d_states_out, int32_t *d_bits, void *stream);
 
 /* ---- input colourspace conversion to I420 -----------------------------------------
  * Replaces the x264vfw_csp_function_t table the driver installs for an I420 encoder (/root/reference/csp.c:436-487,

@@ -4,11 +4,14 @@
 // context variables per slice, moved on by the entropy coding of every finished macroblock, and prices a candidate by running the
 // macroblock's syntax over a COPY of them with the arithmetic coder replaced by a counter in 1/256 bit (entropy[state ^ bin], bypass
 // bin = 256, the I16x16 terminate bin = 7).  The bitstream itself is still written by the host (host/cabac.cpp); what lives here is
-//   * the context variables of the slice a wavefront codes, ONE BYTE EACH IN THREE VGPRs (cab_locate below) — copying them for a candidate
-//     is three moves.  The header syntax and the coded_block_flags are coded by wave-uniform code that reads and writes its register with
-//     v_readlane / a lane select; the residual contexts are laid out so that EVERY LANE OWNS ONE CONTEXT of the block category being
-//     coded: the significance map of a 4x4 block is one step of all lanes, and the serial part of a block is one step per non-zero
-//     coefficient (per-context bin order is all the arithmetic model cares about, and bits add);
+//   * the context variables of the slice a wavefront codes in FOUR VGPRs (cabac_layout.hip.h cab_locate) — copying them for a candidate is
+//     four moves.  The header syntax and the coded_block_flags (registers a0 / a1, one context a lane) are coded by wave-uniform code that
+//     evaluates nothing: every bin, or run of bins, is appended to the bit string of the lane that owns its context (cab_put: a few
+//     independent vector operations), the intra modes' flags and the many-block coded_block_flags arrive as whole strings from a ballot, and
+//     all lanes walk their strings through the chain table once a cab_mb call (cab_walk_a, eight bins a lookup).  The residual contexts are
+//     laid out so that EVERY LANE OWNS ONE CONTEXT of the block category being coded and walk their strings the same way (cab_levels_all).
+//     Per-context bin order is all the arithmetic model cares about, and bits add — tests/cabac_bins_ref.py and tests/cabac_levels_ref.py
+//     restate both parts bin by bin;
 //   * a register with the probability model: lane s = cost of the MPS | cost of the LPS << 9 | state after an LPS << 20;
 //   * cab_mb(): the macroblock layer's bins, either in bitstream order ("evolve": what the finished macroblock leaves behind, skip flag
 //     included) or as x264_macroblock_size_cabac walks them ("size": no skip flag, residual blocks from the last coefficient down with
@@ -33,7 +36,16 @@ static __constant__ const uint16_t c_cabac_entropy[128] = {
 #include "cabac_entropy.inc"
 };
 
-struct Cab { uint32_t a, r, r8; int f8; int f8v; };       // f8: wave-uniform count, f8v: this lane's share of the parallel steps (1/256 bit)
+struct Cab { uint32_t a0, a1, r, r8; int f8; int f8v; };  // f8: wave-uniform count, f8v: this lane's share of the parallel steps (1/256 bit)
+
+// The bins of the macroblock layer's own syntax (contexts in a0 / a1) on their way to the walk: the lane that owns a context keeps that context's
+// bins of the running cab_mb call as a string (first bin = bit 0; b0: contexts of a0, b1: contexts of a1) and counts them in bits 8.. of its a0 / a1.
+// room: how many bins every string can still take for certain (CAB_STR_BITS less ALL bins collected since the last walk, whatever their
+// context — a wave-uniform bound that needs no look at a lane); where it could run out the strings are walked first and collecting goes on (cab_reserve)
+#define CAB_STR_BITS 64          /* bins a string holds: the two dwords of cab_str_t */
+typedef unsigned long long cab_str_t;
+struct CabStr { cab_str_t b0, b1; int room; const uint32_t *ctab; };
+__device__ __forceinline__ CabStr cab_str_begin(const uint32_t *ctab) { return CabStr{ 0, 0, CAB_STR_BITS, ctab }; }
 
 __device__ __forceinline__ uint32_t cab_model(int lane)
 {
@@ -47,7 +59,7 @@ __device__ __forceinline__ void cab_init(Cab &cb, int lane, bool pslice, int qp)
 {
     namespace T = x264gpu_cabac;
     qp = min(max(qp, 0), 51);
-    uint32_t w[3] = { 0, 0, 0 };
+    uint32_t w[3] = { 0, 0, 0 }, wa1 = 0;
     auto seed = [&](int ctx) {
         int m = 0, n = 0;
         if (ctx < 276) { const T::CabacInitRow row = T::cabac_init_0_275[ctx]; m = pslice ? row.mp : row.mi; n = pslice ? row.np : row.ni; }
@@ -55,10 +67,8 @@ __device__ __forceinline__ void cab_init(Cab &cb, int lane, bool pslice, int qp)
         const int pre = min(max(((m * qp) >> 4) + n, 1), 126);
         return (uint32_t)(pre <= 63 ? (63 - pre) << 1 : ((pre - 64) << 1) | 1);
     };
-    for (int j = 0; j < 4; j++) {
-        const int c = lane * 4 + j;
-        if (c < 105) w[0] |= seed(c) << (8 * j); else if (c < 108) w[0] |= seed(399 + c - 105) << (8 * j);
-    }
+    w[0] = seed(lane);
+    if (lane < 41) wa1 = seed(64 + lane); else if (lane < 44) wa1 = seed(399 + lane - 41);
     {
         const int role = lane >> 4, i = lane & 15;
         const int sig_off[5] = { 105, 120, 134, 149, 152 }, last_off[5] = { 166, 181, 195, 210, 213 }, abs_off[5] = { 227, 237, 247, 257, 266 }, n1[5] = { 15, 14, 15, 3, 14 };
@@ -77,23 +87,63 @@ __device__ __forceinline__ void cab_init(Cab &cb, int lane, bool pslice, int qp)
         }
         if (role == 0 && i < 15) w[2] = seed(402 + i); else if (role == 1 && i < 9) w[2] = seed(417 + i); else if (role == 2 && i < 10) w[2] = seed(426 + i);
     }
-    cb.a = w[0]; cb.r = w[1]; cb.r8 = w[2]; cb.f8 = 0; cb.f8v = 0;
+    cb.a0 = w[0]; cb.a1 = wa1; cb.r = w[1]; cb.r8 = w[2]; cb.f8 = 0; cb.f8v = 0;
 }
 
-// one bin of the header syntax / a coded_block_flag (contexts 0..104, 399..401): wave-uniform, context variables in register a
-__device__ __forceinline__ void cab_bin(Cab &cb, uint32_t model, int lane, int ctx, int bin)
+// every lane walks the strings it has collected for its contexts of a0 and a1 through the chain table (CAB_CHAIN_ENTRIES below: what k = 0..8 bins
+// leave of a context variable and cost), eight bins a lookup, the two registers' lookups in flight together; a lane without bins looks up k = 0, which
+// is the variable itself at no cost.  Afterwards a0 / a1 hold the bare variables again and the strings are empty.
+__device__ __forceinline__ void cab_walk_a(Cab &cb, CabStr &s)
 {
-    ctx = __builtin_amdgcn_readfirstlane(ctx >= 399 ? ctx - 399 + 105 : ctx); bin = __builtin_amdgcn_readfirstlane(bin);
-    const int li = ctx >> 2, sh = (ctx & 3) * 8;
-    const uint32_t w = __builtin_amdgcn_readlane(cb.a, li);
-    const int st = (w >> sh) & 255, sg = st >> 1, mps = st & 1;
-    const uint32_t t = __builtin_amdgcn_readlane(model, sg);
-    const bool lps = (mps ^ bin) != 0;
-    cb.f8 += lps ? (t >> 9) & 0x7ff : t & 0x1ff;
-    const int ns = lps ? (int)(t >> 20) : min(sg + 1, 62);
-    const int nm = lps && sg == 0 ? mps ^ 1 : mps;
-    const uint32_t nw = (w & ~(255u << sh)) | ((uint32_t)((ns << 1) | nm) << sh);
-    cb.a = lane == li ? nw : cb.a;
+    int st0 = (int)(cb.a0 & 255u), n0 = (int)(cb.a0 >> 8), st1 = (int)(cb.a1 & 255u), n1 = (int)(cb.a1 >> 8);
+    while (__ballot((n0 | n1) != 0)) {
+        const int k0 = min(n0, CAB_WALK_BINS), k1 = min(n1, CAB_WALK_BINS);
+        const uint32_t e0 = s.ctab[((((1 << k0) - 1) + ((int)(unsigned)s.b0 & ((1 << k0) - 1))) << 7) + st0];
+        const uint32_t e1 = s.ctab[((((1 << k1) - 1) + ((int)(unsigned)s.b1 & ((1 << k1) - 1))) << 7) + st1];
+        st0 = (int)(e0 & 127u); st1 = (int)(e1 & 127u); cb.f8v += (int)(e0 >> 7) + (int)(e1 >> 7);
+        s.b0 >>= k0; s.b1 >>= k1; n0 -= k0; n1 -= k1;
+    }
+    cb.a0 = (uint32_t)st0; cb.a1 = (uint32_t)st1;
+    s.b0 = 0; s.b1 = 0; s.room = CAB_STR_BITS;
+}
+
+// makes sure that every string can take n more bins (n <= CAB_STR_BITS): what is collected is walked first when it could not.  cab_mb calls this at a
+// few fixed points with the most the code up to the next such point can send (the walk is two table loads in a ballot loop: not something to have
+// behind every deposit); a deposit itself checks nothing, so WHOEVER ADDS A BIN to cab_mb adds it to the bound of the reserve point in front of it.  What
+// runs before the first point of a call: the skip flag and mb_type (14 bins at most), a B_8x8's sub_mb_types (20), a P_8x8's (4), the transform-size flag of an
+// intra macroblock (1); a part call (in.pm 1) sends 4 x 9 + 1 bins at most before its coded_block_flags
+__device__ __forceinline__ void cab_reserve(Cab &cb, CabStr &s, int n) { if (s.room < n) cab_walk_a(cb, s); }
+
+// n bins (first = bit 0 of bits) of the header syntax / coded_block_flags on context ctx (0..104, 399..401), all wave-uniform: appended to the
+// string of the lane that owns the context.  Nothing is evaluated here — a few independent vector operations a call, whatever n is.  The caller has
+// reserved the room (cab_reserve; a cab_mb call starts with CAB_STR_BITS)
+__device__ __forceinline__ void cab_put_str(Cab &cb, CabStr &s, int lane, int ctx, unsigned long long bits, int n)
+{
+    ctx = __builtin_amdgcn_readfirstlane(ctx); n = __builtin_amdgcn_readfirstlane(n);
+    if (n <= 0) return;
+    const bool hi = ctx >= 64;
+    const int li = ctx >= 399 ? ctx - 399 + 41 : ctx & 63;
+    const bool mine = lane == li;
+    const cab_str_t part = (cab_str_t)bits & (n >= CAB_STR_BITS ? ~(cab_str_t)0 : (((cab_str_t)1 << n) - 1));
+    if (hi) { s.b1 |= mine ? part << (cb.a1 >> 8) : 0; cb.a1 += mine ? (uint32_t)n << 8 : 0u; }
+    else { s.b0 |= mine ? part << (cb.a0 >> 8) : 0; cb.a0 += mine ? (uint32_t)n << 8 : 0u; }
+    s.room -= n;
+}
+// one bin, or a run of n equal bins (64 at most)
+__device__ __forceinline__ void cab_put(Cab &cb, CabStr &s, int lane, int ctx, int bin, int n = 1)
+{
+    cab_put_str(cb, s, lane, ctx, __builtin_amdgcn_readfirstlane(bin) ? ~0ull : 0ull, n);
+}
+// ... of any length, for a caller that knows no bound (the primitive x264gpu_cabac_bins_walk): as much as there is room for, a walk, the rest
+__device__ __forceinline__ void cab_put_any(Cab &cb, CabStr &s, int lane, int ctx, int bin, int n)
+{
+    n = __builtin_amdgcn_readfirstlane(n);
+    while (n > 0) {
+        cab_reserve(cb, s, 1);
+        const int k = min(n, s.room);
+        cab_put(cb, s, lane, ctx, bin, k);
+        n -= k;
+    }
 }
 __device__ __forceinline__ void cab_bypass(Cab &cb, int n = 1) { cb.f8 += 256 * n; }
 __device__ __forceinline__ void cab_ue_bypass(Cab &cb, int k, int v)
@@ -405,26 +455,45 @@ __device__ __forceinline__ int cab_luma_cbf_of(int type, int cbp_luma, int t8, u
     return (nnz >> blkidx_of(bx, by)) & 1;
 }
 
-__device__ __forceinline__ void cab_mb_type_intra(Cab &cb, uint32_t model, int lane, const CabIn &in, int c0, int c1, int c2, int c3, int c4, int c5)
+__device__ __forceinline__ void cab_mb_type_intra(Cab &cb, CabStr &cs, int lane, const CabIn &in, int c0, int c1, int c2, int c3, int c4, int c5)
 {
-    if (in.type != X264GPU_MB_I16x16) { cab_bin(cb, model, lane, c0, 0); return; }
-    cab_bin(cb, model, lane, c0, 1);
+    if (in.type != X264GPU_MB_I16x16) { cab_put(cb, cs, lane, c0, 0); return; }
+    cab_put(cb, cs, lane, c0, 1);
     if (in.size) cb.f8 += 7;                      // the terminate bin (not I_PCM) as x264's size macro prices it; it moves no context
-    cab_bin(cb, model, lane, c1, in.cbp_luma != 0);
-    if (!in.cbp_chroma) cab_bin(cb, model, lane, c2, 0);
-    else { cab_bin(cb, model, lane, c2, 1); cab_bin(cb, model, lane, c3, in.cbp_chroma >> 1); }
-    cab_bin(cb, model, lane, c4, in.i16mode >> 1);
-    cab_bin(cb, model, lane, c5, in.i16mode & 1);
+    cab_put(cb, cs, lane, c1, in.cbp_luma != 0);
+    if (!in.cbp_chroma) cab_put(cb, cs, lane, c2, 0);
+    else { cab_put(cb, cs, lane, c2, 1); cab_put(cb, cs, lane, c3, in.cbp_chroma >> 1); }
+    cab_put(cb, cs, lane, c4, in.i16mode >> 1);
+    cab_put(cb, cs, lane, c5, in.i16mode & 1);
 }
 
-__device__ __forceinline__ void cab_mvd(Cab &cb, uint32_t model, int lane, int base, int sum, int val)
+__device__ __forceinline__ void cab_mvd(Cab &cb, CabStr &cs, int lane, int base, int sum, int val)
 {
     const int a = abs(val), inc = (sum > 2) + (sum > 32);
-    if (!a) { cab_bin(cb, model, lane, base + inc, 0); return; }
-    cab_bin(cb, model, lane, base + inc, 1);
-    for (int i = 1; i < min(a, 9); i++) cab_bin(cb, model, lane, base + min(i + 2, 6), 1);
-    if (a < 9) cab_bin(cb, model, lane, base + min(a + 2, 6), 0); else cab_ue_bypass(cb, 3, a - 9);
+    if (!a) { cab_put(cb, cs, lane, base + inc, 0); return; }
+    cab_put(cb, cs, lane, base + inc, 1);
+    // the unary prefix: bin i (1..8) goes to context base + min(i + 2, 6) — one bin each on base + 3, + 4, + 5, the rest as ONE string on base + 6:
+    // its ones, closed by the zero when the prefix ends below nine
+    const int ones = min(a, 9) - 1;
+    if (a < 4) {
+        for (int i = 1; i <= ones; i++) cab_put(cb, cs, lane, base + i + 2, 1);
+        cab_put(cb, cs, lane, base + a + 2, 0);
+    } else {
+        cab_put(cb, cs, lane, base + 3, 1); cab_put(cb, cs, lane, base + 4, 1); cab_put(cb, cs, lane, base + 5, 1);
+        const int n6 = ones - 3 + (a < 9 ? 1 : 0);
+        cab_put_str(cb, cs, lane, base + 6, (1ull << (ones - 3)) - 1ull, n6);
+    }
+    if (a >= 9) cab_ue_bypass(cb, 3, a - 9);
     cab_bypass(cb);
+}
+// ref_idx r: unary, the first bin on 54 + ctx (the neighbours' term), the second on 58, the rest — with the closing zero — one string on 59
+__device__ __forceinline__ void cab_ref_idx(Cab &cb, CabStr &cs, int lane, int ctx, int r)
+{
+    if (r <= 0) { cab_put(cb, cs, lane, 54 + ctx, 0); return; }
+    cab_put(cb, cs, lane, 54 + ctx, 1);
+    if (r == 1) { cab_put(cb, cs, lane, 58, 0); return; }
+    cab_put(cb, cs, lane, 58, 1);
+    cab_put_str(cb, cs, lane, 59, (1ull << (r - 2)) - 1ull, r - 1);
 }
 
 // The macroblock layer.  S: the motion cache (neighbours + search results; partitions are cached into it as they are coded and it is
@@ -442,14 +511,16 @@ __device__ __forceinline__ unsigned long long cab_mb(Cab &cb, uint32_t model, in
     dqp_out = 0;
     const bool lavail = in.left, tavail = in.top;
     const bool intra = in.type < X264GPU_MB_P_L0;
+    // the bins of everything up to the residual blocks are collected per context (cab_put) and walked ONCE, before the levels (or at the end)
+    CabStr cs = cab_str_begin(ctab);
     if (!in.pm) {
     if (in.bslice && !in.size) {
-        cab_bin(cb, model, lane, 24 + (lavail && !cab_is_skip(in.ltype)) + (tavail && !cab_is_skip(in.ttype)), in.type == X264GPU_MB_B_SKIP);
-        if (in.type == X264GPU_MB_B_SKIP) return 0;
+        cab_put(cb, cs, lane, 24 + (lavail && !cab_is_skip(in.ltype)) + (tavail && !cab_is_skip(in.ttype)), in.type == X264GPU_MB_B_SKIP);
+        if (in.type == X264GPU_MB_B_SKIP) { cab_walk_a(cb, cs); return 0; }
     }
     if (in.pslice && !in.bslice && !in.size) {
-        cab_bin(cb, model, lane, 11 + (lavail && in.ltype != X264GPU_MB_P_SKIP) + (tavail && in.ttype != X264GPU_MB_P_SKIP), in.type == X264GPU_MB_P_SKIP);
-        if (in.type == X264GPU_MB_P_SKIP) return 0;
+        cab_put(cb, cs, lane, 11 + (lavail && in.ltype != X264GPU_MB_P_SKIP) + (tavail && in.ttype != X264GPU_MB_P_SKIP), in.type == X264GPU_MB_P_SKIP);
+        if (in.type == X264GPU_MB_P_SKIP) { cab_walk_a(cb, cs); return 0; }
     }
     if (in.bslice) {
         // mb_type: Table 7-14 value -> bins; contexts 27 + {0..2} (neighbours that are neither B_Skip nor B_Direct_16x16), 27 + 3, 27 + 5 - b1, 27 + 5 ...
@@ -464,55 +535,69 @@ __device__ __forceinline__ unsigned long long cab_mb(Cab &cb, uint32_t model, in
             const int pair = u0 == 0 ? (u1 == 0 ? 0 : u1 == 1 ? 2 : 4) : u0 == 1 ? (u1 == 0 ? 3 : u1 == 1 ? 1 : 5) : 6 + u1;
             value = 4 + 2 * pair + (in.part == D_8x16);
         }
-        const int len = c_btype_len[value], bits = c_btype_bits[value];
-        for (int i = 0; i < len; i++) cab_bin(cb, model, lane, i == 0 ? 27 + ctx0 : i == 1 ? 27 + 3 : i == 2 ? 27 + 5 - ((bits >> 1) & 1) : 27 + 5, (bits >> i) & 1);
-        if (intra) cab_mb_type_intra(cb, model, lane, in, 32, 32 + 1, 32 + 2, 32 + 2, 32 + 3, 32 + 3);
+        const int len = c_btype_len[value], bits = c_btype_bits[value];          // (len is 1, 3, 6 or 7: a string of more than one bin has bins 1 and 2)
+        cab_put(cb, cs, lane, 27 + ctx0, bits & 1);
+        if (len > 1) {
+            cab_put(cb, cs, lane, 27 + 3, (bits >> 1) & 1);
+            cab_put(cb, cs, lane, 27 + 5 - ((bits >> 1) & 1), (bits >> 2) & 1);
+            if (len > 3) cab_put_str(cb, cs, lane, 27 + 5, (unsigned long long)(bits >> 3), len - 3);
+        }
+        if (intra) cab_mb_type_intra(cb, cs, lane, in, 32, 32 + 1, 32 + 2, 32 + 2, 32 + 3, 32 + 3);
     } else if (!in.pslice) {
         const int ctx = (lavail && in.ltype != X264GPU_MB_I4x4 && in.ltype != X264GPU_MB_I8x8) + (tavail && in.ttype != X264GPU_MB_I4x4 && in.ttype != X264GPU_MB_I8x8);
-        cab_mb_type_intra(cb, model, lane, in, 3 + ctx, 3 + 3, 3 + 4, 3 + 5, 3 + 6, 3 + 7);
-    } else if (intra) { cab_bin(cb, model, lane, 14, 1); cab_mb_type_intra(cb, model, lane, in, 17, 17 + 1, 17 + 2, 17 + 2, 17 + 3, 17 + 3); }
-    else if (in.part == D_8x8) { cab_bin(cb, model, lane, 14, 0); cab_bin(cb, model, lane, 15, 0); cab_bin(cb, model, lane, 16, 1); }
+        cab_mb_type_intra(cb, cs, lane, in, 3 + ctx, 3 + 3, 3 + 4, 3 + 5, 3 + 6, 3 + 7);
+    } else if (intra) { cab_put(cb, cs, lane, 14, 1); cab_mb_type_intra(cb, cs, lane, in, 17, 17 + 1, 17 + 2, 17 + 2, 17 + 3, 17 + 3); }
+    else if (in.part == D_8x8) { cab_put(cb, cs, lane, 14, 0); cab_put(cb, cs, lane, 15, 0); cab_put(cb, cs, lane, 16, 1); }
     else {
-        cab_bin(cb, model, lane, 14, 0);
-        if (in.part == D_16x16) { cab_bin(cb, model, lane, 15, 0); cab_bin(cb, model, lane, 16, 0); }
-        else { cab_bin(cb, model, lane, 15, 1); cab_bin(cb, model, lane, 17, in.part == D_16x8); }
+        cab_put(cb, cs, lane, 14, 0);
+        if (in.part == D_16x16) { cab_put(cb, cs, lane, 15, 0); cab_put(cb, cs, lane, 16, 0); }
+        else { cab_put(cb, cs, lane, 15, 1); cab_put(cb, cs, lane, 17, in.part == D_16x8); }
     }
     }      // !in.pm
     const int t8ctx = 399 + (lavail && in.lt8) + (tavail && in.tt8);
     if (in.pm == 1) {
         // partition_size_cabac of a P part: its vector difference, the sub-macroblock type of a P_8x8 block
-        if (in.pm_lists & 1) { cab_mvd(cb, model, lane, 40, in.pm_sx, in.pm_dx); cab_mvd(cb, model, lane, 47, in.pm_sy, in.pm_dy); }
-        if (in.pm_lists & 2) { cab_mvd(cb, model, lane, 40, in.pm_sx1, in.pm_dx1); cab_mvd(cb, model, lane, 47, in.pm_sy1, in.pm_dy1); }
-        if (in.part == D_8x8 && !in.bslice) cab_bin(cb, model, lane, 21, 1);
+        if (in.pm_lists & 1) { cab_mvd(cb, cs, lane, 40, in.pm_sx, in.pm_dx); cab_mvd(cb, cs, lane, 47, in.pm_sy, in.pm_dy); }
+        if (in.pm_lists & 2) { cab_mvd(cb, cs, lane, 40, in.pm_sx1, in.pm_dx1); cab_mvd(cb, cs, lane, 47, in.pm_sy1, in.pm_dy1); }
+        if (in.part == D_8x8 && !in.bslice) cab_put(cb, cs, lane, 21, 1);
     } else if (intra) {
         if (in.type != X264GPU_MB_I16x16 && (!in.pm || in.pm == 2 || in.pm == 3)) {
             const bool i8 = in.type == X264GPU_MB_I8x8;
-            if (in.t8mode && !in.pm) cab_bin(cb, model, lane, t8ctx, i8);
-            // every lane its block's mode and predicted mode; the bins go out block by block
+            if (in.t8mode && !in.pm) cab_put(cb, cs, lane, t8ctx, i8);
+            // every lane its block's mode and predicted mode (an Intra_8x8 block's in the lane of its first 4x4 block)
             int mode = 0, pm = 0;
             if (lane < 16) { const uint8_t *cur = i8 ? modes8 : modes4; mode = cur[lane]; pm = i4_pred_mode(nmodes, mbx, sy, lane, cur); }
-            // prev_intra_pred_mode_flag (context 68) and the three rem_intra_pred_mode bins (context 69) are two chains: lane 0 and lane 1 walk
-            // them side by side, block after block (contexts 68 and 69 share a dword of register a with 70 and 71, which nothing uses)
-            const uint32_t w68 = __builtin_amdgcn_readlane(cb.a, 68 >> 2);
-            int stp = lane == 0 ? (int)(w68 & 255) : (int)((w68 >> 8) & 255);
-            for (int b = 0; b < 16; b += i8 ? 4 : 1) {
-                if (in.pm && b != (i8 ? 4 * in.pm_b0 : in.pm_b0)) continue;
-                int m = __builtin_amdgcn_readlane(mode, b);
-                const int p = __builtin_amdgcn_readlane(pm, b);
-                const bool same = m == p;
-                if (m > p) m--;
-                cab_step(stp, cb.f8v, model, lane == 0 || (lane == 1 && !same), lane == 0 ? same : m & 1);
-                if (!same) { cab_step(stp, cb.f8v, model, lane == 1, (m >> 1) & 1); cab_step(stp, cb.f8v, model, lane == 1, m >> 2); }
-            }
-            {
-                const uint32_t s68 = (uint32_t)__builtin_amdgcn_readlane(stp, 0), s69 = (uint32_t)__builtin_amdgcn_readlane(stp, 1);
-                cb.a = lane == (68 >> 2) ? (cb.a & ~0xffffu) | s68 | (s69 << 8) : cb.a;
-            }
+            const bool sends = lane < 16 && (!i8 || !(lane & 3)) && (!in.pm || lane == (i8 ? 4 * in.pm_b0 : in.pm_b0));
+            const bool same = mode == pm;
+            const int rem = mode > pm ? mode - 1 : mode;
+            // context 68's string: the prev_intra_pred_mode_flags in block order — one ballot (an Intra_8x8 macroblock's four sit in every fourth bit)
+            const unsigned long long sm = __ballot(sends), fm = __ballot(sends && same), rm = sm & ~fm;
+            unsigned long long s68 = fm;
+            if (i8) s68 = (fm & 1ull) | ((fm >> 3) & 2ull) | ((fm >> 6) & 4ull) | ((fm >> 9) & 8ull);
+            if (in.pm) s68 = fm ? 1ull : 0ull;
+            // context 69's string: the three rem_intra_pred_mode bins of every block whose flag is 0, in block order — such a block pushes bin j to
+            // lane 3 * rank + j (the others push a zero to lane 63, which no block reaches), one ballot reads the string
+            const int dst = sends && !same ? 3 * cab_mbcnt(rm) : 63;
+            const int p0 = __builtin_amdgcn_ds_permute(dst << 2, sends && !same ? rem & 1 : 0);
+            const int p1 = __builtin_amdgcn_ds_permute((dst == 63 ? 63 : dst + 1) << 2, sends && !same ? (rem >> 1) & 1 : 0);
+            const int p2 = __builtin_amdgcn_ds_permute((dst == 63 ? 63 : dst + 2) << 2, sends && !same ? (rem >> 2) & 1 : 0);
+            const unsigned long long s69 = __ballot((p0 | p1 | p2) != 0);
+            const int n68 = __builtin_popcountll(sm), n69 = 3 * __builtin_popcountll(rm);
+            if (!in.pm) {
+                // (two different lanes: what the pair takes of every string's room is the longer of the two, 48 at most.  A deposit counts its bins off
+                //  `room`, so the pair is deposited against a full bound and the saved one is put back less the longer string)
+                if (cs.room < max(n68, n69)) cab_walk_a(cb, cs);
+                const int room = cs.room;
+                cs.room = CAB_STR_BITS;
+                cab_put_str(cb, cs, lane, 68, s68, n68); cab_put_str(cb, cs, lane, 69, s69, n69);
+                cs.room = room - max(n68, n69);
+            } else { cab_put_str(cb, cs, lane, 68, s68, n68); cab_put_str(cb, cs, lane, 69, s69, n69); }
         }
         if (!in.pm || in.pm == 4) {
+        cab_reserve(cb, cs, 3);          // (intra_chroma_pred_mode: three bins at most)
         const int ctx = (lavail && in.ltype < X264GPU_MB_P_L0 && in.lcmode != 0) + (tavail && in.ttype < X264GPU_MB_P_L0 && in.tcmode != 0);
-        if (!in.cmode) cab_bin(cb, model, lane, 64 + ctx, 0);
-        else { cab_bin(cb, model, lane, 64 + ctx, 1); cab_bin(cb, model, lane, 64 + 3, in.cmode > 1); if (in.cmode > 1) cab_bin(cb, model, lane, 64 + 3, in.cmode > 2); }
+        if (!in.cmode) cab_put(cb, cs, lane, 64 + ctx, 0);
+        else { cab_put(cb, cs, lane, 64 + ctx, 1); cab_put(cb, cs, lane, 64 + 3, in.cmode > 1); if (in.cmode > 1) cab_put(cb, cs, lane, 64 + 3, in.cmode > 2); }
         }
     } else if (in.bslice) {
         // ---- B: sub_mb_type, then every list-0 reference index, every list-1 one, list 0's vector differences, list 1's (7.3.5.1 / 7.3.5.2) ----
@@ -523,10 +608,10 @@ __device__ __forceinline__ unsigned long long cab_mb(Cab &cb, uint32_t model, in
             if (part == D_8x8)
                 for (int kp = 0; kp < 4; kp++) {
                     const int u = use_of(kp);
-                    if (u == 3) { cab_bin(cb, model, lane, 36, 0); continue; }
-                    cab_bin(cb, model, lane, 36, 1);
-                    if (u == 2) { cab_bin(cb, model, lane, 37, 1); cab_bin(cb, model, lane, 38, 0); cab_bin(cb, model, lane, 39, 0); cab_bin(cb, model, lane, 39, 0); }
-                    else { cab_bin(cb, model, lane, 37, 0); cab_bin(cb, model, lane, 39, u == 1); }
+                    if (u == 3) { cab_put(cb, cs, lane, 36, 0); continue; }
+                    cab_put(cb, cs, lane, 36, 1);
+                    if (u == 2) { cab_put(cb, cs, lane, 37, 1); cab_put(cb, cs, lane, 38, 0); cab_put(cb, cs, lane, 39, 0, 2); }
+                    else { cab_put(cb, cs, lane, 37, 0); cab_put(cb, cs, lane, 39, u == 1); }
                 }
             const int sc0 = S.cref, sc1 = S.cmvx, sc2 = S.cmvy, sc3 = S.cdir;
             for (int l = 0; l < 2; l++) {
@@ -540,8 +625,7 @@ __device__ __forceinline__ unsigned long long cab_mb(Cab &cb, uint32_t model, in
                     const int r = rl(l ? in.b_r1 : in.b_r0, b8 * 16);
                     if (sends) {
                         int ctx = (rl(S.cref, g0 - 1) > 0 && !rl(S.cdir, g0 - 1)) + 2 * (rl(S.cref, g0 - 4) > 0 && !rl(S.cdir, g0 - 4));
-                        for (int q = r; q > 0; q--) { cab_bin(cb, model, lane, 54 + ctx, 1); ctx = (ctx >> 2) + 4; }
-                        cab_bin(cb, model, lane, 54 + ctx, 0);
+                        cab_reserve(cb, cs, 16); cab_ref_idx(cb, cs, lane, ctx, r);          // (r + 1 bins, r <= 15)
                     }
                     const bool mine = lane == g0 || (w8 == 2 && lane == g0 + 1) || (h8 == 2 && lane == g0 + 4) || (w8 == 2 && h8 == 2 && lane == g0 + 5);
                     S.cref = mine ? (sends ? r : u == 3 ? r : -1) : S.cref;
@@ -562,11 +646,12 @@ __device__ __forceinline__ unsigned long long cab_mb(Cab &cb, uint32_t model, in
                     if (sends) {
                         int px, py;
                         mb_predict_mv(S, part, x8, y8, w8, r, px, py, go);
+                        cab_reserve(cb, cs, 18);          // (a difference sends nine context-coded bins at most: 1 + 3 + 5)
                         for (int comp = 0; comp < 2; comp++) {
                             const int la = x8 > 0 ? (int)((am >> (8 * ((y8 * 2 + x8 - 1) * 2 + comp))) & 255) : lavail ? (int)((nl >> (8 * ((y8 * 2 + 1) * 2 + comp))) & 255) : 0;
                             const int ta = y8 > 0 ? (int)((am >> (8 * (((y8 - 1) * 2 + x8) * 2 + comp))) & 255) : tavail ? (int)((nt >> (8 * ((2 + x8) * 2 + comp))) & 255) : 0;
                             const int d = comp ? vy - py : vx - px;
-                            cab_mvd(cb, model, lane, comp ? 47 : 40, la + ta, d);
+                            cab_mvd(cb, cs, lane, comp ? 47 : 40, la + ta, d);
                             const unsigned long long capped = (unsigned long long)min(abs(d), 66);
                             for (int yy = y8; yy < y8 + h8; yy++) for (int xx = x8; xx < x8 + w8; xx++) am |= capped << (8 * ((yy * 2 + xx) * 2 + comp));
                         }
@@ -582,7 +667,7 @@ __device__ __forceinline__ unsigned long long cab_mb(Cab &cb, uint32_t model, in
     } else {
         const int part = in.part, np = part == D_16x16 ? 1 : part == D_8x8 ? 4 : 2;
         const int w8 = part == D_16x16 || part == D_16x8 ? 2 : 1, h8 = part == D_16x16 || part == D_8x16 ? 2 : 1;
-        if (part == D_8x8) for (int kp = 0; kp < 4; kp++) cab_bin(cb, model, lane, 21, 1);          // sub_mb_type P_L0_8x8
+        if (part == D_8x8) cab_put(cb, cs, lane, 21, 1, 4);                                      // sub_mb_type P_L0_8x8, four times
         const int sc0 = S.cref, sc1 = S.cmvx, sc2 = S.cmvy;
         if (lane == 5 || lane == 6 || lane == 9 || lane == 10) S.cref = -2;
         if (in.nref > 1)
@@ -591,9 +676,8 @@ __device__ __forceinline__ unsigned long long cab_mb(Cab &cb, uint32_t model, in
                 const int slot = part == D_16x16 ? ME_16 : part == D_16x8 ? ME_16x8 + kp : part == D_8x16 ? ME_8x16 + kp : ME_8 + kp;
                 const int r = rl(S.ref, slot), g0 = (y8 + 1) * 4 + x8 + 1;
                 // ref_idx: neighbours with a reference above 0 (skipped and intra macroblocks have none)
-                int ctx = (rl(S.cref, g0 - 1) > 0) + 2 * (rl(S.cref, g0 - 4) > 0);
-                for (int q = r; q > 0; q--) { cab_bin(cb, model, lane, 54 + ctx, 1); ctx = (ctx >> 2) + 4; }
-                cab_bin(cb, model, lane, 54 + ctx, 0);
+                const int ctx = (rl(S.cref, g0 - 1) > 0) + 2 * (rl(S.cref, g0 - 4) > 0);
+                cab_reserve(cb, cs, 16); cab_ref_idx(cb, cs, lane, ctx, r);          // (r + 1 bins, r <= 15)
                 const bool mine = lane == g0 || (w8 == 2 && lane == g0 + 1) || (h8 == 2 && lane == g0 + 4) || (w8 == 2 && h8 == 2 && lane == g0 + 5);
                 S.cref = mine ? r : S.cref;
             }
@@ -604,11 +688,12 @@ __device__ __forceinline__ unsigned long long cab_mb(Cab &cb, uint32_t model, in
             const int r = rl(S.ref, slot), vx = rl(S.mvx, slot), vy = rl(S.mvy, slot), g0 = (y8 + 1) * 4 + x8 + 1;
             int px, py;
             mb_predict_mv(S, part, x8, y8, w8, r, px, py);
+            cab_reserve(cb, cs, 18);          // (the part's two differences, nine context-coded bins each at most)
             for (int comp = 0; comp < 2; comp++) {
                 const int la = x8 > 0 ? (int)((amvd >> (8 * ((y8 * 2 + x8 - 1) * 2 + comp))) & 255) : lavail ? (int)((in.lamvd >> (8 * ((y8 * 2 + 1) * 2 + comp))) & 255) : 0;
                 const int ta = y8 > 0 ? (int)((amvd >> (8 * (((y8 - 1) * 2 + x8) * 2 + comp))) & 255) : tavail ? (int)((in.tamvd >> (8 * ((2 + x8) * 2 + comp))) & 255) : 0;
                 const int d = comp ? vy - py : vx - px;
-                cab_mvd(cb, model, lane, comp ? 47 : 40, la + ta, d);
+                cab_mvd(cb, cs, lane, comp ? 47 : 40, la + ta, d);
                 const unsigned long long capped = (unsigned long long)min(abs(d), 66);
                 for (int yy = y8; yy < y8 + h8; yy++) for (int xx = x8; xx < x8 + w8; xx++) amvd |= capped << (8 * ((yy * 2 + xx) * 2 + comp));
             }
@@ -617,31 +702,35 @@ __device__ __forceinline__ unsigned long long cab_mb(Cab &cb, uint32_t model, in
         }
         S.cref = sc0; S.cmvx = sc1; S.cmvy = sc2;
     }
+    cab_reserve(cb, cs, 7);          // (coded_block_pattern: 4 + 2, the transform-size flag of an inter macroblock)
     if (in.pm ? in.pm == 3 : in.type != X264GPU_MB_I16x16)
         for (int b8 = 0; b8 < 4; b8++) {
             const int x = b8 & 1, y = b8 >> 1;
             const int a = x ? !((in.cbp_luma >> (b8 - 1)) & 1) : lavail ? !((in.lcbp_luma >> (b8 + 1)) & 1) : 0;
             const int b = y ? !((in.cbp_luma >> (b8 - 2)) & 1) : tavail ? !((in.tcbp_luma >> (b8 + 2)) & 1) : 0;
-            cab_bin(cb, model, lane, 73 + a + 2 * b, (in.cbp_luma >> b8) & 1);
+            cab_put(cb, cs, lane, 73 + a + 2 * b, (in.cbp_luma >> b8) & 1);
         }
     if (in.pm ? in.pm == 4 : in.type != X264GPU_MB_I16x16) {
-        cab_bin(cb, model, lane, 77 + (lavail && in.lcbp_chroma) + 2 * (tavail && in.tcbp_chroma), in.cbp_chroma != 0);
-        if (in.cbp_chroma) cab_bin(cb, model, lane, 77 + 4 + (lavail && in.lcbp_chroma == 2) + 2 * (tavail && in.tcbp_chroma == 2), in.cbp_chroma == 2);
+        cab_put(cb, cs, lane, 77 + (lavail && in.lcbp_chroma) + 2 * (tavail && in.tcbp_chroma), in.cbp_chroma != 0);
+        if (in.cbp_chroma) cab_put(cb, cs, lane, 77 + 4 + (lavail && in.lcbp_chroma == 2) + 2 * (tavail && in.tcbp_chroma == 2), in.cbp_chroma == 2);
     }
-    if (!in.pm && !intra && in.t8mode && in.cbp_luma) cab_bin(cb, model, lane, t8ctx, in.t8);
+    if (!in.pm && !intra && in.t8mode && in.cbp_luma) cab_put(cb, cs, lane, t8ctx, in.t8);
     if (in.pm || in.cbp_luma || in.cbp_chroma || in.type == X264GPU_MB_I16x16) {
         const bool i16 = !in.pm && in.type == X264GPU_MB_I16x16;
         int dqp = in.qp - in.last_qp;
         // an I16x16 with nothing coded, DC included, never raises the quantiser (x264's qp_delta writers): it is sent as "no change"
         if (i16 && !in.cbp_luma && !in.cbp_chroma && !((in.nnz >> 24) & 1) && dqp > 0) dqp = 0;
         if (!in.pm) {
-        int ctx = in.last_dqp != 0;
+        const int ctx = in.last_dqp != 0;
+        if (dqp < -26) dqp += 52; else if (dqp > 25) dqp -= 52;
+        const int val = dqp > 0 ? 2 * dqp - 1 : -2 * dqp;          // (52 at most)
+        cab_reserve(cb, cs, val + 1);          // (val ones and the closing zero)
         if (dqp) {
-            if (dqp < -26) dqp += 52; else if (dqp > 25) dqp -= 52;
-            int val = dqp > 0 ? 2 * dqp - 1 : -2 * dqp;
-            do { cab_bin(cb, model, lane, 60 + ctx, 1); ctx = 2 + (ctx >> 1); } while (--val);
-        }
-        cab_bin(cb, model, lane, 60 + ctx, 0);
+            // unary: the first bin on 60 + ctx, the second on 62, the rest — with the closing zero — one string on 63
+            cab_put(cb, cs, lane, 60 + ctx, 1);
+            if (val == 1) cab_put(cb, cs, lane, 62, 0);
+            else { cab_put(cb, cs, lane, 62, 1); cab_put_str(cb, cs, lane, 63, (1ull << (val - 2)) - 1ull, val - 1); }
+        } else cab_put(cb, cs, lane, 60 + ctx, 0);
         dqp_out = dqp;
         }
         pf.mark2(17);
@@ -679,11 +768,12 @@ __device__ __forceinline__ unsigned long long cab_mb(Cab &cb, uint32_t model, in
             constexpr int CAT = decltype(cat_tag)::value;
             static_assert(CAT == 0 || CAT == 3, "the DC categories");
             (void)shift;
+            cab_reserve(cb, cs, nblk);          // (a flag a block)
             for (int b = 0; b < nblk; b++) {
                 if (!coded(b)) continue;
                 const int coef = coef_of(b);
                 const bool nz = __ballot(coef != 0) != 0;
-                cab_bin(cb, model, lane, 85 + CAT * 4 + inc_of(b), nz);
+                cab_put(cb, cs, lane, 85 + CAT * 4 + inc_of(b), nz);
                 if (nz) { if (CAT == 0) W.ldc = true; else W.nzdc |= 1u << b; }          // (the block itself: cab_levels_all)
             }
         };
@@ -697,25 +787,21 @@ __device__ __forceinline__ unsigned long long cab_mb(Cab &cb, uint32_t model, in
             const bool mine_blk = lane < nblk && ((codedmask >> b_lane) & 1);
             const int inc = inc_of(b_lane);
             const unsigned long long nzm = (unsigned long long)(nzbits & codedmask);
-            unsigned long long seq = 0;
-#pragma unroll
-            for (int j = 0; j < 4; j++) { const unsigned long long m = __ballot(mine_blk && inc == j); seq = lane == j ? m : seq; }
-            const int cbase = 85 + CAT * 4;
-            int stc = 0;
-#pragma unroll
-            for (int j = 0; j < 4; j++) { const int c = cbase + j; const uint32_t w = __builtin_amdgcn_readlane(cb.a, c >> 2); stc = lane == j ? (int)((w >> ((c & 3) * 8)) & 255) : stc; }
-            while (__ballot(seq != 0)) {
-                const bool have = seq != 0;
-                const int b = have ? __builtin_ctzll(seq) : 0;
-                cab_step(stc, cb.f8v, model, have, (int)((nzm >> b) & 1));
-                seq &= seq - 1;
-            }
+            cab_reserve(cb, cs, nblk);          // (a flag a block)
+            // context increment j's string: the flags of the blocks that use it, in block order — every such block pushes its flag to the lane of
+            // its rank among them (the others push a zero to lane 63; a block's rank is 15 at most), a ballot reads the string off.  The four
+            // pushes go out together
+            unsigned long long mem[4];
+            int pushed[4];
 #pragma unroll
             for (int j = 0; j < 4; j++) {
-                const int c = cbase + j, li = c >> 2, sh = (c & 3) * 8;
-                const uint32_t v = (uint32_t)__builtin_amdgcn_readlane(stc, j);
-                cb.a = lane == li ? (cb.a & ~(255u << sh)) | (v << sh) : cb.a;
+                const bool m = mine_blk && inc == j;
+                mem[j] = __ballot(m);
+                pushed[j] = __builtin_amdgcn_ds_permute((m ? cab_mbcnt(mem[j]) : 63) << 2, m ? (int)((nzm >> b_lane) & 1) : 0);
             }
+#pragma unroll
+            for (int j = 0; j < 4; j++)
+                if (mem[j]) cab_put_str(cb, cs, lane, 85 + CAT * 4 + j, __ballot(pushed[j] != 0), __builtin_popcountll(mem[j]));
             (void)coef_of; (void)shift;          // (the blocks themselves — significance maps and levels — are coded by cab_levels_all at the end)
             if (CAT == 4) W.nzac |= (unsigned)nzm; else { W.cat0 = CAT; W.nz0 |= (unsigned)nzm; }
         };
@@ -750,8 +836,9 @@ __device__ __forceinline__ unsigned long long cab_mb(Cab &cb, uint32_t model, in
             if (in.cbp_chroma == 2)
                 blocks_many(std::integral_constant<int, 4>{}, 16, 8, 0xffu, (in.nnz >> 16) & 0xffu, [&](int k) { return lane < 15 ? (int)lvs[X264GPU_LV_CHROMA_AC + k * 16 + 1 + lane] : 0; }, [&](int k) { return ac_inc((k >> 2) & 1, k & 3); });
         }
+        cab_walk_a(cb, cs);          // (header and coded_block_flags: the one walk of this call, counted with the flags)
         flush_levels();
-    }
+    } else cab_walk_a(cb, cs);
     return amvd;
 }
 

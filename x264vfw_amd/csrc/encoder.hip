@@ -62,7 +62,7 @@ struct x264gpu_encoder {
     unsigned long long *dbg = nullptr;   // diagnostics buffer set by x264gpu_encoder_set_debug
     uint8_t *tc = nullptr;               // RD: total_coeff of every block of the picture being coded
     uint8_t *amvd = nullptr;             // CABAC RD: |mvd| of every 8x8 block of the picture being coded
-    uint32_t *cab_out = nullptr;         // ... and the context variables every slice's wavefront ended with: [stream][slice][3][64] (tests; layout: cabac_rd.hip.h cab_locate)
+    uint32_t *cab_out = nullptr;         // ... and the context variables every slice's wavefront ended with: [stream][slice][4][64] (tests; layout: cabac_layout.hip.h cab_locate)
     int *perm = nullptr; unsigned *wtime = nullptr; bool wt_valid[4] = { false, false, false, false };      // load balance: EncK.perm / wtime, one history per picture kind (I, P, B reference, B)
     int *sl_stat = nullptr, *sl_rerun = nullptr;     // --slices N: per (stream, slice) intra statistics of the speculative slice passes (EncK.sl_stat)
     unsigned long long *prof = nullptr;  // MB_PROF builds: phase counters of the last macroblock-loop launch
@@ -191,7 +191,7 @@ static int encoder_create_impl(x264gpu_encoder **out, const x264gpu_config *cfg,
     for (int r = 1; r < (cfg->dpb > 0 ? 8 : cfg->refs); r++) alloc((void **)&e->mvr[r], S * k.nmb * 2 * sizeof(int16_t), 0);
     alloc((void **)&e->wf_progress, S * 2 * WFG_ROWS * sizeof(int), 0);
     if (cfg->rd && !cfg->cabac) alloc((void **)&e->tc, S * k.nmb * 24, 0);
-    if (cfg->rd && cfg->cabac) { alloc((void **)&e->amvd, S * k.nmb * (cfg->dpb > 0 ? 16 : 8), 0); alloc((void **)&e->cab_out, S * (cfg->slices > 1 ? cfg->slices : 1) * 192 * sizeof(uint32_t), 0); }
+    if (cfg->rd && cfg->cabac) { alloc((void **)&e->amvd, S * k.nmb * (cfg->dpb > 0 ? 16 : 8), 0); alloc((void **)&e->cab_out, S * (cfg->slices > 1 ? cfg->slices : 1) * 256 * sizeof(uint32_t), 0); }
     if (S >= 512 && !getenv("X264GPU_NO_BALANCE")) { alloc((void **)&e->perm, S * sizeof(int), 0); alloc((void **)&e->wtime, 4 * S * sizeof(unsigned), 0); }
     if (cfg->slices_plain && cfg->slices > 1) { alloc((void **)&e->sl_stat, 3 * S * cfg->slices * 4 * sizeof(int), 0);      /* one history per picture kind: P, B reference, B */ alloc((void **)&e->sl_rerun, S * cfg->slices * sizeof(int), 0); }
 #ifdef MB_PROF
@@ -360,9 +360,9 @@ int x264gpu_encoder_cabac_states(x264gpu_encoder *e, int stream, int slice, uint
 {
     ARG_TRY(e && out460 && stream >= 0 && stream < e->cfg.streams && slice >= 0 && slice < (e->cfg.slices > 1 ? e->cfg.slices : 1));
     if (!e->cab_out) return X264GPU_EINVAL;
-    uint32_t w[192];
+    uint32_t w[256];
     HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(w, e->cab_out + ((size_t)stream * (e->cfg.slices > 1 ? e->cfg.slices : 1) + slice) * 192, sizeof(w), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(w, e->cab_out + ((size_t)stream * (e->cfg.slices > 1 ? e->cfg.slices : 1) + slice) * 256, sizeof(w), hipMemcpyDeviceToHost));
     for (int c = 0; c < 460; c++) {
         int reg, lane, sh;
         out460[c] = cab_locate(c, reg, lane, sh) ? (uint8_t)(w[reg * 64 + lane] >> sh) : 0;

@@ -1638,8 +1638,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MB_WAVES_PER
 #endif
     // x264_slice_write: the slice's quantiser (header, context initialisation, start of the mb_qp_delta chain) is its FIRST macroblock's
     int last_qp = uni((int)k.mbqp[(size_t)s * k.nmb + mb_first]);
-    // CABAC RD: the slice's context variables (two registers, see cabac_rd.hip.h), the probability model, the previous macroblock's mb_qp_delta
-    Cab cab = { 0, 0, 0, 0, 0 };
+    // CABAC RD: the slice's context variables (four registers, see cabac_layout.hip.h), the probability model, the previous macroblock's mb_qp_delta
+    Cab cab = { 0, 0, 0, 0, 0, 0 };
     uint32_t cab_modelv = 0;
     int last_dqp = 0;
     if constexpr (RD >= 2) { cab_init(cab, lane, pslice, last_qp); cab_modelv = cab_model(lane); }
@@ -3247,7 +3247,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MB_WAVES_PER
     if (PS && k.sl_stat && lane == 0) { int *st = k.sl_stat + ((size_t)s * nsl + blockIdx.y) * 4; st[0] = intra_count - L.slw[2]; st[1] = L.slw[0]; st[2] = L.slw[1]; }
     if (k.wtime && lane == 0 && blockIdx.y == 0) k.wtime[s] = (unsigned)min((unsigned long long)(__builtin_readcyclecounter() - wt0) >> 6, 0xffffffffull);
     if constexpr (RD >= 2) {
-        if (k.cab_out) { uint32_t *o = k.cab_out + ((size_t)s * (k.slices > 1 ? k.slices : 1) + blockIdx.y) * 192; o[lane] = cab.a; o[64 + lane] = cab.r; o[128 + lane] = cab.r8; }
+        if (k.cab_out) { uint32_t *o = k.cab_out + ((size_t)s * (k.slices > 1 ? k.slices : 1) + blockIdx.y) * 256; o[lane] = cab.a0; o[64 + lane] = cab.r; o[128 + lane] = cab.r8; o[192 + lane] = cab.a1; }
     }
 #ifdef MB_PROF
     if (lane == 0 && k.prof) for (int i = 0; i < 32; i++) k.prof[(size_t)s * 32 + i] = pf.acc[i];

@@ -489,7 +489,7 @@ __global__ void k_cab_level_walk(const int16_t *lv, const int *what, const uint3
     const int i = blockIdx.x, lane = threadIdx.x;
     for (int j = lane; j < X264GPU_MB_LEVELS; j += 64) l[j] = lv[(size_t)i * X264GPU_MB_LEVELS + j];
     __syncthreads();
-    Cab cb; cb.a = 0; cb.r = r_in[i * 64 + lane]; cb.r8 = r8_in[i * 64 + lane]; cb.f8 = 0; cb.f8v = 0;
+    Cab cb; cb.a0 = 0; cb.a1 = 0; cb.r = r_in[i * 64 + lane]; cb.r8 = r8_in[i * 64 + lane]; cb.f8 = 0; cb.f8v = 0;
     const uint32_t model = cab_model(lane);
     CabLv W = { what[i * 5], (unsigned)what[i * 5 + 1], (unsigned)what[i * 5 + 2], (unsigned)what[i * 5 + 3], what[i * 5 + 4] != 0 };
     Prof pf;
@@ -507,6 +507,47 @@ int x264gpu_cabac_level_walk(const int16_t *d_levels, const int32_t *d_what, int
     const uint32_t *ctab = nullptr;
     { const int rc = x264gpu::cabac_chain_table(&ctab); if (rc != X264GPU_OK) return rc; }
     hipLaunchKernelGGL(x264gpu::k_cab_level_walk, dim3(n), dim3(64), 0, (hipStream_t)stream, d_levels, d_what, d_r, d_r8, d_r_out, d_r8_out, d_bits, ctab);
+    HIP_TRY(hipGetLastError());
+    return X264GPU_OK;
+}
+}  // extern "C"
+
+/* the bin collector and walk of the macroblock layer's own syntax (cabac_rd.hip.h cab_put / cab_walk_a) as a primitive: n cases; case i's bins are the
+ * triples d_first[i] .. d_first[i + 1] - 1 of d_triples (context 0..104 or 399..401, bin, repeat count, in coding order; a triple with another context
+ * or no repeats is passed over), its context variables d_states[460 i ..] in, d_states_out[460 i ..] out, the bits (1/256) to d_bits[i] */
+namespace x264gpu {
+__global__ void k_cab_bins_walk(const int32_t *triples, const int32_t *first, const uint8_t *st_in, uint8_t *st_out, int *bits, const uint32_t *ctab)
+{
+    const int i = blockIdx.x, lane = threadIdx.x;
+    const uint8_t *si = st_in + (size_t)i * 460;
+    uint8_t *so = st_out + (size_t)i * 460;
+    const int c0 = lane, c1 = lane < 41 ? 64 + lane : lane < 44 ? 399 + lane - 41 : -1;          // (cab_locate: the contexts this lane owns in a0 / a1)
+    Cab cb; cb.a0 = si[c0] & 127u; cb.a1 = c1 >= 0 ? si[c1] & 127u : 0u;          // (a context variable has seven bits: the chain table's index)
+    cb.r = 0; cb.r8 = 0; cb.f8 = 0; cb.f8v = 0;
+    CabStr cs = cab_str_begin(ctab);
+    const int t0 = __builtin_amdgcn_readfirstlane(first[i]), t1 = __builtin_amdgcn_readfirstlane(first[i + 1]);
+    for (int t = t0; t < t1; t++) {
+        const int ctx = __builtin_amdgcn_readfirstlane(triples[3 * t]), bin = __builtin_amdgcn_readfirstlane(triples[3 * t + 1]) & 1;
+        const int rep = __builtin_amdgcn_readfirstlane(triples[3 * t + 2]);
+        if (!((ctx >= 0 && ctx < 105) || (ctx >= 399 && ctx <= 401))) continue;
+        cab_put_any(cb, cs, lane, ctx, bin, rep);
+    }
+    cab_walk_a(cb, cs);
+    for (int c = lane; c < 460; c += 64) if (c >= 105 && !(c >= 399 && c <= 401)) so[c] = si[c];
+    so[c0] = (uint8_t)cb.a0;
+    if (c1 >= 0) so[c1] = (uint8_t)cb.a1;
+    const int total = cab_total(cb);
+    if (lane == 0) bits[i] = total;
+}
+}  // namespace x264gpu
+extern "C" {
+int x264gpu_cabac_bins_walk(const int32_t *d_triples, const int32_t *d_first, int n, const uint8_t *d_states, uint8_t *d_states_out, int32_t *d_bits, void *stream)
+{
+    ARG_TRY(d_triples && d_first && d_states && d_states_out && d_bits && n >= 0);
+    if (!n) return X264GPU_OK;
+    const uint32_t *ctab = nullptr;
+    { const int rc = x264gpu::cabac_chain_table(&ctab); if (rc != X264GPU_OK) return rc; }
+    hipLaunchKernelGGL(x264gpu::k_cab_bins_walk, dim3(n), dim3(64), 0, (hipStream_t)stream, d_triples, d_first, d_states, d_states_out, d_bits, ctab);
     HIP_TRY(hipGetLastError());
     return X264GPU_OK;
 }
