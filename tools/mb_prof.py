@@ -2,6 +2,8 @@
 
     make -C x264vfw_amd/csrc clean && make -C x264vfw_amd/csrc -j8 EXTRA=-DMB_PROF && python tools/mb_prof.py [streams] [frames]
 
+EXTRA="-DMB_PROF -DMB_PROF_INTRA" adds a line that splits the intra analysis into its 16x16, 8x8 and 4x4 parts and counts the 4x4 blocks analysed.
+
 Prints, per picture, the average cycles per macroblock of every phase (s_memtime deltas summed by lane 0 of each stream's wavefront).
 The timers perturb scheduling a little; use the table for proportions, bench.py for absolute time."""
 import ctypes as C
@@ -64,12 +66,17 @@ def main():
         tot = a[:13].sum() + (a[15] if a[15] > 100 else 0)          # -DMB_PROF_RD builds: slot 15 = cycles of the CABAC pricing (RD sessions)
         print("%-4s %10.0f " % ("IIPRb"[pt] + str(disp), tot) + " ".join("%9.0f" % v for v in a[:13]) + " %9.2f %9.2f %9.2f" % (a[13], a[14], a[15]) + "   %.1f ms" % e0.elapsed_time(e1))
         if a[16] > 0:         # -DMB_PROF_RD: inside the CABAC pricing (cabac_rd.hip.h), per macroblock
-            print("     cab_mb calls %.2f  header %.0f  cbf+sigmaps %.0f  levels: prep %.0f walk %.0f rest %.0f cycles;  walk steps %.1f  non-zero coefficients %.1f" % (a[16], a[17], a[18], a[22], a[23], a[19], a[20], a[21]))
+            print("     cab_mb calls %.2f  header %.0f  cbf+sigmaps %.0f  levels %.0f cycles;  walk steps %.1f  non-zero coefficients %.1f" % (a[16], a[17], a[18], a[19], a[20], a[21]))          # (slots 22 / 23: the intra split below)
         if a[27] > 0:
             print("     around the pricing: candidate's distortion terms + header inputs %.0f  cost bookkeeping %.0f cycles" % (a[27], a[28]))
         if a[24] > 0:
             print("     inter encode: prediction (b_predict) %.0f  luma transform / quantiser / reconstruction %.0f  chroma %.0f cycles" % (a[24], a[25], a[26]))
-        if a[29] + a[31] > 0:         # B slices: the prediction memo (k_mb.hip.h PMEMO)
+        if out[:, 30].any():          # -DMB_PROF_INTRA: the intra analysis split (k_mb.hip.h PFI); slot 30 = three counts of 21 bits
+            cnt = [float(((out[:, 30] >> np.uint64(sh)) & np.uint64((1 << 21) - 1)).sum()) / (S * n) for sh in (0, 21, 42)]
+            print("     intra analysis: 16x16 %.0f  8x8 %.0f  4x4 %.0f cycles (%.1f%% of the macroblock);  4x4 blocks analysed %.2f a macroblock, %.2f where the loop is entered;"
+                  "  macroblocks entering it %.1f%%, running all sixteen %.1f%%"
+                  % (a[9] - a[22] - a[23], a[22], a[23], 100 * a[23] / tot, cnt[0], cnt[0] / max(cnt[2], 1e-9), 100 * cnt[2], 100 * cnt[1]))
+        if a[29] + a[31] > 0:        # B slices: the prediction memo (k_mb.hip.h PMEMO)
             print("     inter encode predictions per macroblock: %.2f served from the memo, %.2f fetched" % (a[29], a[31]))
         mx = out[:, :13].sum(axis=1).astype(np.float64)
         print("     slowest/mean stream cycles: %.3f   share: " % (mx.max() / mx.mean()) + " ".join("%8.1f%%" % (100 * v / tot) for v in a[:13]))

@@ -106,6 +106,48 @@ __device__ __forceinline__ bool pred4_mode_ok(int mode, int avail)
 // Build U[] for the 4x4 block whose top-left sample is `blk` inside an LDS tile of stride ts whose row -1 /
 // column -1 hold the neighbours.  All 64 lanes call.  Lane k (0..14) fetches e[k-1]; the 2- and 3-tap
 // filters come from DPP row shifts of that register (no LDS round trip); lane 15 computes the DC value.
+// pred4_build_row is that for the 16-lane DPP row this lane is in: r = lane within the row, `on` = the row builds at all; U, blk and avail are the row's.
+__device__ __forceinline__ void pred4_build_row(uint8_t *U, const uint8_t *blk, int ts, int avail, int r, bool on)
+{
+    int v = 0;
+    if (on && r < 15) {
+        const int k = r - 1;
+        const int kk = k < 0 ? 0 : k > 12 ? 12 : k;
+        if (kk <= 3) v = blk[(3 - kk) * ts - 1];                       // left column, bottom -> top
+        else if (kk == 4) v = blk[-ts - 1];                           // corner
+        else {
+            int x = kk - 5;
+            if (x > 3 && !(avail & AVAIL_TOPRIGHT)) x = 3;            // replicate top[3] (8.3.1.2)
+            v = blk[-ts + x];
+        }
+    } else if (on) {
+        const uint32_t t = *(const uint32_t *)(blk - ts);
+        const int st = (int)__builtin_amdgcn_sad_u8(t, 0u, 0u);
+        const int sl = blk[-1] + blk[ts - 1] + blk[2 * ts - 1] + blk[3 * ts - 1];
+        const bool l = avail & AVAIL_LEFT, tp = avail & AVAIL_TOP;
+        v = l && tp ? (st + sl + 4) >> 3 : l ? (sl + 2) >> 2 : tp ? (st + 2) >> 2 : 128;
+    }
+    const int lo = dpp<0x111>(v);     // row_shr:1  -> value of lane-1  (e[k-1])
+    const int hi = dpp<0x101>(v);     // row_shl:1  -> value of lane+1  (e[k+1])
+    if (on) {
+        if (r < 15) U[r] = (uint8_t)v;
+        else U[U_DC] = (uint8_t)v;
+        if (r >= 1 && r <= 13) {
+            U[U_F2 + r - 1] = (uint8_t)((v + hi + 1) >> 1);
+            U[U_F3 + r - 1] = (uint8_t)((lo + 2 * v + hi + 2) >> 2);
+        }
+    }
+    lds_order();
+}
+// Two blocks in one pass: the first in DPP row 0 (lanes 0..15) into U0, the second in row 1 (lanes 16..31) into U1.  The two are built side by side at the
+// latency of one: same loads, same shifts, same stores, on twice the lanes.
+__device__ __forceinline__ void pred4_build_u2(uint8_t *U0, uint8_t *U1, const uint8_t *blk0, const uint8_t *blk1, int ts, int avail0, int avail1, int lane)
+{
+    const bool b = lane & 16;
+    pred4_build_row(b ? U1 : U0, b ? blk1 : blk0, ts, b ? avail1 : avail0, lane & 15, lane < 32);
+}
+// One block, lanes 0..15 (kept as its own body, not a call of the row form: the RD-refinement instantiations, which use only this one, then compile to
+// what they were — their register allocation is on the edge, see mb_analyse_intra's ROUNDS)
 __device__ __forceinline__ void pred4_build_u(uint8_t *U, const uint8_t *blk, int ts, int avail, int lane)
 {
     int v = 0;

@@ -89,6 +89,7 @@ struct Prof {
     __device__ __forceinline__ void mark(int i) { const unsigned long long n = __builtin_readcyclecounter(); acc[i] += n - t; t = n; }
     __device__ __forceinline__ void count(int i) { acc[i]++; }
     __device__ __forceinline__ void count(int i, int n) { acc[i] += (unsigned long long)n; }
+    __device__ __forceinline__ void count(int i, unsigned long long n) { acc[i] += n; }
     // a second, nested clock (the phases' clock t keeps running): begin2 .. mark2
     __device__ __forceinline__ void begin2() { t2 = __builtin_readcyclecounter(); }
     __device__ __forceinline__ void mark2(int i) { const unsigned long long n = __builtin_readcyclecounter(); acc[i] += n - t2; t2 = n; }
@@ -99,9 +100,19 @@ struct Prof {
     __device__ __forceinline__ void mark(int) {}
     __device__ __forceinline__ void count(int) {}
     __device__ __forceinline__ void count(int, int) {}
+    __device__ __forceinline__ void count(int, unsigned long long) {}
     __device__ __forceinline__ void begin2() {}
     __device__ __forceinline__ void mark2(int) {}
 };
+#endif
+// -DMB_PROF -DMB_PROF_INTRA: the intra analysis split on the nested clock: acc[22] = cycles of its 8x8 part, acc[23] = of its 4x4 part (the 16x16 part is the intra
+// phase less the two), acc[30] = three counts of 21 bits: 4x4 blocks analysed | macroblocks that ran all sixteen | that entered the loop.  Slots 22 / 23 have no other
+// writer; slot 30 is also named by the B encode's "prediction has arrived" sentinel, whose condition never holds.  The analysis restarts the nested clock (begin2) after
+// its 16x16 part: no caller of mb_analyse_intra has a begin2 .. mark2 section open around the call, and one that did would have to reopen it.
+#ifdef MB_PROF_INTRA
+#define PFI(x) x
+#else
+#define PFI(x)
 #endif
 
 // a wave-uniform value the compiler cannot prove uniform (it came through LDS or a vector load): say so, it then lives in an SGPR
@@ -916,7 +927,7 @@ __device__ __forceinline__ void load_levels_scan(const int16_t *src, int v[4], i
 // Final encode of an Intra_4x4 / Intra_8x8 macroblock of a trellis session (x264: i_skip_intra is 0 under --trellis 1, so the blocks are coded
 // again): the modes of the analysis (L.modes4 / L.modes8), every block predicted from its re-coded neighbours in the tile, transformed,
 // quantised by the trellis search, reconstructed.  Levels go to lvw in their final layout; returns the non-zero flags (R.nnz4 / R.nnz8 form).
-template <int M, class TR>
+template <int M, bool PAIR, class TR>
 __device__ __forceinline__ unsigned mb_encode_i4x4_trellis(const EncK &k, MbLds<M> &L, const MbCtx &c, uint32_t cz, uint32_t t4, const Q4 &q4, const TR &trc, int16_t *lvw)
 {
     // The blocks in ten rounds along the anti-diagonals x + 2 y instead of sixteen steps in coding order: a block's neighbours (left, top, top left, and the
@@ -933,17 +944,31 @@ __device__ __forceinline__ unsigned mb_encode_i4x4_trellis(const EncK &k, MbLds<
         uint8_t *bt = tile;
         int my_idx = 0;
         int16_t *const pair = &L.cand[0][0];          // two blocks' coefficients side by side (the search's candidate list is idle during the encode passes)
-        for (int q = 0; q < nb; q++) {
-            const int by = by0 + q, bx = t - 2 * by, idx = blkidx_of(bx, by);
-            const int avail = i4_avail(c.mbx, c.sy, k.mbw, idx);
+        if constexpr (PAIR) {
+            // both blocks' U in one pass (the second's in L.U8, idle here; where the round has one block the second is the first again), then each slot's
+            // lanes predict their block's mode alone: the mode's table words come from the lanes of t4 that hold them, off the U -> prediction chain
+            const int by1 = by0 + nb - 1, idx0 = blkidx_of(t - 2 * by0, by0), idx1 = blkidx_of(t - 2 * by1, by1);
+            uint8_t *const bt0 = tile + by0 * 4 * IT_STRIDE + (t - 2 * by0) * 4, *const bt1 = tile + by1 * 4 * IT_STRIDE + (t - 2 * by1) * 4;
             lds_sync();
-            uint8_t *bq = tile + by * 4 * IT_STRIDE + bx * 4;
-            pred4_build_u(L.U, bq, IT_STRIDE, avail, lane);
-            const uint32_t pr = pred4_row4(L.U, t4);
-            const uint32_t en = (uint32_t)__shfl((int)cz, idx * 4 + j);
-            const int bm = L.modes4[idx];
-            const uint32_t bpq = (uint32_t)__shfl((int)pr, bm * 4 + j);
-            if (slot == q) { unpack4(en, e); unpack4(bpq, p); bp = bpq; bt = bq; my_idx = idx; }
+            pred4_build_u2(L.U, L.U8, bt0, bt1, IT_STRIDE, i4_avail(c.mbx, c.sy, k.mbw, idx0), i4_avail(c.mbx, c.sy, k.mbw, idx1), lane);
+            my_idx = slot ? idx1 : idx0;
+            bt = slot ? bt1 : bt0;
+            bp = pred4_row4(slot ? L.U8 : L.U, (uint32_t)__shfl((int)t4, L.modes4[my_idx] * 4 + j));
+            unpack4((uint32_t)__shfl((int)cz, my_idx * 4 + j), e); unpack4(bp, p);
+        } else {
+            // (the RD-refinement instantiations: one build and one prediction pass per block, as before the paired build)
+            for (int q = 0; q < nb; q++) {
+                const int by = by0 + q, bx = t - 2 * by, idx = blkidx_of(bx, by);
+                const int avail = i4_avail(c.mbx, c.sy, k.mbw, idx);
+                lds_sync();
+                uint8_t *bq = tile + by * 4 * IT_STRIDE + bx * 4;
+                pred4_build_u(L.U, bq, IT_STRIDE, avail, lane);
+                const uint32_t pr = pred4_row4(L.U, t4);
+                const uint32_t en = (uint32_t)__shfl((int)cz, idx * 4 + j);
+                const int bm = L.modes4[idx];
+                const uint32_t bpq = (uint32_t)__shfl((int)pr, bm * 4 + j);
+                if (slot == q) { unpack4(en, e); unpack4(bpq, p); bp = bpq; bt = bq; my_idx = idx; }
+            }
         }
 #pragma unroll
         for (int i = 0; i < 4; i++) v[i] = e[i] - p[i];
@@ -1042,9 +1067,11 @@ struct IntraRes { int satd_i16, satd_i8, satd_i4, pred16; unsigned nnz4, nnz8; i
                   int dir16[4], dir8v; };
 
 // Needs the neighbour samples in L.tile / L.tile8 / L.nb and the neighbour macroblocks' edge modes in L.nmodes.
-template <int M, class TR = TrCtx>
+// ROUNDS: the 4x4 part in ten anti-diagonal rounds (every instantiation but the RD-refinement ones, RD 5 / 6 — the only ones that spill VGPRs: with the rounds,
+// k_mb_slice<5, 2, true, 6, true> differed from the checker on two hard-content pictures and the cause is not found; they keep the loop in coding order)
+template <int M, bool ROUNDS, class TR = TrCtx>
 __device__ __forceinline__ void mb_analyse_intra(const EncK &k, MbLds<M> &L, const MbCtx &c, uint32_t cz, uint32_t t4, int parts, int i_satd_inter,
-                                                 bool fast_intra, bool early_term, bool mbrd, const Q4 &q4, const Q8 &q8, IntraRes &R, const TR *tra = nullptr)
+                                                 bool fast_intra, bool early_term, bool mbrd, const Q4 &q4, const Q8 &q8, IntraRes &R, Prof &pf, const TR *tra = nullptr)
 {
     const bool RF2 = mbrd && ((k.rd >> 1) & 31) && (k.slice_type != X264GPU_SLICE_B || k.subme >= 9);      // x264's i_mbrd >= 2 (RD refinement, subme >= 8; a B slice analyses one level down)
     const bool every_mode = RF2 || (mbrd && !fast_intra);          // x264: i_mbrd >= 1 + b_fast_intra
@@ -1074,6 +1101,7 @@ __device__ __forceinline__ void mb_analyse_intra(const EncK &k, MbLds<M> &L, con
             if (left || top) { const int cst = cost16(m1); R.dir16[1] = cst; if (cst < R.satd_i16) { R.satd_i16 = cst; R.pred16 = m1; } }
         }
         R.satd_i16 += b_type_cost;
+        PFI(pf.begin2());          // (the 16x16 part = the intra phase less the two below)
         if (R.satd_i16 > thresh16) return;
     }
     // ---- 8x8: R8 layout, lane = (mode group, row); eight modes in one pass, the ninth in a second ----
@@ -1167,14 +1195,100 @@ __device__ __forceinline__ void mb_analyse_intra(const EncK &k, MbLds<M> &L, con
         if (idx == 3) R.satd_i8 = i_cost;
         else i_cost = (i_cost * (idx == 0 ? 1024 : idx == 1 ? 512 : 341)) >> 8;
         const int thr8 = sm < 3 ? 4 : sm < 6 ? 5 : 6;
+        PFI(pf.mark2(22));
         if (early_term && min(i_cost, R.satd_i16) > (int)(((long long)i_satd_inter * thr8) >> 2)) return;
     }
-    // ---- 4x4: nine modes per block in parallel (one quad of lanes per mode), blocks in coding order ----
-    if (parts & 2) {
+    // ---- 4x4: ten rounds along the anti-diagonals x + 2 y, the (at most two) blocks of a round side by side ----
+    // What a block reads — its left, top, top-left and (where i4_avail grants them) top-right samples, the modes of its left and top blocks — lies on earlier
+    // diagonals, so the two blocks of a round share one pass of every stage: one U build (DPP rows 0 and 1), one prediction + SATD of the modes 0..7 of both
+    // (lane = block << 5 | mode << 2 | row) and a short one of mode 8 of both (lanes 0..7: block << 2 | row, the lanes that then encode the chosen modes), one
+    // transform / quantiser / inverse.  The mode choice is x264's, block by block.
+    // Early exit: x264 adds the costs in coding order and leaves after a block < 15 once the sum exceeds thresh.  Every term (best + 3 lambda, best >= -3 lambda:
+    // only the predicted mode has the bonus, raw costs are not negative) is >= 0, so the loop in coding order completes exactly when the sum over the blocks
+    // 0..14 is <= thresh, and any partial sum that leaves out block 15 exceeding thresh means it does not: tested after each of the rounds 0..8.  What an
+    // exit leaves half filled (L.modes4, L.lv4, R.nnz4, the tile) is read only when R.satd_i4 is valid.
+    if (ROUNDS && (parts & 2)) {
+        int thresh = early_term ? min(min(i_satd_inter, R.satd_i16), R.satd_i8) : MB_COST_MAX;
+        if (early_term && mbrd) thresh = (int)((long long)thresh * (fast_intra ? 9 : 10) / 8);       // RD: a little slack, the SATD order is not final
+        if (lane < 16) L.modes4[lane] = 2;
+        int i_cost = lambda * (24 + 16) + b_type_cost, t;
+        const uint32_t t4p = (uint32_t)__shfl((int)t4, lane & 31), t48 = (uint32_t)__shfl((int)t4, 32 + j);      // the table words of this layout (t4: lane = mode << 2 | row)
+        const int blk = lane >> 5, slot = (lane >> 2) & 1;
+        const bool tr4 = tra && (tra->on & TR_I4);          // --trellis 2: the blocks the following ones predict from are the searched ones
+        int16_t *const pair = &L.cand[0][0];                // ... the round's coefficients side by side for one search call (the candidate list is idle outside a search)
+        uint8_t *const U1 = L.U8;                           // the second block's U (the 8x8 analysis is over)
+        PFI(pf.count(30, 1ull << 42));
+        for (t = 0; t < 10; t++) {
+            // the blocks (bx, by) with bx + 2 by == t: by from max(0, ceil((t - 3) / 2)) to min(3, t / 2); B = A where there is one only
+            const int byA = t <= 3 ? 0 : (t - 2) >> 1, nb = min(3, t >> 1) - byA + 1, byB = byA + nb - 1, bxA = t - 2 * byA, bxB = t - 2 * byB;
+            const int idxA = blkidx_of(bxA, byA), idxB = blkidx_of(bxB, byB);
+            const int availA = i4_avail(c.mbx, c.sy, k.mbw, idxA), availB = i4_avail(c.mbx, c.sy, k.mbw, idxB);
+            lds_sync();
+            const int pmA = i4_pred_mode(L.nmodes, c.mbx, c.sy, idxA, L.modes4), pmB = i4_pred_mode(L.nmodes, c.mbx, c.sy, idxB, L.modes4);
+            uint8_t *btA = tile + byA * 4 * IT_STRIDE + bxA * 4, *btB = tile + byB * 4 * IT_STRIDE + bxB * 4;
+            pred4_build_u2(L.U, U1, btA, btB, IT_STRIDE, availA, availB, lane);
+            const uint32_t pr = pred4_row4(blk ? U1 : L.U, t4p);
+            const uint32_t en = (uint32_t)__shfl((int)cz, (blk ? idxB : idxA) * 4 + j);
+            const int sat = quad_sum(c.satd ? satd4_half(en, pr, lane) : sad4(en, pr));
+            const uint32_t en8 = (uint32_t)__shfl((int)cz, (slot ? idxB : idxA) * 4 + j);
+            uint32_t pr8 = 0;
+            int sat8 = 0;
+            if ((availA | availB) & AVAIL_LEFT) {          // (mode 8 predicts from the left column alone)
+                pr8 = pred4_row4(slot ? U1 : L.U, t48);
+                sat8 = quad_sum(c.satd ? satd4_half(en8, pr8, lane) : sad4(en8, pr8));
+            }
+            int bmA, bmB;
+            const int bestA = pick_intra_mode([&](int m) { return m < 8 ? rl(sat, m * 4) : rl(sat8, 0); }, availA, pmA, lambda, true, every_mode, bmA);
+            i_cost += bestA + 3 * lambda;
+            if (nb > 1) {
+                const int bestB = pick_intra_mode([&](int m) { return m < 8 ? rl(sat, 32 + m * 4) : rl(sat8, 4); }, availB, pmB, lambda, true, every_mode, bmB);
+                i_cost += bestB + 3 * lambda;
+            } else bmB = bmA;
+            if (lane < nb) L.modes4[lane ? idxB : idxA] = (uint8_t)(lane ? bmB : bmA);
+            PFI(pf.count(30, nb));
+            if (t < 9 && i_cost > thresh) break;
+            // code the round's blocks (the next ones predict from them; the last one so that the result is complete if Intra4x4 wins): lanes 0..3 A, 4..7 B
+            const int bm = slot ? bmB : bmA, my_idx = slot ? idxB : idxA;
+            uint8_t *bt = slot ? btB : btA;
+            const bool mine = lane < 4 * nb;
+            const uint32_t bp07 = (uint32_t)__shfl((int)pr, slot << 5 | (bm & 7) << 2 | j), bp8 = (uint32_t)__shfl((int)pr8, slot << 2 | j);
+            const uint32_t bp = bm == 8 ? bp8 : bp07;
+            int e[4], p[4], v[4];
+            unpack4(en8, e); unpack4(bp, p);
+#pragma unroll
+            for (int i = 0; i < 4; i++) v[i] = e[i] - p[i];
+            dct4_quad(v, lane);
+            if (tr4) {
+                if (mine) store_levels_scan(pair + slot * 16, v, j);
+                lds_sync();
+                // (psy: the round's blocks are not neighbours in the block order — the source transform of the second lies idxB - idxA blocks from the first's)
+                trellis_run<2>(*tra, pair, 16, nb, c.qp, true, lane, tr_fd4(*tra) + idxA * 16, (idxB - idxA) * 16);
+                lds_sync();
+                load_levels_scan(pair + slot * 16, v, j);
+                lds_sync();
+            } else quant4_row(v, q4, j);
+            const bool nz = quad_or((v[0] | v[1] | v[2] | v[3]) != 0 ? 1 : 0) != 0;
+            if (mine) store_levels_scan(L.lv4 + my_idx * 16, v, j);
+            dequant4_row(v, q4, j);
+            idct4_quad(v, lane);
+#pragma unroll
+            for (int i = 0; i < 4; i++) v[i] += p[i];
+            if (mine) *(uint32_t *)(bt + j * IT_STRIDE) = nz ? pack4_clip(v) : bp;
+            const unsigned long long bal = __ballot(nz && j == 0 && mine);
+            if (bal & 1) R.nnz4 |= 1u << idxA;
+            if (bal & 16) R.nnz4 |= 1u << idxB;
+        }
+        lds_sync();
+        if (t == 10) { R.satd_i4 = i_cost; PFI(pf.count(30, 1ull << 21)); }
+        PFI(pf.mark2(23));
+    }
+    // ---- 4x4, the blocks in coding order (ROUNDS false: the RD-refinement instantiations, see above the template) ----
+    if (!ROUNDS && (parts & 2)) {
         int thresh = early_term ? min(min(i_satd_inter, R.satd_i16), R.satd_i8) : MB_COST_MAX;
         if (early_term && mbrd) thresh = (int)((long long)thresh * (fast_intra ? 9 : 10) / 8);       // RD: a little slack, the SATD order is not final
         if (lane < 16) L.modes4[lane] = 2;
         int i_cost = lambda * (24 + 16) + b_type_cost, idx;
+        PFI(pf.count(30, 1ull << 42));
         for (idx = 0;; idx++) {
             const int bx = z_bx(idx), by = z_by(idx);
             const int avail = i4_avail(c.mbx, c.sy, k.mbw, idx);
@@ -1189,6 +1303,7 @@ __device__ __forceinline__ void mb_analyse_intra(const EncK &k, MbLds<M> &L, con
             const int best = pick_intra_mode([&](int m) { return rl(sat, m * 4); }, avail, pm, lambda, true, every_mode, bm);
             i_cost += best + 3 * lambda;
             if (lane == 0) L.modes4[idx] = (uint8_t)bm;
+            PFI(pf.count(30, 1));
             if (idx < 15 && i_cost > thresh) break;
             const uint32_t bp = (uint32_t)__shfl((int)pr, bm * 4 + j);
             int e[4], p[4], v[4];
@@ -1215,7 +1330,8 @@ __device__ __forceinline__ void mb_analyse_intra(const EncK &k, MbLds<M> &L, con
             if (idx == 15) break;
         }
         lds_sync();
-        if (idx == 15) R.satd_i4 = i_cost;
+        if (idx == 15) { R.satd_i4 = i_cost; PFI(pf.count(30, 1ull << 21)); }
+        PFI(pf.mark2(23));
     }
 }
 
@@ -2089,7 +2205,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MB_WAVES_PER
             }
             satd_chroma = mb_intra_chroma_cost(k, L, c, predc, rf_dirc);
             pf.mark(PH_INTRA_CHROMA);
-            mb_analyse_intra(k, L, c, cz, t4, parts, c.chroma_me ? i_satd_inter - satd_chroma : i_satd_inter, fast_intra, early_term, rdon, q_li, q8i, IR, TRL2 && tra_ctx.on ? &tra_ctx : nullptr);
+            mb_analyse_intra<M, RD != 5 && RD != 6>(k, L, c, cz, t4, parts, c.chroma_me ? i_satd_inter - satd_chroma : i_satd_inter, fast_intra, early_term, rdon, q_li, q8i, IR, pf, TRL2 && tra_ctx.on ? &tra_ctx : nullptr);
             if (c.chroma_me) { IR.satd_i16 += satd_chroma; IR.satd_i8 += satd_chroma; IR.satd_i4 += satd_chroma; }
             if (pslice) {
                 if (lane == 0) { recd.aux[0] = i_satd_inter; recd.aux[1] = min(min(IR.satd_i16, IR.satd_i8), IR.satd_i4); recd.aux[2] = rl(S.cost, ME_16); }
@@ -2812,7 +2928,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MB_WAVES_PER
                 if (commit && lane < 16) recd.i4_mode[lane] = L.modes4[lane];
                 nnz = IR.nnz4;
                 const bool tri4 = TRL && !TRL2 && (trc.on & TR_I4) != 0;
-                if (tri4) nnz = mb_encode_i4x4_trellis(k, L, c, cz, t4, q_li, trc, lvw);
+                if (tri4) nnz = mb_encode_i4x4_trellis<M, RD != 5 && RD != 6>(k, L, c, cz, t4, q_li, trc, lvw);
                 for (int i8 = 0; i8 < 4; i8++) if ((nnz >> (4 * i8)) & 15) cbp_luma |= 1 << i8;
                 {
                     const uint32_t rz = *(const uint32_t *)(tile + zy * IT_STRIDE + zx);

@@ -359,7 +359,7 @@ for (;; rd_ph++) {
             }
             pf.mark(PH_ME_GLUE);
             satd_chroma = mb_intra_chroma_cost(k, L, c, predc);
-            mb_analyse_intra(k, L, c, cz, t4, parts, c.chroma_me ? i_cost - satd_chroma : i_cost, fast_intra, early_term, false, q_li, q8i, IR, (const TrCtx *)nullptr);
+            mb_analyse_intra<M, RD != 5 && RD != 6>(k, L, c, cz, t4, parts, c.chroma_me ? i_cost - satd_chroma : i_cost, fast_intra, early_term, false, q_li, q8i, IR, pf, (const TrCtx *)nullptr);
             if (c.chroma_me) { IR.satd_i16 += satd_chroma; IR.satd_i8 += satd_chroma; IR.satd_i4 += satd_chroma; }
             pf.mark(PH_INTRA);
             rd_best = i_cost; rd_i16 = IR.satd_i16; rd_i8 = IR.satd_i8; rd_i4 = IR.satd_i4;
@@ -391,7 +391,7 @@ for (;; rd_ph++) {
         if constexpr (TRL2) {
             if (k.trellis & 64) { tra_ctx.on = k.trellis & 63; tra_ctx.r = cab.r; tra_ctx.r8 = cab.r8; tra_ctx.model = cab_modelv; tra_ctx.tt.size_unary = k.tr_su; tra_ctx.tt.trans_unary = k.tr_tu; tra_ctx.tt.lambda2 = k.tr_l2; }
         }
-        mb_analyse_intra(k, L, c, cz, t4, parts, c.chroma_me ? rd_satd_inter - satd_chroma : rd_satd_inter, fast_intra, early_term, true, q_li, q8i, IR, TRL2 && tra_ctx.on ? &tra_ctx : nullptr);
+        mb_analyse_intra<M, RD != 5 && RD != 6>(k, L, c, cz, t4, parts, c.chroma_me ? rd_satd_inter - satd_chroma : rd_satd_inter, fast_intra, early_term, true, q_li, q8i, IR, pf, TRL2 && tra_ctx.on ? &tra_ctx : nullptr);
         if (c.chroma_me) { IR.satd_i16 += satd_chroma; IR.satd_i8 += satd_chroma; IR.satd_i4 += satd_chroma; }
         pf.mark(PH_INTRA);
         // x264_mb_analyse_transform_rd: the other transform size for the winner (B_SKIP has none)
