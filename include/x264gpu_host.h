@@ -47,6 +47,10 @@ int x264host_mux_close(void *h, int64_t largest_pts, int64_t second_largest_pts)
 int x264host_last_decision(x264_t *h, int *qp, int *scenecut, int32_t costs[4]);
 /* ... and the float quantiser (x264 rc->qpm) its macroblock quantisers were rounded from (0 = the integer quantiser) */
 float x264host_last_qpm(x264_t *h);
+/* GOP slots with quantisers planned ahead (X264GPU_GOP_SLOTS_RC=1: CRF with B pictures under --threads G): the pictures planned ahead so far; 0 when the mode is off */
+long x264host_gop_slots_planned(x264_t *h);
+/* tests: the reconstruction of the picture GOP slot `slot` (--threads G > 1) coded last, tight I420; 0, or -1 */
+int x264host_gop_slots_recon(x264_t *h, int slot, uint8_t *i420_out);
 /* ... the second pass' plan (init_pass2): per picture of the statistics file, display order, the planned quantiser scale and the bits expected before it; returns the count */
 int x264host_pass2_plan(x264_t *h, double *new_qscale, double *expected_bits, int n);
 /* VBV sessions (--vbv-maxrate / --vbv-bufsize): the rate control's view of the picture whose NAL units the last call returned.  out[12] = the buffer fill (bits)

@@ -5,6 +5,7 @@
 #include "batch.hpp"
 #include "quality.hpp"
 #include "noisereduction.hpp"
+#include "siderows.hpp"
 #include <string.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -12,9 +13,6 @@
 #include <chrono>
 #include <condition_variable>
 #include <mutex>
-
-// The gather entry is resolved weakly: with a device library without it (an older build; the tests' CPU stand-in) the group copies row by row instead.
-#pragma weak x264gpu_gather_rows
 
 namespace x264host {
 
@@ -133,15 +131,9 @@ bool batch_side_inputs(BatchGroup *g, int first)
     bool ok = true;
     if (any[0] || any[1] || any[2]) {
         if (g->async) ok = x264gpu_event_record(g->ev_side, nullptr) == X264GPU_OK && x264gpu_stream_wait_event(st, g->ev_side) == X264GPU_OK;
-        if (ok && x264gpu_gather_rows) {
-            // the table goes up on an upload stream, not on the compute stream: x264gpu_memcpy_h2d waits for its stream, and the compute stream still runs the round before
-            ok = x264gpu_memcpy_h2d((void *)g->d_side_tab[gen], g->side_tab.data(), 3 * N * sizeof(void *), g->up_streams.empty() ? nullptr : g->up_streams[0]) == X264GPU_OK;
-            for (int a = 0; a < 3 && ok; a++) if (any[a]) ok = x264gpu_gather_rows(g->d_side_tab[gen] + (size_t)a * N, row, g->d_side[a][gen], g->N, st) == X264GPU_OK;
-        } else
-            for (int a = 0; a < 3 && ok; a++) if (any[a]) for (size_t s = 0; s < N && ok; s++) {
-                const void *src = g->side_tab[(size_t)a * N + s];
-                ok = (src ? x264gpu_memcpy_d2d(g->d_side[a][gen] + s * row, src, row, st) : x264gpu_memset(g->d_side[a][gen] + s * row, 0, row, st)) == X264GPU_OK;
-            }
+        // (the table goes up on an upload stream, not on the compute stream, which still runs the round before)
+        uint8_t *const dst[3] = { g->d_side[0][gen], g->d_side[1][gen], g->d_side[2][gen] };
+        ok = ok && side_rows_gather(g->side_tab.data(), any, g->d_side_tab[gen], dst, N, row, st, g->up_streams.empty() ? nullptr : g->up_streams[0]);
     }
     ok = ok && x264gpu_encoder_set_mb_qp_offsets(g->gpu, any[0] ? (const float *)g->d_side[0][gen] : nullptr) == X264GPU_OK &&
          x264gpu_encoder_set_lowres_mvs(g->gpu, any[1] ? (const int16_t *)g->d_side[1][gen] : nullptr) == X264GPU_OK &&
@@ -234,9 +226,7 @@ bool Batch::join(const x264gpu_config &cfg1, int N, size_t insz, size_t nmb, int
                 ok = x264gpu_malloc((void **)&ng->d_side_tab[i], 3 * (size_t)N * sizeof(void *)) == X264GPU_OK && (!side.offsets || x264gpu_malloc((void **)&ng->d_side[0][i], rows) == X264GPU_OK) &&
                      (!side.mvs || (x264gpu_malloc((void **)&ng->d_side[1][i], rows) == X264GPU_OK && x264gpu_malloc((void **)&ng->d_side[2][i], rows) == X264GPU_OK));
             }
-            const int16_t absent = 0x7fff;
-            ok = ok && (!side.mvs || (x264gpu_malloc((void **)&ng->d_mv_absent, nmb * 4) == X264GPU_OK && x264gpu_memset(ng->d_mv_absent, 0, nmb * 4, nullptr) == X264GPU_OK &&
-                                      x264gpu_stream_sync(nullptr) == X264GPU_OK && x264gpu_memcpy_h2d(ng->d_mv_absent, &absent, sizeof(absent), nullptr) == X264GPU_OK));
+            ok = ok && (!side.mvs || (ng->d_mv_absent = side_rows_absent(nmb)) != nullptr);
             if (!ok) { batch_destroy(ng); return false; }
         }
         const char *oe = getenv("X264GPU_BATCH_OVERLAP");

@@ -103,6 +103,9 @@ struct x264_t {
     int32_t last_costs[4] = { 0, 0, 0, 0 };
     int G = 1;                    // --threads G: GOP slots (1: none); G > 1 sessions run through `gops` alone
     GopSlots gops;                // host/gopslots.hpp: G closed GOPs of the stream in lock-step, dealt to the visible devices
+    // X264GPU_GOP_SLOTS_RC=1, a CRF session with B pictures under --threads G: the session plans every picture as a --threads 1 session does (lookahead, slice types,
+    // its own DPB model, RateControl::start — bmode_plan) and hands it to the slots instead of coding it; plan_count: pictures planned so far (coding order)
+    bool slots_rc = false; long plan_count = 0;
     int slices = 1;               // x264 slice threads: slices per picture (own wavefront + own NAL each)
     int slices_plain = 0;         // ... or x264 --slices N: the same split, filtered across the boundaries, up to one slice per macroblock row
     bool failed = false;                 // a GPU call failed; the session only returns errors from now on
@@ -442,7 +445,7 @@ static void open_modes(x264_t *h)
     if (p.i_bframe) {
         // (below --subme 7 x264 analyses B slices without RD: k_mb_b.inc's NORD flow; from 7 up their RD decisions count CABAC sizes or CAVLC bits)
         // (--threads G: closed GOPs in lock-step carry B pictures when every GOP has the same picture structure and quantisers: constant quantiser)
-        const char *why = (p.i_threads > 1 && p.rc.i_rc_method != X264_RC_CQP) ? "threads 1, or a constant quantiser with --threads G" : p.i_keyint_max < 2 ? "keyint > 1" :
+        const char *why = (p.i_threads > 1 && p.rc.i_rc_method != X264_RC_CQP && !h->slots_rc) ? "threads 1, or a constant quantiser with --threads G" : p.i_keyint_max < 2 ? "keyint > 1" :
                           (p.rc.i_rc_method == X264_RC_ABR && p.rc.i_bitrate <= 0) ? "constant-quantiser, CRF or ABR rate control with a bitrate" : nullptr;
         if (why) { xlog(&p, X264_LOG_WARNING, "B-frames need %s in the MI355X path: bframes 0\n", why); p.i_bframe = 0; }
     }
@@ -546,7 +549,7 @@ static void open_quantisers(x264_t *h)
     if (p.rc.i_rc_method == X264_RC_CQP || p.rc.f_aq_strength <= 0) p.rc.i_aq_mode = X264_AQ_NONE;
     // macroblock-tree: needs a rate-controlled session and pictures held back (rc-lookahead); x264 switches it off under constant QP
     if (p.rc.i_rc_method == X264_RC_CQP || p.rc.i_lookahead <= 0) p.rc.b_mb_tree = 0;
-    if (p.rc.b_mb_tree && p.i_threads > 1) { xlog(&p, X264_LOG_INFO, "mbtree needs threads 1 (GOPs in lock-step are coded before what follows them is seen): mbtree 0\n"); p.rc.b_mb_tree = 0; }
+    if (p.rc.b_mb_tree && p.i_threads > 1 && !h->slots_rc) { xlog(&p, X264_LOG_INFO, "mbtree needs threads 1 (GOPs in lock-step are coded before what follows them is seen): mbtree 0\n"); p.rc.b_mb_tree = 0; }
     p.rc.b_mb_tree = p.rc.b_mb_tree != 0;
     h->tstats.writing = rc.tree_write = rc.pass1 && p.rc.b_mb_tree && MbTreeStats::opted_in();
     // (VBV plans over the lookahead too, with or without the tree: x264's vbv_lookahead; rc-lookahead 0 leaves it the reactive algorithm)
@@ -613,7 +616,9 @@ static x264gpu_config open_device_config(x264_t *h)
 {
     x264_param_t &p = h->param;
     x264gpu_config cfg = {};
-    h->G = GopSlots::fit(p, h->keyint);
+    // (quantisers planned ahead: a ring picture has up to three rows of the plan store beside it)
+    h->G = GopSlots::fit(p, h->keyint, h->slots_rc ? 3 * (size_t)h->nmb * 4 : 0);
+    if (h->G <= 1) h->slots_rc = false;          // (nothing to run in parallel: the session is the --threads 1 one)
     cfg.width = p.i_width; cfg.height = p.i_height; cfg.streams = h->G; cfg.refs = p.i_frame_reference; cfg.slices = h->slices; cfg.slices_plain = h->slices_plain; cfg.cabac = p.b_cabac;
     cfg.qp_i = h->qp_i; cfg.qp_p = h->qp_p; cfg.me_range = p.analyse.i_me_range; cfg.subme = p.analyse.i_subpel_refine;
     cfg.deblock = p.b_deblocking_filter; cfg.deblock_alpha = p.i_deblocking_filter_alphac0; cfg.deblock_beta = p.i_deblocking_filter_beta;
@@ -677,8 +682,19 @@ static bool open_device(x264_t *h)
             sp.idr_pic_id = (int)(gop & 0xffff);
             write_slices(cd.bytes, cd.off, cd.types, sp, ch->slices, mb, lv, ch->param.b_annexb != 0, cd.idr, nullptr, 1);
         };
-        return h->gops.open(p, cfg, h->rc, { h->G, h->keyint, h->nmb, h->qp_i, h->qp_p, h->bframes, h->bpyramid, h->weightp, h->log2_max_frame_num, h->direct_mode, h->dpbmode,
-                                             h->device, slice_params_base(h), write_coded });
+        GopSlots::Setup su = { h->G, h->keyint, h->nmb, h->qp_i, h->qp_p, h->bframes, h->bpyramid, h->weightp, h->log2_max_frame_num, h->direct_mode, h->dpbmode,
+                               h->device, slice_params_base(h), write_coded };
+        if (h->slots_rc) {
+            // what the session's own lookahead will hand the slots with every planned picture (bmode_plan): offsets from the tree or --aq-mode 2 / 3, vectors from the
+            // lookahead object the tree opens; the lookahead's wait is x264's i_slicetype_length
+            su.planned = true;
+            su.plan_offsets = p.rc.b_mb_tree || (p.rc.i_aq_mode >= 2 && p.rc.f_aq_strength > 0);
+            su.plan_mvs = p.rc.b_mb_tree != 0;
+            su.plan_wait = p.rc.b_mb_tree && p.rc.i_lookahead > h->bframes ? p.rc.i_lookahead : h->bframes;
+            if (p.rc.b_mb_tree && h->weightp)
+                xlog(&p, X264_LOG_INFO, "weightp %d in GOP slots: a fade's explicit weights are not coded (the slots of a device call share them; the lookahead still weighs fades for its costs)\n", h->weightp);
+        }
+        return h->gops.open(p, cfg, h->rc, su);
     } else if (ok_setup && h->batch.want) {
         // what the session's own lookahead will hand the group with every picture (bmode_plan): offsets from the tree or --aq-mode 2 / 3, vectors from the lookahead object
         // the tree (or a VBV plan) opens; sessions that differ in any of it, or in what shapes it, form groups of their own
@@ -826,6 +842,12 @@ x264_t *x264_encoder_open(x264_param_t *param)
     if (!p.i_timebase_num || !p.i_timebase_den) { p.i_timebase_num = p.i_fps_den; p.i_timebase_den = p.i_fps_num; }
 
     open_toolset(h);
+    {   // GOP slots with quantisers planned ahead (opt-in): CRF with B pictures under --threads G, nothing that reads coded sizes or shares the session's state
+        const char *se = getenv("X264GPU_GOP_SLOTS_RC"), *be = getenv("X264GPU_BATCH");
+        h->slots_rc = se && atoi(se) == 1 && p.i_threads > 1 && p.rc.i_rc_method == X264_RC_CRF && p.rc.f_rf_constant >= 1.0f && p.i_bframe > 0 && p.i_keyint_max >= 2 &&
+                      p.i_keyint_max < (1 << 20) && p.rc.i_vbv_max_bitrate <= 0 && p.rc.i_vbv_buffer_size <= 0 && !p.rc.b_stat_read && !p.rc.b_stat_write && !(be && atoi(be) >= 2) &&
+                      !p.analyse.i_noise_reduction;
+    }
     open_vbv(h);
     open_modes(h);
     open_quantisers(h);
@@ -872,6 +894,7 @@ int x264_encoder_headers(x264_t *h, x264_nal_t **pp_nal, int *pi_nal)
     return (int)h->out.size();
 }
 
+static int gop_slots_pop(x264_t *h, x264_nal_t **pp_nal, int *pi_nal, x264_picture_t *pic_out);
 // ---- --threads G > 1 (host/gopslots.hpp): the picture goes to the slots, or the input has ended; then the next coded picture in output order, if there is one ----
 static int encode_gop_slots(x264_t *h, x264_nal_t **pp_nal, int *pi_nal, x264_picture_t *pic_in, x264_picture_t *pic_out, bool resident)
 {
@@ -880,6 +903,11 @@ static int encode_gop_slots(x264_t *h, x264_nal_t **pp_nal, int *pi_nal, x264_pi
     h->failed |= gs.failed;
     if (rc < 0) return -1;
     if (pic_in && gs.with_b()) h->all_pts.push_back(pic_in->i_pts);
+    return gop_slots_pop(h, pp_nal, pi_nal, pic_out);
+}
+static int gop_slots_pop(x264_t *h, x264_nal_t **pp_nal, int *pi_nal, x264_picture_t *pic_out)
+{
+    GopSlots &gs = h->gops;
     GopSlots::Coded c;
     if (!gs.pop(c)) return 0;
     h->out = std::move(c.bytes);
@@ -1036,7 +1064,8 @@ static void bmode_plan(x264_t *h, x264_t::PicPlan &f, x264gpu_encoder *gpu, long
     int fc[16], ff[16], nf = 0;
     for (size_t i = 0; i < behind.size() && nf < 16 && behind[i].type == PIC_B; i++) { fc[nf] = (int)(coded_index + 1 + (long)i); ff[nf] = behind[i].e.frame; nf++; }
     // (the explicit weights of a picture are the same in every stream of a device call: a member of a batch group, whose lookahead would find its own, codes fades unweighted)
-    const DpbPlan plan = h->dpb.plan(pl.type, pl.e.frame, nf, fc, ff, pl.type == PIC_P && pl.e.w.on && !h->batch.joined() ? &pl.e.w : nullptr);
+    // (... and so does a session whose pictures are coded by GOP slots)
+    const DpbPlan plan = h->dpb.plan(pl.type, pl.e.frame, nf, fc, ff, pl.type == PIC_P && pl.e.w.on && !h->batch.joined() && !h->slots_rc ? &pl.e.w : nullptr);
     f.nal_ref_idc = plan.nal_ref_idc;
     x264gpu_pic &pic = f.pic;
     pic = plan.pic;
@@ -1390,6 +1419,40 @@ static int inflight_retire(x264_t *h, x264_nal_t **pp_nal, int *pi_nal, x264_pic
     return bmode_finish(h, f, h->h_mb.data(), h->h_lv.data(), pp_nal, pi_nal, pic_out);
 }
 
+// ---- GOP slots with quantisers planned ahead (X264GPU_GOP_SLOTS_RC=1): the plan pass.  Every picture the slice-type decision releases is planned as encode_bmode plans
+//      it — in the stream's coding order, on the session's own DPB model and rate control, nothing issued to a device encoder — and handed to the slots with the rows its
+//      own encoder would have been told; a flush plans everything left, then the slots code their partly gathered batch.  Then the next coded picture, if there is one
+static int encode_slots_rc(x264_t *h, x264_nal_t **pp_nal, int *pi_nal, x264_picture_t *pic_out, bool flushing)
+{
+    auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    GopSlots &gs = h->gops;
+    while (!gs.was_flushed()) {
+        const double tb0 = now();
+        const bool decided = h->slicetype.decide(flushing, h->rc);
+        h->failed |= h->slicetype.failed;
+        h->t_b[0] += now() - tb0;
+        if (h->failed) return -1;
+        if (!decided) break;
+        x264_t::PicPlan f;
+        bmode_plan(h, f, nullptr, h->plan_count, false);
+        h->dpb.commit();
+        h->plan_count++;
+        h->t_b[4] += 1;
+        const SliceType::Pic &pl = f.pl;
+        const double tb1 = now();
+        const int rc = gs.put_planned({ pl.e.frame, pl.type, f.pic.qp, f.pic.qpm, f.pic.direct_temporal, h->q_raw[(size_t)pl.e.slot], f.d_offsets, { f.d_mvs[0], f.d_mvs[1] } });
+        h->t_b[1] += now() - tb1;
+        h->failed |= gs.failed;
+        if (rc < 0) return -1;
+    }
+    if (flushing) {
+        const int rc = gs.flush();
+        h->failed |= gs.failed;
+        if (rc < 0) return -1;
+    }
+    return gop_slots_pop(h, pp_nal, pi_nal, pic_out);
+}
+
 static int encode_bmode_inflight(x264_t *h, x264_nal_t **pp_nal, int *pi_nal, x264_picture_t *pic_out, bool flushing)
 {
     // issue what can be issued (a new picture's arrival may decide a mini-GOP: its closing picture, its B reference, its b pictures, as far as contexts and slots go) ...
@@ -1409,6 +1472,7 @@ int x264_encoder_encode(x264_t *h, x264_nal_t **pp_nal, int *pi_nal, x264_pictur
     *pi_nal = 0; *pp_nal = nullptr;
     if (h->failed) return -1;
     if (!pic_in) {      // flush: GOP-parallel batches, or the pictures still waiting in the lookahead queue, one per call
+        if (h->slots_rc) return encode_slots_rc(h, pp_nal, pi_nal, pic_out, true);
         if (h->G > 1) return encode_gop_slots(h, pp_nal, pi_nal, nullptr, pic_out, false);
         if (h->dpbmode) return h->inflight > 1 ? encode_bmode_inflight(h, pp_nal, pi_nal, pic_out, true) : encode_bmode(h, pp_nal, pi_nal, pic_out, true);
         return h->queue.empty() ? 0 : encode_queued(h, pp_nal, pi_nal, pic_out, true);
@@ -1422,6 +1486,7 @@ int x264_encoder_encode(x264_t *h, x264_nal_t **pp_nal, int *pi_nal, x264_pictur
     // Zero-copy input (x264gpu_host_input_i420): the caller (the VfW shell after the device-side colourspace conversion)
     // already placed a tight I420 picture in the encoder's device staging buffer.
     const bool resident = pic_in->img.plane[0] == h->d_in;
+    if (h->slots_rc && h->gops.was_flushed()) { xlog(&p, X264_LOG_ERROR, "x264_encoder_encode: pictures after a flush are not supported in GOP-parallel mode\n"); return -1; }
     auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     double t0 = now(), t1;
 #define PHASE(i) do { t1 = now(); h->t_phase[i] += t1 - t0; t0 = t1; } while (0)
@@ -1432,7 +1497,7 @@ int x264_encoder_encode(x264_t *h, x264_nal_t **pp_nal, int *pi_nal, x264_pictur
         const uint8_t *src = pic_in->img.plane[pl];
         for (int y = 0; y < ph; y++, dst += pw, src += pic_in->img.i_stride[pl]) memcpy(dst, src, pw);
     }
-    if (h->G > 1) return encode_gop_slots(h, pp_nal, pi_nal, pic_in, pic_out, resident);
+    if (h->G > 1 && !h->slots_rc) return encode_gop_slots(h, pp_nal, pi_nal, pic_in, pic_out, resident);
     PHASE(0);
     // ---- the picture enters the lookahead queue (x264_lookahead_put_frame): upload, frame cost against the previous source picture,
     //      AQ offsets, slice-type decision (keyint / forced type / scenecut) — all causal, so they are taken on arrival ----
@@ -1487,7 +1552,7 @@ int x264_encoder_encode(x264_t *h, x264_nal_t **pp_nal, int *pi_nal, x264_pictur
         }
         h->all_pts.push_back(e.pts);
         PHASE(1);
-        const int size = h->inflight > 1 ? encode_bmode_inflight(h, pp_nal, pi_nal, pic_out, false) : encode_bmode(h, pp_nal, pi_nal, pic_out, false);
+        const int size = h->slots_rc ? encode_slots_rc(h, pp_nal, pi_nal, pic_out, false) : h->inflight > 1 ? encode_bmode_inflight(h, pp_nal, pi_nal, pic_out, false) : encode_bmode(h, pp_nal, pi_nal, pic_out, false);
         PHASE(4);
         h->t_phase[5] += 1;
         return size;
@@ -1502,7 +1567,7 @@ int x264_encoder_encode(x264_t *h, x264_nal_t **pp_nal, int *pi_nal, x264_pictur
     return size;
 }
 
-int x264_encoder_delayed_frames(x264_t *h) { return !h || h->failed ? 0 : h->G > 1 ? h->gops.delayed() : h->dpbmode ? h->slicetype.delayed() + (int)h->fl.size() + (h->defer[0].valid ? 1 : 0) + (h->defer[1].valid ? 1 : 0) : (int)h->queue.size(); }
+int x264_encoder_delayed_frames(x264_t *h) { return !h || h->failed ? 0 : h->slots_rc ? h->slicetype.delayed() + h->gops.delayed() : h->G > 1 ? h->gops.delayed() : h->dpbmode ? h->slicetype.delayed() + (int)h->fl.size() + (h->defer[0].valid ? 1 : 0) + (h->defer[1].valid ? 1 : 0) : (int)h->queue.size(); }
 
 void x264_encoder_close(x264_t *h)
 {
@@ -1719,6 +1784,9 @@ int x264host_write_headers_b(int width, int height, int level_idc, int log2_max_
 /* device pointer of the encoder's input staging buffer: a tight I420 picture (Y w*h, U, V).  A picture whose plane[0]
  * equals this pointer is encoded in place, without the host copy-in and upload (used by the VfW shell, vfw.cpp). */
 uint8_t *x264gpu_host_input_i420(x264_t *h) { return h ? h->d_in : nullptr; }
+
+long x264host_gop_slots_planned(x264_t *h) { return h && h->slots_rc ? h->gops.planned() : 0; }
+int x264host_gop_slots_recon(x264_t *h, int slot, uint8_t *i420_out) { return h && h->G > 1 && i420_out ? h->gops.recon(slot, i420_out) : -1; }
 
 int x264host_last_decision(x264_t *h, int *qp, int *scenecut, int32_t costs[4])
 {

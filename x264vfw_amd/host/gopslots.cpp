@@ -1,5 +1,6 @@
 // gopslots.cpp — the --threads G mode (gopslots.hpp has the contract)
 #include "gopslots.hpp"
+#include "siderows.hpp"
 #include <limits.h>
 #include <stdlib.h>
 #include <string>
@@ -25,10 +26,10 @@ static std::vector<std::pair<int, int>> gop_coding_order(int n, int bframes, int
     return out;
 }
 
-int GopSlots::fit(x264_param_t &p, int keyint)
+int GopSlots::fit(x264_param_t &p, int keyint, size_t plan_bytes)
 {
     int G = p.i_threads;
-    const double pic = (double)p.i_width * p.i_height * 1.5;
+    const double pic = (double)p.i_width * p.i_height * 1.5 + (double)plan_bytes;
     while (G > 1 && pic * keyint * G > 24e9) G--;
     if (keyint >= (1 << 20)) G = 1;                  // "infinite" keyint: nothing to run in parallel
     if (G != p.i_threads) xlog(&p, X264_LOG_INFO, "threads %d -> %d (GOP ring of keyint %d pictures)\n", p.i_threads, G, keyint);
@@ -55,6 +56,25 @@ bool GopSlots::open(const x264_param_t &param, x264gpu_config cfg, RateControl &
              x264gpu_malloc((void **)&dc.d_mb, (size_t)dc.nsl * c.nmb * sizeof(x264gpu_mb)) == X264GPU_OK &&
              x264gpu_malloc((void **)&dc.d_lv, (size_t)dc.nsl * c.nmb * X264GPU_MB_LEVELS * sizeof(int16_t)) == X264GPU_OK &&
              x264gpu_malloc((void **)&dc.d_ring, (size_t)dc.nsl * K * insz) == X264GPU_OK;
+        if (ok && c.planned && (c.plan_offsets || c.plan_mvs)) {
+            const size_t row = (size_t)c.nmb * 4;          // a float, or a vector of two int16, a macroblock
+            for (int a = 0; a < 3 && ok; a++)
+                if (a == 0 ? c.plan_offsets : c.plan_mvs)
+                    ok = x264gpu_malloc((void **)&dc.d_plan[a], (size_t)dc.nsl * K * row) == X264GPU_OK && x264gpu_malloc((void **)&dc.d_side[a], (size_t)dc.nsl * row) == X264GPU_OK;
+            ok = ok && x264gpu_malloc((void **)&dc.d_tab, 3 * (size_t)dc.nsl * sizeof(void *)) == X264GPU_OK && (!c.plan_mvs || (dc.d_absent = side_rows_absent((size_t)c.nmb)) != nullptr);
+            // a device library may take the lookahead's vectors for encoders of one stream only (it says so when it is handed the array: nothing is read here).  The
+            // device's slots then get an encoder each, coded one after the other: same pictures, same bytes, no lock-step on that device
+            if (ok && c.plan_mvs && dc.nsl > 1) {
+                if (x264gpu_encoder_set_lowres_mvs(dc.gpu, (const int16_t *)dc.d_side[1]) == X264GPU_OK) ok = x264gpu_encoder_set_lowres_mvs(dc.gpu, nullptr) == X264GPU_OK;
+                else {
+                    xlog(p, X264_LOG_INFO, "device %d: the device library takes lookahead vectors for one stream an encoder (%s): its %d GOP slots run on an encoder each\n", dc.dev, x264gpu_last_error(), dc.nsl);
+                    x264gpu_encoder_destroy(dc.gpu); dc.gpu = nullptr;
+                    cfg.streams = 1;
+                    dc.solo.assign((size_t)dc.nsl, nullptr);
+                    for (int l = 0; l < dc.nsl && ok; l++) ok = x264gpu_encoder_create(&dc.solo[(size_t)l], &cfg) == X264GPU_OK;
+                }
+            }
+        }
     }
     const std::string err = ok ? "" : x264gpu_last_error();
     (void)x264gpu_set_device(c.device);
@@ -69,6 +89,11 @@ bool GopSlots::open(const x264_param_t &param, x264gpu_config cfg, RateControl &
         gopb = true;
         gorder = gop_coding_order(K, c.bframes, c.bpyramid);
         gdpb.dpb.configure(p->i_frame_reference, c.bframes, c.bpyramid, c.log2_max_frame_num, c.weightp);
+        if (c.planned) {
+            recs.assign(n, Rec());
+            xlog(p, X264_LOG_INFO, "%d GOP slots in lock-step with B pictures (bframes %d, b-pyramid %d, quantisers planned ahead by the session's lookahead and rate control%s%s): pictures leave in coding order, %d calls late\n",
+                 G, c.bframes, c.bpyramid, c.plan_offsets ? ", quantiser offsets" : "", c.plan_mvs ? ", lookahead vectors" : "", (G - 1) * K + c.plan_wait + 1);
+        } else
         xlog(p, X264_LOG_INFO, "%d GOP slots in lock-step with B pictures (bframes %d, b-pyramid %d, constant quantiser): pictures leave in coding order, %d calls late\n", G, c.bframes, c.bpyramid, (G - 1) * K + c.bframes + 1);
     }
     return true;
@@ -80,9 +105,13 @@ void GopSlots::close()
     for (auto &dc : devs) {
         if (devs.size() > 1) (void)x264gpu_set_device(dc.dev);
         if (dc.gpu) x264gpu_encoder_destroy(dc.gpu);
+        for (x264gpu_encoder *e : dc.solo) if (e) x264gpu_encoder_destroy(e);
         if (dc.d_mb) x264gpu_free(dc.d_mb);
         if (dc.d_lv) x264gpu_free(dc.d_lv);
         if (dc.d_ring) x264gpu_free(dc.d_ring);
+        for (int a = 0; a < 3; a++) { if (dc.d_plan[a]) x264gpu_free(dc.d_plan[a]); if (dc.d_side[a]) x264gpu_free(dc.d_side[a]); }
+        if (dc.d_tab) x264gpu_free((void *)dc.d_tab);
+        if (dc.d_absent) x264gpu_free(dc.d_absent);
     }
     if (devs.size() > 1) (void)x264gpu_set_device(c.device);
     devs.clear();          // (a second close finds nothing)
@@ -147,6 +176,31 @@ void GopSlots::start_pool(int pos, int slot0, int nslots, const std::function<vo
         pool.emplace_back([work, th, nthr, slot0, nslots]() { for (int s = slot0 + th; s < slot0 + nslots; s += nthr) work(s); });
 }
 
+// Quantisers planned ahead, in front of device d's call for coding position cpos (on its thread, its device current): the rows of its slots' pictures out of the plan
+// store become the encoder's [nsl][mb_count] arrays — offsets, vectors of list 0, vectors of list 1 — one gather an array on the stream the call runs on.  A slot
+// coded along and thrown away takes the first asked slot's rows; a slot without vectors among slots with them the "absent" row.  false: the device's last error set
+bool GopSlots::planned_side_rows(DevCtx &dc, int d, int cpos, int slot0, int nslots)
+{
+    const size_t N = (size_t)dc.nsl, row = (size_t)c.nmb * 4, K = (size_t)c.keyint;
+    std::vector<const void *> tab(3 * N, nullptr);
+    bool any[3] = { false, false, false };
+    int mine0 = -1;          // the first asked slot this device owns (it owns one, or it would sit the position out): the plan store is per device
+    for (int s = slot0; s < slot0 + nslots && mine0 < 0; s++) if (s % D() == d) mine0 = s;
+    if (mine0 < 0) return true;
+    for (size_t l = 0; l < N; l++) {
+        int s = slot_of((int)l, d);
+        if (s < slot0 || s >= slot0 + nslots) s = mine0;
+        const Rec &r = recs[(size_t)s * K + (size_t)cpos];
+        for (int a = 0; a < 3; a++)
+            if (r.have[a]) { tab[(size_t)a * N + l] = dc.d_plan[a] + ((size_t)cpos * N + (size_t)(s / D())) * row; any[a] = true; }
+    }
+    for (int a = 1; a < 3; a++) if (any[a]) for (size_t l = 0; l < N; l++) if (!tab[(size_t)a * N + l]) tab[(size_t)a * N + l] = dc.d_absent;
+    if ((any[0] || any[1] || any[2]) && !side_rows_gather(tab.data(), any, dc.d_tab, dc.d_side, N, row, nullptr, nullptr)) return false;
+    return x264gpu_encoder_set_mb_qp_offsets(dc.gpu, any[0] ? (const float *)dc.d_side[0] : nullptr) == X264GPU_OK &&
+           x264gpu_encoder_set_lowres_mvs(dc.gpu, any[1] ? (const int16_t *)dc.d_side[1] : nullptr) == X264GPU_OK &&
+           x264gpu_encoder_set_lowres_mvs1(dc.gpu, any[2] ? (const int16_t *)dc.d_side[2] : nullptr) == X264GPU_OK;
+}
+
 // Sessions with B pictures: coding position cpos of `order` for the slots [slot0, slot0 + nslots) of batch `batch` — the plan from the DPB model (the same for
 // every slot), one x264gpu_encode_pictures per device that owns one of the slots.  0, or -1 after a device failure
 int GopSlots::code_position_b(int batch, int cpos, int slot0, int nslots, const std::vector<std::pair<int, int>> &order, GopDpb &gd)
@@ -157,6 +211,11 @@ int GopSlots::code_position_b(int batch, int cpos, int slot0, int nslots, const 
     for (size_t i = (size_t)cpos + 1; i < order.size() && nf < 16 && order[i].second == PIC_B; i++) { fc[nf] = (int)i; ff[nf] = order[i].first; nf++; }
     const DpbPlan plan = gd.dpb.plan(type, disp, nf, fc, ff, nullptr);
     x264gpu_pic pic = plan.pic;
+    // quantisers planned ahead: what the plan pass decided for the slot's picture (a slot coded along and thrown away: the first asked slot's)
+    auto rec_of = [&](int s) -> const Rec & { return recs[(size_t)(s >= slot0 && s < slot0 + nslots ? s : slot0) * K + (size_t)cpos]; };
+    if (c.planned) {
+        if (type == PIC_B || type == PIC_BREF) { pic.direct_temporal = rec_of(slot0).direct_temporal; pic.direct_auto = 0; gd.dpb.set_direct(pic.direct_temporal, 0); }
+    } else
     if ((type == PIC_B || type == PIC_BREF) && c.direct_mode == 2) {
         // x264 slice_header_init: temporal direct prediction only when the co-located picture's reference 0 is this picture's reference 0
         const bool temporal = pic.nref[0] && pic.nref[1] && gd.l0ref0poc[pic.slot[1][0]] == plan.list_poc[0][0];
@@ -166,24 +225,53 @@ int GopSlots::code_position_b(int batch, int cpos, int slot0, int nslots, const 
     if (plan.nal_ref_idc) gd.l0ref0poc[pic.dst] = pic.nref[0] ? plan.list_poc[0][0] : INT_MIN;
     // constant quantiser by picture type, a zone shifts it by the picture's display index in the stream (a slot coded along and thrown away: the type's)
     std::vector<int> qps((size_t)G, rc->qp_constant[type]);
-    for (int s = slot0; s < slot0 + nslots; s++) qps[(size_t)s] = rc->start(type, (int)(((long)batch * G + s) * K + disp));
+    // (quantisers planned ahead: RateControl::start ran in the plan pass, in the stream's coding order; a slot's float quantiser and direct mode travel in its x264gpu_pic)
+    std::vector<float> qpms((size_t)G, 0.f);
+    std::vector<uint8_t> temporal((size_t)G, (uint8_t)pic.direct_temporal);
+    for (int s = 0; s < G; s++) {
+        if (c.planned) { const Rec &r = rec_of(s); qps[(size_t)s] = r.qp; qpms[(size_t)s] = r.qpm; if (type == PIC_B || type == PIC_BREF) temporal[(size_t)s] = (uint8_t)r.direct_temporal; }
+        else if (s >= slot0 && s < slot0 + nslots) qps[(size_t)s] = rc->start(type, (int)(((long)batch * G + s) * K + disp));
+    }
     SliceParams sp = c.sp;
     gd.dpb.fill(sp);
     gd.dpb.commit();
     x264gpu_mb *hmb; int16_t *hlv;
     auto launch = [&](DevCtx &dc, int d) {
         std::vector<x264gpu_pic> pics((size_t)dc.nsl, pic);
-        for (int l = 0; l < dc.nsl; l++) pics[(size_t)l].qp = qps[(size_t)slot_of(l, d)];
+        for (int l = 0; l < dc.nsl; l++) {
+            const size_t s = (size_t)slot_of(l, d);
+            pics[(size_t)l].qp = qps[s];
+            if (c.planned) { pics[(size_t)l].qpm = qpms[s]; pics[(size_t)l].direct_temporal = temporal[s]; }
+        }
+        if (!dc.solo.empty()) {
+            // an encoder a slot (open() says when): the asked slots one after the other, each told its own rows where they lie in the plan store
+            const size_t row = (size_t)c.nmb * 4;
+            for (int l = 0; l < dc.nsl; l++) {
+                const int s = slot_of(l, d);
+                if (s < slot0 || s >= slot0 + nslots) continue;
+                const Rec &r = recs[(size_t)s * K + (size_t)cpos];
+                const uint8_t *rows[3];
+                for (int a = 0; a < 3; a++) rows[a] = r.have[a] ? dc.d_plan[a] + ((size_t)cpos * dc.nsl + (size_t)l) * row : nullptr;
+                x264gpu_encoder *e = dc.solo[(size_t)l];
+                if (x264gpu_encoder_set_mb_qp_offsets(e, (const float *)rows[0]) != X264GPU_OK || x264gpu_encoder_set_lowres_mvs(e, (const int16_t *)rows[1]) != X264GPU_OK ||
+                    x264gpu_encoder_set_lowres_mvs1(e, (const int16_t *)rows[2]) != X264GPU_OK ||
+                    x264gpu_encode_pictures(e, dc.d_ring + ((size_t)disp * dc.nsl + (size_t)l) * insz, &pics[(size_t)l], dc.d_mb + (size_t)l * c.nmb,
+                                            dc.d_lv + (size_t)l * c.nmb * X264GPU_MB_LEVELS, nullptr) != X264GPU_OK) return false;
+            }
+            return true;
+        }
+        if (c.planned && !planned_side_rows(dc, d, cpos, slot0, nslots)) return false;
         return x264gpu_encode_pictures(dc.gpu, dc.d_ring + (size_t)disp * dc.nsl * insz, pics.data(), dc.d_mb, dc.d_lv, nullptr) == X264GPU_OK;
     };
     if (run_devices(slot0, nslots, true, launch, &hmb, &hlv) < 0) return -1;
     const int ref_idc = plan.nal_ref_idc;
-    start_pool(cpos, slot0, nslots, [this, batch, cpos, disp, type, hmb, hlv, qps, sp, ref_idc](int s) {
+    start_pool(cpos, slot0, nslots, [this, batch, cpos, disp, type, hmb, hlv, qps, temporal, sp, ref_idc](int s) {
         const size_t row = row_of(s);
         Coded &cd = slotbuf[(size_t)s * c.keyint + cpos];
         cd.ref_idc = ref_idc; cd.disp = disp;
         SliceParams sps = sp;
         sps.qp = qps[(size_t)s];
+        if (c.planned && (type == PIC_B || type == PIC_BREF)) sps.direct_spatial = !temporal[(size_t)s];
         c.write(cd, type, (long)batch * c.G + s, sps, hmb + row * c.nmb, hlv + row * c.nmb * X264GPU_MB_LEVELS);
     });
     return 0;
@@ -291,6 +379,45 @@ int GopSlots::put(const Input &in, int64_t pic_pts)
     return 0;
 }
 
+// Quantisers planned ahead: the stream's next picture in CODING order (closed GOPs: GOP by GOP, so the slot and the coding position follow from the count).  Its
+// source and rows move to the device that owns the slot; when slot G - 1 delivers the coding position the full GOP has there, the position is coded.  A picture of
+// slot G - 1 that is not the full GOP's (the stream's last, shorter GOP, known at the flush only) ends the lock-step rounds: flush() codes that GOP alone
+int GopSlots::put_planned(const Planned &pl)
+{
+    const int G = c.G, K = c.keyint;
+    const long per_batch = (long)G * K;
+    if (failed) return -1;
+    if (flushed) { xlog(p, X264_LOG_ERROR, "x264_encoder_encode: pictures after a flush are not supported in GOP-parallel mode\n"); return -1; }
+    const long i = submitted, b = i / per_batch, r = i % per_batch;
+    const int s = (int)(r / K), cpos = (int)(r % K), t = pl.frame % K;
+    if (pl.frame / K != b * G + s) { xlog(p, X264_LOG_ERROR, "x264_encoder_encode: GOP slots: picture %d was planned outside its GOP's turn (the GOPs of the stream are not closed and %d pictures long)\n", pl.frame, K); failed = true; return -1; }
+    if (r == 0) gb_next = 0;
+    DevCtx &dc = devs[(size_t)(s % D())];
+    const size_t l = (size_t)(s / D()), row = (size_t)c.nmb * 4;
+    Rec &rec = recs[(size_t)s * K + cpos];
+    rec.type = pl.type; rec.disp = t; rec.qp = pl.qp; rec.qpm = pl.qpm; rec.direct_temporal = pl.direct_temporal;
+    const void *rows[3] = { pl.d_offsets, pl.d_mvs[0], pl.d_mvs[1] };
+    bool ok = x264gpu_memcpy_d2d(dc.d_ring + ((size_t)t * dc.nsl + l) * insz, pl.d_src, insz, nullptr) == X264GPU_OK;
+    for (int a = 0; a < 3 && ok; a++) {
+        rec.have[a] = rows[a] != nullptr;
+        if (rows[a] && !dc.d_plan[a]) { xlog(p, X264_LOG_ERROR, "x264_encoder_encode: GOP slots: a picture was planned with rows its plan store was not opened for\n"); failed = true; return -1; }
+        if (rows[a]) ok = x264gpu_memcpy_d2d(dc.d_plan[a] + ((size_t)cpos * dc.nsl + l) * row, rows[a], row, nullptr) == X264GPU_OK;
+    }
+    // (the copies run on the caller's device's stream; a slot on another device is coded on that device's: they are complete before it starts.  On the caller's own
+    //  device the position's call runs behind them on the same stream; the lookahead reuses its arrays on that stream too)
+    if (ok && dc.dev != c.device) ok = x264gpu_stream_sync(nullptr) == X264GPU_OK;
+    if (!ok) { xlog(p, X264_LOG_ERROR, "x264_encoder_encode: upload failed: %s\n", x264gpu_last_error()); return -1; }
+    submitted++;
+    const bool full_gops = cpos < (int)gorder.size() && gorder[(size_t)cpos].first == t && gorder[(size_t)cpos].second == pl.type;
+    if (s == G - 1 && full_gops && cpos == gb_next) {
+        if (code_position_b((int)b, cpos, 0, G, gorder, gdpb) < 0) return -1;
+        gb_next++;
+        next_pos = cpos + 1 == K ? 0 : cpos + 1;
+    } else if (!pool.empty()) join_pool();
+    drain_coded();
+    return 0;
+}
+
 // codes what the partly gathered batch holds, position by position, with the slots that have that position; later calls only drain
 int GopSlots::flush()
 {
@@ -312,7 +439,9 @@ int GopSlots::flush()
                 join_pool();
                 GopDpb gp;
                 gp.dpb.configure(p->i_frame_reference, c.bframes, c.bpyramid, c.log2_max_frame_num, c.weightp);
-                const std::vector<std::pair<int, int>> po = gop_coding_order(part, c.bframes, c.bpyramid);
+                std::vector<std::pair<int, int>> po = gop_coding_order(part, c.bframes, c.bpyramid);
+                // (quantisers planned ahead: the order the plan pass took, which is what the serial session codes)
+                if (c.planned) for (int cpos = 0; cpos < part; cpos++) { const Rec &r = recs[(size_t)full * K + cpos]; po[(size_t)cpos] = { r.disp, r.type }; }
                 for (int cpos = 0; cpos < part; cpos++) slot_have[(size_t)full * K + cpos] = 0;
                 for (int cpos = 0; cpos < part; cpos++)
                     if (code_position_b((int)b, cpos, full, 1, po, gp) < 0) return -1;
@@ -330,6 +459,21 @@ int GopSlots::flush()
     join_pool();
     drain_coded();
     return 0;
+}
+
+int GopSlots::recon(int slot, uint8_t *i420_out)
+{
+    if (slot < 0 || slot >= c.G || devs.empty()) return -1;
+    join_pool();
+    DevCtx &dc = devs[(size_t)(slot % D())];
+    uint8_t *d = nullptr;
+    int rc = D() > 1 ? x264gpu_set_device(dc.dev) : X264GPU_OK;
+    if (rc == X264GPU_OK) rc = x264gpu_malloc((void **)&d, insz);
+    if (rc == X264GPU_OK) rc = dc.solo.empty() ? x264gpu_encoder_get_recon(dc.gpu, slot / D(), d, nullptr) : x264gpu_encoder_get_recon(dc.solo[(size_t)(slot / D())], 0, d, nullptr);
+    if (rc == X264GPU_OK) rc = x264gpu_memcpy_d2h(i420_out, d, insz, nullptr);
+    if (d) x264gpu_free(d);
+    if (D() > 1) (void)x264gpu_set_device(c.device);
+    return rc == X264GPU_OK ? 0 : -1;
 }
 
 bool GopSlots::pop(Coded &cd)

@@ -18,7 +18,8 @@
 // order and on a DPB model of its own.
 // Output order.  I / P: stream order.  With B pictures: coding order inside every GOP, GOPs in stream order, with x264's pts / dts (the emitting code's).  One
 // picture a call either way, through pop().
-// Delay.  Nothing leaves before the first batch's last GOP starts delivering: (G - 1) * keyint calls, + bframes + 1 with B pictures.
+// Delay.  Nothing leaves before the first batch's last GOP starts delivering: (G - 1) * keyint calls, + bframes + 1 with B pictures (+ the lookahead's wait when the
+// quantisers are planned ahead: put_planned).
 //
 // Threads.  put / flush / pop / close belong to one calling thread.  A position runs on that thread when there is one device, else on one host thread per device,
 // joined before run_devices returns.  The access units of a position are then written by the CAVLC pool WHILE the next position runs on the devices.  A pool
@@ -43,13 +44,26 @@ struct GopSlots {
     // the access unit of GOP `gop`'s picture of type PIC_* into cd, from the slot's records and levels; runs on pool threads, several at a time
     using Writer = std::function<void(Coded &cd, int pic_type, long gop, SliceParams sp, const x264gpu_mb *mb, const int16_t *lv)>;
     // what the session settled before open(): G (what fit returned), the structure, the toolset, the caller's device, the session-constant SliceParams, the writer
-    struct Setup { int G, keyint, nmb, qp_i, qp_p, bframes, bpyramid, weightp, log2_max_frame_num, direct_mode; bool dpbmode; int device; SliceParams sp; Writer write; };
+    struct Setup { int G, keyint, nmb, qp_i, qp_p, bframes, bpyramid, weightp, log2_max_frame_num, direct_mode; bool dpbmode; int device; SliceParams sp; Writer write;
+                   bool planned = false, plan_offsets = false, plan_mvs = false; int plan_wait = 0; };      // planned: see Planned below; which rows its pictures can come with; the lookahead's wait (for the log)
     // a picture that arrives: tight I420 at `host`, or — resident — already in `staging`, the session's device buffer on the caller's device; the session's lookahead
     // and its four sums on that device (CRF)
     struct Input { const uint8_t *host; uint8_t *staging; bool resident; x264gpu_lookahead *la; int32_t *d_la; };
 
-    // the slot count the device ring (keyint x G pictures) allows: under 24 GB; p.i_threads follows, said in the log
-    static int fit(x264_param_t &p, int keyint);
+    // Quantisers planned ahead (X264GPU_GOP_SLOTS_RC=1: CRF sessions with B pictures).  The session runs its lookahead, its slice-type decision, a DPB model that follows
+    // the serial stream and RateControl::start for every picture as a --threads 1 session would, in the stream's coding order, and hands each planned picture in here
+    // instead of coding it: its source picture on the caller's device, what was decided for it, and the rows its own encoder would have been told (device arrays on the
+    // caller's device; nullptr: none).  The lookahead recycles those arrays long before a slot codes the picture — up to (G - 1) x keyint pictures later — so the
+    // picture goes into the ring and the rows into the plan store of the device that owns the slot (both device to device).  Slot G - 1's picture of a coding position
+    // completes the position, which is then coded: every slot at its own quantisers, rows and direct mode.
+    struct Planned { int frame, type, qp; float qpm; int direct_temporal; const uint8_t *d_src; const float *d_offsets; const int16_t *d_mvs[2]; };
+    int put_planned(const Planned &pl);          // 0, or -1: said in the log
+    long planned() const { return c.planned ? submitted : 0; }
+    bool was_flushed() const { return flushed; }
+    int recon(int slot, uint8_t *i420_out);          // tests: the reconstruction of the picture the slot's stream coded last, to the host; 0, or -1
+
+    // the slot count the device ring (keyint x G pictures, plan_bytes of plan store beside each) allows: under 24 GB; p.i_threads follows, said in the log
+    static int fit(x264_param_t &p, int keyint, size_t plan_bytes = 0);
     // the slots dealt to the devices — an encoder of cfg (its streams: the device's slots), record buffers and a ring per device — then the host side.  Leaves the
     // caller's device current.  false: said in the log (close() frees what exists)
     bool open(const x264_param_t &param, x264gpu_config cfg, RateControl &rc, const Setup &setup);
@@ -67,9 +81,16 @@ private:
     struct DevCtx {
         int dev = 0, nsl = 0, base = 0;  // device ordinal; slots it owns; its first row in the host download buffers
         x264gpu_encoder *gpu = nullptr;
+        std::vector<x264gpu_encoder *> solo;      // quantisers planned ahead on a device library that takes lookahead vectors for one stream an encoder: an encoder a slot instead of gpu
         uint8_t *d_ring = nullptr;       // [keyint positions][nsl slots] tight I420 pictures of the batch being gathered
         x264gpu_mb *d_mb = nullptr; int16_t *d_lv = nullptr;
+        // quantisers planned ahead: the plan store [keyint coding positions][nsl slots] of each array (offsets, vectors of list 0 / 1), the arrays gathered for the
+        // position being coded [nsl], the device table of [3][nsl] row pointers the gather reads, the vectors' "absent" row (host/siderows.hpp)
+        uint8_t *d_plan[3] = { nullptr, nullptr, nullptr }, *d_side[3] = { nullptr, nullptr, nullptr }; const void **d_tab = nullptr; int16_t *d_absent = nullptr;
     };
+    // what the plan pass decided for a ring picture (slot * keyint + coding position); have: which rows lie in the plan store
+    struct Rec { int type = -1, disp = 0, qp = 0; float qpm = 0.f; int direct_temporal = 0; bool have[3] = { false, false, false }; };
+    std::vector<Rec> recs;
     struct GopDpb { Dpb dpb; int l0ref0poc[8] = { 0 }; };
     const x264_param_t *p = nullptr;
     RateControl *rc = nullptr;
@@ -103,6 +124,7 @@ private:
     void start_pool(int pos, int slot0, int nslots, const std::function<void(int)> &work);
     int code_position(int batch, int t, int nslots_with_t);
     int code_position_b(int batch, int cpos, int slot0, int nslots, const std::vector<std::pair<int, int>> &order, GopDpb &gd);
+    bool planned_side_rows(DevCtx &dc, int d, int cpos, int slot0, int nslots);
     void drain_coded();
 };
 

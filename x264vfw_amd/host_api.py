@@ -112,6 +112,8 @@ PIC_IDR, PIC_I, PIC_P, PIC_BREF, PIC_B = range(5)
 _sig("x264host_last_decision", _i, [C.c_void_p, C.POINTER(_i), C.POINTER(_i), C.POINTER(C.c_int32)])
 _sig("x264host_last_qpm", C.c_float, [C.c_void_p])
 _sig("x264host_pictures_in_flight", C.c_int, [C.c_void_p])
+_sig("x264host_gop_slots_planned", C.c_long, [C.c_void_p])
+_sig("x264host_gop_slots_recon", _i, [C.c_void_p, _i, C.c_void_p])
 _sig("x264host_pass2_plan", _i, [C.c_void_p, C.c_void_p, C.c_void_p, _i])
 _sig("x264host_last_vbv", _i, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(_i), C.POINTER(_i), _i])
 VBV_FIELDS = ("fill_before", "fill_after", "qp_novbv", "qp_clipped", "frame_size_planned", "attempts", "filler", "qp_final", "overhead_bits", "buffer_size", "max_rate",
