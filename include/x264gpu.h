@@ -127,6 +127,11 @@ int x264gpu_gather_rows(const void *const *d_rows, size_t row_bytes, void *d_dst
  * chroma DC planes, luma DC flag; d_r / d_r8 the role-indexed context registers (64 lanes a case, csrc/cabac_layout.hip.h) in, d_r_out / d_r8_out out;
  * d_bits the bits in 1/256 (sign and escape bypass bins included).  tests/test_gpu_prims.py checks it against a serial restatement. */
 int x264gpu_cabac_level_walk(const int16_t *d_levels, const int32_t *d_what, int n, const uint32_t *d_r, const uint32_t *d_r8, uint32_t *d_r_out, uint32_t *d_r8_out, int32_t *d_bits, void *stream);
+/* The same walk as the macroblock layer runs it: the significance maps of the 8x8 luma blocks (significant_coeff_flag contexts in lanes 0..14,
+ * last_significant_coeff_flag contexts in lanes 16..24 of d_r8) ride the walk of their block's levels.  Arguments as above but d_what holds SIX ints a case, the
+ * sixth the map mode of category 5: 0 = levels only (= x264gpu_cabac_level_walk), 1 = the map with every context's bins from the block's last coefficient down
+ * (x264's size-only coder), 2 = upwards (bitstream order).  tests/test_gpu_cabac_sig8.py checks it against a serial restatement. */
+int x264gpu_cabac_residual_walk(const int16_t *d_levels, const int32_t *d_what, int n, const uint32_t *d_r, const uint32_t *d_r8, uint32_t *d_r_out, uint32_t *d_r8_out, int32_t *d_bits, void *stream);
 /* The other part of that pricing as a primitive: the macroblock layer's own bins (mb_type .. mb_qp_delta, coded_block_flags; contexts 0..104 and
  * 399..401), which the device collects as one bit string per context and walks through the chain table at the end (csrc/cabac_rd.hip.h cab_put /
  * cab_walk_a — this runs those two and nothing else).  n cases; case i codes the triples d_first[i] .. d_first[i + 1] - 1 of d_triples (three ints each:

@@ -4,6 +4,9 @@
 
 EXTRA="-DMB_PROF -DMB_PROF_INTRA" adds a line that splits the intra analysis into its 16x16, 8x8 and 4x4 parts and counts the 4x4 blocks analysed.
 
+EXTRA="-DMB_PROF -DMB_PROF_RD" times the CABAC pricing (slot 15) and splits it: header, coded_block_flags, levels, and the "residual walk:" line — the 8x8
+significance maps' cycles, blocks and rounds, the walk loop's cycles, words and lookups a word.
+
 Prints, per picture, the average cycles per macroblock of every phase (s_memtime deltas summed by lane 0 of each stream's wavefront).
 The timers perturb scheduling a little; use the table for proportions, bench.py for absolute time."""
 import ctypes as C
@@ -62,11 +65,21 @@ def main():
         e1.record()
         torch.cuda.synchronize()
         lib.check(f(h, out.ctypes.data), "mb_prof (is this an MB_PROF build?)")
+        # the residual walk's own counts ride in the upper halves of four count slots (k_mb.hip.h Prof::count_hi): 16 = 8x8 blocks whose significance map was priced,
+        # 20 = chain-table lookups of the walk loop, 21 = words walked, 29 = rounds of the 8x8 maps (one bin a round before the maps became strings, one non-zero
+        # position a round of the compaction since)
+        hi = np.zeros(32)
+        for sl in (16, 20, 21, 29):
+            hi[sl] = float((out[:, sl] >> np.uint64(32)).sum()) / (S * n)
+            out[:, sl] &= np.uint64(0xffffffff)
         a = out.astype(np.float64).mean(axis=0) / n
         tot = a[:13].sum() + (a[15] if a[15] > 100 else 0)          # -DMB_PROF_RD builds: slot 15 = cycles of the CABAC pricing (RD sessions)
         print("%-4s %10.0f " % ("IIPRb"[pt] + str(disp), tot) + " ".join("%9.0f" % v for v in a[:13]) + " %9.2f %9.2f %9.2f" % (a[13], a[14], a[15]) + "   %.1f ms" % e0.elapsed_time(e1))
         if a[16] > 0:         # -DMB_PROF_RD: inside the CABAC pricing (cabac_rd.hip.h), per macroblock
             print("     cab_mb calls %.2f  header %.0f  cbf+sigmaps %.0f  levels %.0f cycles;  walk steps %.1f  non-zero coefficients %.1f" % (a[16], a[17], a[18], a[19], a[20], a[21]))          # (slots 22 / 23: the intra split below)
+        if hi[21] > 0 and not out[:, 30].any():          # (slots 22 / 23 are the intra split's in -DMB_PROF_INTRA builds)
+            print("     residual walk: 8x8 maps %.0f cycles, %.2f blocks a macroblock, %.2f rounds a block;  walk loop %.0f cycles, %.1f words a macroblock, %.2f lookups a word"
+                  % (a[22], hi[16], hi[29] / max(hi[16], 1e-9), a[23], hi[21], hi[20] / max(hi[21], 1e-9)))
         if a[27] > 0:
             print("     around the pricing: candidate's distortion terms + header inputs %.0f  cost bookkeeping %.0f cycles" % (a[27], a[28]))
         if a[24] > 0:

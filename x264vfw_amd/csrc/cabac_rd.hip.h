@@ -9,9 +9,11 @@
 //     evaluates nothing: every bin, or run of bins, is appended to the bit string of the lane that owns its context (cab_put: a few
 //     independent vector operations), the intra modes' flags and the many-block coded_block_flags arrive as whole strings from a ballot, and
 //     all lanes walk their strings through the chain table once a cab_mb call (cab_walk_a, eight bins a lookup).  The residual contexts are
-//     laid out so that EVERY LANE OWNS ONE CONTEXT of the block category being coded and walk their strings the same way (cab_levels_all).
-//     Per-context bin order is all the arithmetic model cares about, and bits add — tests/cabac_bins_ref.py and tests/cabac_levels_ref.py
-//     restate both parts bin by bin;
+//     laid out so that EVERY LANE OWNS ONE CONTEXT of the block category being coded and walk their strings the same way (cab_levels_all):
+//     levels and significance maps alike, an 8x8 block's map too, whose positions share contexts (CabLv::map8 — its lanes compact their bins out
+//     of the block's non-zero mask in vector ALU code and ride the walk of the block's levels; profiles/cabac_sig8_strings.md).
+//     Per-context bin order is all the arithmetic model cares about, and bits add — tests/cabac_bins_ref.py, tests/cabac_levels_ref.py and
+//     tests/cabac_sig8_ref.py restate the parts bin by bin;
 //   * a register with the probability model: lane s = cost of the MPS | cost of the LPS << 9 | state after an LPS << 20;
 //   * cab_mb(): the macroblock layer's bins, either in bitstream order ("evolve": what the finished macroblock leaves behind, skip flag
 //     included) or as x264_macroblock_size_cabac walks them ("size": no skip flag, residual blocks from the last coefficient down with
@@ -185,6 +187,13 @@ struct CabLv {
     unsigned nzac;           // chroma AC blocks with coefficients (bit = plane * 4 + block)
     unsigned nzdc;           // chroma DC blocks with coefficients (bit = plane)
     bool ldc;                // the luma DC block of an Intra_16x16 has coefficients
+    int map8;                // cat0 5: the 8x8 blocks' significance maps ride the walk too — CAB_MAP8_OFF (levels only), _SIZE, _STREAM (the order within a context)
+};
+enum { CAB_MAP8_OFF = 0, CAB_MAP8_SIZE = 1, CAB_MAP8_STREAM = 2 };
+
+// the scan positions of an 8x8 luma block that share a significance-map context (15 significant_coeff_flag contexts, then 9 last_significant_coeff_flag ones)
+static __constant__ const unsigned long long c_cabac_pos8[24] = {
+#include "cabac_masks8x8.inc"
 };
 
 // inclusive prefix sum of v over the wavefront's 64 lanes (DPP: row_shr 1 / 2 / 4 / 8 inside each row of sixteen, then row_bcast:15 into rows 1 and 3 and
@@ -308,7 +317,38 @@ __device__ __forceinline__ void cab_levels_all(Cab &cb, uint32_t model, int lane
             cab_strings_c1<LANE0>(a, c1, blo, bhi, N, pf);
             unsigned long long serial = 0;                   // the cg contexts (bit q - 5) whose strings do not fit a word: coded coefficient by coefficient below
             if (mg) cab_strings_cg<LANE0, 5>(a, a15, cg, blo, bhi, N, serial, pf);
-            // ---- the significance map (4x4-type blocks; an 8x8 block's positions share contexts: cab_block8): position p of a block has its own
+            // ---- the significance map of an 8x8 block (W.map8): its positions SHARE contexts — lanes 0..14 of r8 own the significant_coeff_flag contexts,
+            //      lanes 16..24 the last_significant_coeff_flag ones, c_cabac_pos8 says which positions each sees.  The lanes are not the level contexts'
+            //      (32..41), so the map's strings ride the same walk below.  Within a context the bins go from the last coefficient down as x264's size
+            //      coder sends them (_SIZE) or upwards in bitstream order (_STREAM); position 63 is never coded.  A `last` context's string is closed form:
+            //      one bin a non-zero position, all zero but the block's last position's; a `sig` context's is the block's non-zero flags at its positions,
+            //      compacted — a bit a NON-ZERO position at the rank of that position among the context's (vector ALU only, ten rounds at most) ----
+            if (gshift == 6 && W.map8 != CAB_MAP8_OFF) {
+                pf.begin3(); pf.count_hi(16);
+                const unsigned long long mask = __builtin_bitreverse64(nzm);                  // bit p: position p holds a coefficient (slot = 63 - p)
+                const int last = 63 - __builtin_clzll(mask);
+                const unsigned long long upto = last < 63 ? (2ull << last) - 1 : 0x7fffffffffffffffull;
+                const bool down = W.map8 == CAB_MAP8_SIZE;
+                unsigned long long mine = 0;
+                if (lane < 15) mine = c_cabac_pos8[lane] & upto;
+                else if (lane >= 16 && lane < 25) mine = c_cabac_pos8[15 + lane - 16] & upto & mask;
+                const int n = __builtin_popcountll(mine);
+                unsigned bm = 0;
+                if (lane >= 16) bm = (mine >> last) & 1ull ? (down ? 1u : 1u << (n - 1)) : 0u;
+                else {
+                    unsigned long long ones = mine & mask;
+                    while (__ballot(ones != 0)) {
+                        pf.count_hi(29);
+                        const int i = ones ? __builtin_ctzll(ones) : 0;
+                        const int rank = __builtin_popcountll(mine & ((1ull << i) - 1ull));
+                        bm |= ones ? 1u << (down ? n - 1 - rank : rank) : 0u;
+                        ones &= ones - 1ull;
+                    }
+                }
+                blo |= bm; N += n;                  // (16 bins at most: the level strings of this word went to other lanes)
+                pf.mark3(22);
+            }
+            // ---- the significance map (4x4-type blocks): position p of a block has its own
             //      significant_coeff_flag context (lane sigbase + p) and last_significant_coeff_flag context (lane lastbase + p), so a context sees one
             //      bin a block at most — every such lane appends ITS bin of each block of the word, straight from the word's non-zero mask ----
             if (ncm1) {
@@ -330,12 +370,15 @@ __device__ __forceinline__ void cab_levels_all(Cab &cb, uint32_t model, int lane
             {
                 int st = (int)((reg >> sh) & 255u);
                 unsigned long long B = ((unsigned long long)bhi << 32) | blo;
+                pf.begin3(); pf.count_hi(21);
                 while (__ballot(N > 0)) {
+                    pf.count_hi(20);
                     const int k = min(N, CAB_WALK_BINS);
                     const uint32_t e = ctab[((((1 << k) - 1) + ((int)(unsigned)B & ((1 << k) - 1))) << 7) + st];
                     st = (int)(e & 127u); cb.f8v += (int)(e >> 7);
                     B >>= k; N -= k;
                 }
+                pf.mark3(23);
                 reg = (reg & ~(255u << sh)) | ((uint32_t)st << sh);
             }
             // ---- (rare) a cg context with more than 63 bins in one word: its coefficients one by one ----
@@ -392,28 +435,6 @@ __device__ __forceinline__ void cab_block4(Cab &cb, int &st, uint32_t model, int
     const int p = is_s ? lane - sig0 : lane - last0;
     const int nzp = (int)((mask >> (p & 63)) & 1);
     cab_step(st, cb.f8v, model, (is_s && p <= last) || (is_l && nzp && p <= last), is_s ? nzp : p == last);
-}
-
-static __constant__ const unsigned long long c_cabac_pos8[24] = {
-#include "cabac_masks8x8.inc"
-};
-
-// ... of an 8x8 luma block (64 coefficients, one per lane).  Positions share contexts here, so a lane walks the positions of ITS context:
-// downwards as x264's size-only coder does (flags interleaved with the levels from the last coefficient down), upwards in bitstream order.
-__device__ __forceinline__ void cab_block8(Cab &cb, int &st, uint32_t model, int lane, int coef, bool size)
-{
-    const unsigned long long mask = __ballot(coef != 0);
-    const int last = 63 - __builtin_clzll(mask);
-    const unsigned long long upto = last < 63 ? (2ull << last) - 1 : 0x7fffffffffffffffull;
-    unsigned long long mine = 0;
-    if (lane < 15) mine = c_cabac_pos8[lane] & upto;
-    else if (lane >= 16 && lane < 25) mine = c_cabac_pos8[15 + lane - 16] & upto & mask;
-    while (__ballot(mine != 0)) {
-        const bool have = mine != 0;
-        const int i = have ? (size ? 63 - __builtin_clzll(mine) : __builtin_ctzll(mine)) : 0;
-        cab_step(st, cb.f8v, model, have, lane < 15 ? (int)((mask >> i) & 1) : i == last);
-        mine &= ~(1ull << i);
-    }
 }
 
 // what the coder needs to know about the macroblock and its neighbours (all wave-uniform)
@@ -762,8 +783,8 @@ __device__ __forceinline__ unsigned long long cab_mb(Cab &cb, uint32_t model, in
         };
         // residual: the category's context variables are this lane's byte of r (r8 for 8x8 blocks) for the duration of its blocks
         // (the levels of every block are coded at the end, all categories side by side: W collects which blocks hold coefficients)
-        CabLv W = { -1, 0u, 0u, 0u, false };
-        auto flush_levels = [&]() { pf.mark2(18); cab_levels_all(cb, model, lane, lvs, W, ctab, pf); pf.mark2(19); W.cat0 = -1; W.nz0 = 0; W.nzac = 0; W.nzdc = 0; W.ldc = false; };
+        CabLv W = { -1, 0u, 0u, 0u, false, CAB_MAP8_OFF };
+        auto flush_levels = [&]() { pf.mark2(18); cab_levels_all(cb, model, lane, lvs, W, ctab, pf); pf.mark2(19); W.cat0 = -1; W.nz0 = 0; W.nzac = 0; W.nzdc = 0; W.ldc = false; W.map8 = CAB_MAP8_OFF; };
         auto blocks = [&](auto cat_tag, int shift, int nblk, auto coef_of, auto inc_of, auto coded) {
             constexpr int CAT = decltype(cat_tag)::value;
             static_assert(CAT == 0 || CAT == 3, "the DC categories");
@@ -812,11 +833,7 @@ __device__ __forceinline__ unsigned long long cab_mb(Cab &cb, uint32_t model, in
         } else if (in.t8) {
             // (part mode: only the part's 8x8 blocks — pm_b1 < 0: one block)
             const int pmask = in.pm ? (1 << in.pm_b0) | (in.pm_b1 >= 0 ? 1 << in.pm_b1 : 0) : 15;
-            int st = cb.r8 & 255;
-            for (int i8 = 0; i8 < 4; i8++)
-                if (((in.cbp_luma & pmask) >> i8) & 1) cab_block8(cb, st, model, lane, (int)lvs[(i8 * 4 + (lane & 3)) * 16 + (lane >> 2)], in.size);
-            cb.r8 = (uint32_t)st;
-            W.cat0 = 5; W.nz0 = (unsigned)(in.cbp_luma & pmask);
+            W.cat0 = 5; W.nz0 = (unsigned)(in.cbp_luma & pmask); W.map8 = in.size ? CAB_MAP8_SIZE : CAB_MAP8_STREAM;          // (maps and levels: cab_levels_all)
         } else {
             unsigned coded = ((in.cbp_luma & 1) ? 0x000fu : 0) | ((in.cbp_luma & 2) ? 0x00f0u : 0) | ((in.cbp_luma & 4) ? 0x0f00u : 0) | ((in.cbp_luma & 8) ? 0xf000u : 0);
             if (in.pm == 1) coded &= (0xfu << (4 * in.pm_b0)) | (in.pm_b1 >= 0 ? 0xfu << (4 * in.pm_b1) : 0u);

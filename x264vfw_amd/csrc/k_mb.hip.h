@@ -93,6 +93,17 @@ struct Prof {
     // a second, nested clock (the phases' clock t keeps running): begin2 .. mark2
     __device__ __forceinline__ void begin2() { t2 = __builtin_readcyclecounter(); }
     __device__ __forceinline__ void mark2(int i) { const unsigned long long n = __builtin_readcyclecounter(); acc[i] += n - t2; t2 = n; }
+    // inside the CABAC pricing's residual walk: a second count in the upper half of a count's slot (16, 20, 21, 29: tools/mb_prof.py takes the halves apart), and a
+    // third clock for slots 22 / 23, which belong to the intra split in -DMB_PROF_INTRA builds
+    __device__ __forceinline__ void count_hi(int i) { acc[i] += 1ull << 32; }
+    unsigned long long t3;
+#ifndef MB_PROF_INTRA
+    __device__ __forceinline__ void begin3() { t3 = __builtin_readcyclecounter(); }
+    __device__ __forceinline__ void mark3(int i) { acc[i] += __builtin_readcyclecounter() - t3; }
+#else
+    __device__ __forceinline__ void begin3() {}
+    __device__ __forceinline__ void mark3(int) {}
+#endif
 };
 #else
 struct Prof {
@@ -103,6 +114,9 @@ struct Prof {
     __device__ __forceinline__ void count(int, unsigned long long) {}
     __device__ __forceinline__ void begin2() {}
     __device__ __forceinline__ void mark2(int) {}
+    __device__ __forceinline__ void count_hi(int) {}
+    __device__ __forceinline__ void begin3() {}
+    __device__ __forceinline__ void mark3(int) {}
 };
 #endif
 // -DMB_PROF -DMB_PROF_INTRA: the intra analysis split on the nested clock: acc[22] = cycles of its 8x8 part, acc[23] = of its 4x4 part (the 16x16 part is the intra

@@ -483,15 +483,17 @@ int x264gpu_trellis_blocks(const int16_t *d_coefs, int nblk, int cat, int qp, in
  * context registers r / r8 in and out (64 lanes each), the bits (1/256) out */
 }  // extern "C"
 namespace x264gpu {
+template <bool MAP8>          // MAP8: six values a case, the sixth the 8x8 significance-map mode (x264gpu_cabac_residual_walk)
 __global__ void k_cab_level_walk(const int16_t *lv, const int *what, const uint32_t *r_in, const uint32_t *r8_in, uint32_t *r_out, uint32_t *r8_out, int *bits, const uint32_t *ctab)
 {
+    constexpr int NW = MAP8 ? 6 : 5;
     __shared__ int16_t l[X264GPU_MB_LEVELS];
     const int i = blockIdx.x, lane = threadIdx.x;
     for (int j = lane; j < X264GPU_MB_LEVELS; j += 64) l[j] = lv[(size_t)i * X264GPU_MB_LEVELS + j];
     __syncthreads();
     Cab cb; cb.a0 = 0; cb.a1 = 0; cb.r = r_in[i * 64 + lane]; cb.r8 = r8_in[i * 64 + lane]; cb.f8 = 0; cb.f8v = 0;
     const uint32_t model = cab_model(lane);
-    CabLv W = { what[i * 5], (unsigned)what[i * 5 + 1], (unsigned)what[i * 5 + 2], (unsigned)what[i * 5 + 3], what[i * 5 + 4] != 0 };
+    CabLv W = { what[i * NW], (unsigned)what[i * NW + 1], (unsigned)what[i * NW + 2], (unsigned)what[i * NW + 3], what[i * NW + 4] != 0, MAP8 ? what[i * NW + 5] : CAB_MAP8_OFF };
     Prof pf;
     cab_levels_all(cb, model, lane, l, W, ctab, pf);
     r_out[i * 64 + lane] = cb.r; r8_out[i * 64 + lane] = cb.r8;
@@ -506,7 +508,20 @@ int x264gpu_cabac_level_walk(const int16_t *d_levels, const int32_t *d_what, int
     if (!n) return X264GPU_OK;
     const uint32_t *ctab = nullptr;
     { const int rc = x264gpu::cabac_chain_table(&ctab); if (rc != X264GPU_OK) return rc; }
-    hipLaunchKernelGGL(x264gpu::k_cab_level_walk, dim3(n), dim3(64), 0, (hipStream_t)stream, d_levels, d_what, d_r, d_r8, d_r_out, d_r8_out, d_bits, ctab);
+    hipLaunchKernelGGL(x264gpu::k_cab_level_walk<false>, dim3(n), dim3(64), 0, (hipStream_t)stream, d_levels, d_what, d_r, d_r8, d_r_out, d_r8_out, d_bits, ctab);
+    HIP_TRY(hipGetLastError());
+    return X264GPU_OK;
+}
+/* ... with the significance maps of the 8x8 luma blocks in the same walk, as cab_mb prices a macroblock's residual: d_what[6 n], the five values above and
+ * the map mode of category 5 (0: levels only, 1: the map in x264's size order — every context's bins from the last coefficient down, 2: in bitstream order);
+ * the map's contexts are lanes 0..14 (significant_coeff_flag) and 16..24 (last_significant_coeff_flag) of r8 */
+int x264gpu_cabac_residual_walk(const int16_t *d_levels, const int32_t *d_what, int n, const uint32_t *d_r, const uint32_t *d_r8, uint32_t *d_r_out, uint32_t *d_r8_out, int32_t *d_bits, void *stream)
+{
+    ARG_TRY(d_levels && d_what && d_r && d_r8 && d_r_out && d_r8_out && d_bits && n >= 0);
+    if (!n) return X264GPU_OK;
+    const uint32_t *ctab = nullptr;
+    { const int rc = x264gpu::cabac_chain_table(&ctab); if (rc != X264GPU_OK) return rc; }
+    hipLaunchKernelGGL(x264gpu::k_cab_level_walk<true>, dim3(n), dim3(64), 0, (hipStream_t)stream, d_levels, d_what, d_r, d_r8, d_r_out, d_r8_out, d_bits, ctab);
     HIP_TRY(hipGetLastError());
     return X264GPU_OK;
 }

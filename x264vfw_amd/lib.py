@@ -151,6 +151,7 @@ _SIGS = {
     "x264gpu_nr_update": (_i, [_vp, _vp, _vp, _i, _i, _vp]),
     "x264gpu_denoise_blocks": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
     "x264gpu_cabac_level_walk": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "x264gpu_cabac_residual_walk": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "x264gpu_cabac_bins_walk": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "x264gpu_encoder_deblock_pictures": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "x264gpu_get_device": (_i, [_vp]),
