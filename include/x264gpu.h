@@ -444,6 +444,15 @@ int  x264gpu_encoder_set_lowres_mvs1(x264gpu_encoder *enc, const int16_t *d_mvs)
 /* tests: the 460 CABAC context variables ((pStateIdx << 1) | valMPS) the wavefront of (stream, slice) ended the last picture with (RD sessions
  * with cabac: x264 prices candidates on the states the finished macroblocks left, [x264-upstream] encoder/rdo.c) */
 int  x264gpu_encoder_cabac_states(x264gpu_encoder *enc, int stream, int slice, uint8_t *out460);
+/* tests: the load balance of the lock-step batch (csrc/encoder.hip k_balance).  From 512 streams up the macroblock loop codes stream d_perm[n] in workgroup n:
+ * the streams ranked by (d_wtime[stream] descending, stream ascending), the first half = (streams + 1) / 2 ranks in that order, the others dealt backwards
+ * behind them (rank r at half + streams - 1 - r).  x264gpu_balance_perm queues exactly the launch the encoder queues (one workgroup of 1024 threads) on
+ * `stream`; EINVAL for streams < 1 or > 8192 (above that the encoder codes in identity order). */
+int  x264gpu_balance_perm(const unsigned *d_wtime, int streams, int *d_perm, void *stream);
+/* ... and the order the last picture through this launch context was coded in: returns cfg.streams and fills h_perm[workgroup] = stream when it ran permuted,
+ * returns 0 (h_perm untouched) when it ran in identity order: the first picture of its kind (I, P, B reference, B), fewer than 512 streams, slices > 1,
+ * X264GPU_NO_BALANCE set when the encoder was created.  Waits for the stream of that picture.  Negative: an error. */
+int  x264gpu_encoder_last_perm(x264gpu_encoder *enc, int *h_perm);
 
 /* ---- the lookahead's frame costs in x264's structure: x264_slicetype_frame_cost(p0, p1, b) for ANY triple of pictures held in the lookahead
  * ([x264-upstream] encoder/slicetype.c slicetype_frame_cost / slicetype_slice_cost / slicetype_mb_cost, behind codec.c:1693) — I, P and B

@@ -64,6 +64,7 @@ struct x264gpu_encoder {
     uint8_t *amvd = nullptr;             // CABAC RD: |mvd| of every 8x8 block of the picture being coded
     uint32_t *cab_out = nullptr;         // ... and the context variables every slice's wavefront ended with: [stream][slice][4][64] (tests; layout: cabac_layout.hip.h cab_locate)
     int *perm = nullptr; unsigned *wtime = nullptr; bool wt_valid[4] = { false, false, false, false };      // load balance: EncK.perm / wtime, one history per picture kind (I, P, B reference, B)
+    bool last_permuted = false;          // the last encode_core call set EncK.perm (x264gpu_encoder_last_perm)
     int *sl_stat = nullptr, *sl_rerun = nullptr;     // --slices N: per (stream, slice) intra statistics of the speculative slice passes (EncK.sl_stat)
     unsigned long long *prof = nullptr;  // MB_PROF builds: phase counters of the last macroblock-loop launch
     int *wf_progress = nullptr;          // [streams][2][WFG_ROWS] row counters of the multi-workgroup wavefront kernels
@@ -467,7 +468,7 @@ __global__ void k_col_from_records(EncK k)
 static int encode_core(x264gpu_encoder *e, const uint8_t *d_i420, const x264gpu_pic &pic, x264gpu_mb *d_mb, int16_t *d_levels, hipStream_t st)
 {
     int slice_type = pic.slice_type;
-    e->last_stream = st;
+    e->last_stream = st; e->last_permuted = false;
     if (slice_type == X264GPU_SLICE_I_NONIDR) slice_type = X264GPU_SLICE_I;            // same kernels; only the DPB handling differs
     const bool bslice = slice_type == X264GPU_SLICE_B;
     ARG_TRY(pic.dst >= 0 && pic.dst < e->slots && pic.qp >= 0 && pic.qp <= 51);
@@ -576,6 +577,7 @@ static int encode_core(x264gpu_encoder *e, const uint8_t *d_i420, const x264gpu_
         k.perm = nullptr; k.wtime = e->wtime ? e->wtime + (size_t)kind * S : nullptr;
         if (e->perm && e->wt_valid[kind] && k.slices <= 1 && S <= 8192) { hipLaunchKernelGGL(k_balance, dim3(1), dim3(1024), 0, st, k.wtime, e->perm, S); k.perm = e->perm; }
         if (k.wtime) e->wt_valid[kind] = true;
+        e->last_permuted = k.perm != nullptr;
     }
     k.sl_stat = slice_type != X264GPU_SLICE_I && e->sl_stat ? e->sl_stat + (size_t)(!bslice ? 0 : pic.keep ? 1 : 2) * S * (size_t)e->cfg.slices * 4 : nullptr;      // the first guess: the last picture of the same kind
     k.sl_rerun = e->sl_rerun; k.sl_pass = 0;
@@ -744,6 +746,25 @@ int x264gpu_encoder_direct_scores(x264gpu_encoder *e, int *h_scores)
         for (int sl = 0; sl < nsl; sl++) { h_scores[2 * s] += tmp[((size_t)s * nsl + sl) * 2]; h_scores[2 * s + 1] += tmp[((size_t)s * nsl + sl) * 2 + 1]; }
     }
     return X264GPU_OK;
+}
+
+// tests: k_balance as encode_core launches it
+int x264gpu_balance_perm(const unsigned *d_wtime, int streams, int *d_perm, void *stream)
+{
+    ARG_TRY(d_wtime && d_perm && streams >= 1 && streams <= 8192);
+    hipLaunchKernelGGL(k_balance, dim3(1), dim3(1024), 0, (hipStream_t)stream, d_wtime, d_perm, streams);
+    HIP_TRY(hipGetLastError());
+    return X264GPU_OK;
+}
+
+// tests: the workgroup -> stream order of the last picture (0: identity order; synchronises with the device)
+int x264gpu_encoder_last_perm(x264gpu_encoder *e, int *h_perm)
+{
+    ARG_TRY(e && h_perm);
+    if (!e->last_permuted) return 0;
+    HIP_TRY(hipStreamSynchronize(e->last_stream));
+    HIP_TRY(hipMemcpy(h_perm, e->perm, (size_t)e->cfg.streams * sizeof(int), hipMemcpyDeviceToHost));
+    return e->cfg.streams;
 }
 
 }  // extern "C"

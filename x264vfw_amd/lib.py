@@ -153,6 +153,8 @@ _SIGS = {
     "x264gpu_cabac_level_walk": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "x264gpu_cabac_residual_walk": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "x264gpu_cabac_bins_walk": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "x264gpu_balance_perm": (_i, [_vp, _i, _vp, _vp]),
+    "x264gpu_encoder_last_perm": (_i, [_vp, _vp]),
     "x264gpu_encoder_deblock_pictures": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "x264gpu_get_device": (_i, [_vp]),
     "x264gpu_lookahead_create": (_i, [C.POINTER(_vp), _i, _i, _i, _i, _i]),
