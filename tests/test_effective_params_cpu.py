@@ -8,7 +8,10 @@ import sys
 
 import pytest
 
+import settings_sessions
+
 HERE = os.path.dirname(os.path.abspath(__file__))
+_GOLD = None
 
 X264_ANALYSE_I4x4, X264_ANALYSE_I8x8, X264_ANALYSE_PSUB16x16, X264_ANALYSE_PSUB8x8, X264_ANALYSE_BSUB16x16 = 0x0001, 0x0002, 0x0010, 0x0020, 0x0100
 X264_RC_CQP, X264_RC_CRF, X264_RC_ABR = 0, 1, 2
@@ -28,7 +31,7 @@ PRESET = {
     "veryslow": dict(refs=16, me="umh", subme=10, trellis=2, p4x4=True),
     "placebo": dict(refs=16, me="tesa", subme=11, trellis=2, p4x4=True),
 }
-# the documented downgrades of this path (INTEGRATION.md "what a session runs"; host/encoder.cpp x264_encoder_open): ref > 5 -> 5, subme > 9 -> 9,
+# the documented downgrades of this path (INTEGRATION.md "what a session runs"; host/settings.cpp Settings::toolset): ref > 5 -> 5, subme > 9 -> 9,
 # tesa -> esa (and RD refinement needs hex / umh: subme 7 there), p4x4 off, trellis needs CABAC + subme >= 6
 def expected(name):
     e = dict(PRESET[name])
@@ -78,6 +81,21 @@ def test_second_pass_without_statistics_support_keeps_its_rate_control(tmp_path)
     # ... and the first pass likewise
     info = _session(tmp_path, 3, ["log=1", "bitrate=300", "pass=1", "stats=" + st, "bframes=0", "weightp=0", "keyint=8", "scenecut=0", "rc-lookahead=0", "no-mbtree"])
     assert info["rc_method"] == X264_RC_ABR and info["stat_write"] == 0, info
+
+
+@pytest.mark.parametrize("name", sorted(settings_sessions.SESSIONS))
+def test_sessions_settle_as_the_parent_did(tmp_path, name):
+    """tests/golden/settings_parent_sessions.json: tests/stub/run_host_calls.py's line for every row of settings_sessions.SESSIONS — every x264_encoder_encode's return
+    value, x264_encoder_delayed_frames after it, the log (level, text, order), the stream's and the metadata's hashes, the parameters reported back and the pictures
+    in flight — recorded with the stand-in build of the commit before the open rules became host/settings.cpp.  A row per rule, both ways where it has two, the
+    environment's say included"""
+    global _GOLD
+    if _GOLD is None:
+        _GOLD = json.load(open(os.path.join(HERE, "golden", "settings_parent_sessions.json")))
+        assert sorted(_GOLD) == sorted(settings_sessions.SESSIONS)
+    got = settings_sessions.run(name, str(tmp_path))
+    for key in settings_sessions.KEYS:
+        assert got[key] == _GOLD[name][key], (name, key, got[key], _GOLD[name][key])
 
 
 def test_bench_refuses_a_library_override():

@@ -14,6 +14,7 @@
 #include "mbtreestats.hpp"
 #include "ratecontrol.hpp"
 #include "slicetype.hpp"
+#include "settings.hpp"
 #include <limits.h>
 #include <math.h>
 #include <stdarg.h>
@@ -34,12 +35,11 @@ using namespace x264host;
 struct x264_t {
     x264_param_t param;
     std::string stat_in, stat_out;
+    // host/settings.hpp: what the session really runs — the effective parameters' constants (picture structure, session mode, quantisers, profile and level, lookahead
+    // window, pictures in flight).  x264_encoder_open settles them once, before anything is created; everything else reads them through `set`
+    Settings settled_at_open;
+    const Settings &set = settled_at_open;
     x264gpu_encoder *gpu = nullptr;
-    int mbw = 0, mbh = 0, nmb = 0;
-    int qp_i = 23, qp_p = 23, pic_init_qp = 26;
-    int keyint = 250;
-    int log2_max_frame_num = 8;
-    int level_idc = 40, profile_idc = 66;
     int frame_no = 0;            // frames submitted
     int frames_since_idr = 0;
     int frame_num = 0;
@@ -59,65 +59,48 @@ struct x264_t {
     //      its host copies (two: the pipelined I / P session downloads one picture's while the one before is coded) ----
     Quality ql;
     x264gpu_quality *d_q = nullptr, hq[2] = {};
-    int cqo_without_psy_trellis = 0;     // the chroma quantiser offset as it is without psy-trellis' share (what remains when psy-trellis gives way to nr, open_quantisers)
     NoiseReduction nr;                   // host/noisereduction.hpp: --nr — the session's state on the device, moved on behind every accepted picture
     MbTreeStats tstats;                  // host/mbtreestats.hpp: the macroblock-tree statistics file of a 2-pass encode (X264GPU_MBTREE_STATS=1), written or read
     const float *last_offsets = nullptr; // device: the per-macroblock quantiser offsets of the picture handed back last (x264host_last_mb_qp_offsets; nullptr: none)
     // ---- lookahead-driven decisions (threads 1 only): scenecut and CRF, both fed by x264gpu_lookahead_frame_cost ----
     x264gpu_lookahead *la = nullptr;
     int32_t *d_la = nullptr;             // device: the four sums of the last picture
-    int keyint_min = 25;
     RateControl rc;                      // host/ratecontrol.hpp: which rate control the session runs, every picture's quantiser
-    // ---- VBV (--vbv-maxrate / --vbv-bufsize; open_vbv validates them): such a session runs serially on the DPB model; a picture whose coded size would under-run the
+    // ---- VBV (--vbv-maxrate / --vbv-bufsize; Settings validates them: set.vbv, set.hrd): such a session runs serially on the DPB model; a picture whose coded size would under-run the
     //      buffer is coded again at a higher quantiser (x264 re-quantises row by row while the picture is coded: the entropy coder runs behind the device here) ----
-    bool vbv = false;
     int minigop_b = 0;                   // B pictures of the mini-GOP being coded (x264 frame->i_bframes)
     // x264host_last_vbv: the picture whose NAL units the last call returned
     struct VbvInfo { double fill_before = 0, fill_after = 0, qp_novbv = 0, qp_clipped = 0, frame_size_planned = 0, qp_final = 0; long overhead_bits = 0; int attempts = 0, filler = 0; bool valid = false; RateControl::Planned planned; } last_vbv;
-    // --nal-hrd: the HRD in the VUI, buffering-period and picture-timing SEI messages (Annex C / D / E)
-    HrdParams hrd;
     long hrd_pics_since_bp = 0;          // coded pictures since the last buffering period (cpb_removal_delay counts them, two clock ticks each)
     double t_b[5] = { 0, 0, 0, 0, 0 };          // ... sessions on the DPB model: slice-type analysis, GPU hot path, download, entropy coding, pictures
     double t_phase[6] = { 0, 0, 0, 0, 0, 0 };   // X264GPU_HOST_TIMING=1: seconds in copy-in, upload + lookahead, GPU, download, entropy coding, calls
     // ---- lookahead queue (threads 1): pictures wait here rc-lookahead deep when the macroblock-tree needs to see what follows them ----
     struct QEntry { int64_t pts; int slot; int type; int scenecut; int32_t costs[4]; x264_image_t img; int qp; int buf; bool launched; float qpm = 0.f; double qpf = 0; };      // type: 0 P, 1 I, 2 IDR; qpm: the float quantiser handed to the device (0: none), qpf: the rate control's; qp / buf / launched: set by gpu_stage
     std::deque<QEntry> queue;
-    int L = 0, Q = 1;                    // pictures held back; ring slots (L + 1)
     std::vector<uint8_t *> q_raw;        // device: source pictures (slot 0 is d_in when nothing is held back: zero-copy input)
     std::vector<int32_t *> q_info;       // device: lookahead block records per slot
     void *q_block[4] = { nullptr, nullptr, nullptr, nullptr };      // device: the blocks the queue's per-slot arrays are cut from (raw pictures, block records, AQ offsets, tree offsets)
     std::vector<float *> q_aq;           // device: AQ offsets per slot (x264 f_qp_offset_aq, single floats)
     float *d_tree = nullptr;             // device: macroblock-tree quantiser offsets of the picture being coded
     long la_count = 0; int la_gop = 0;   // pictures seen by the lookahead; distance from the last IDR at lookahead time
-    bool mbtree = false; float aq_strength = 0.f, tree_strength = 0.f;      // x264_adaptive_quant_frame's strength (mode 1: aq-strength * 1.0397f; 2 / 3: aq-strength), macroblock_tree_finish's 5.0f * (1.0f - qcomp)
-    int aq_mode = 0;                     // --aq-mode (1 variance, 2 auto-variance, 3 auto-variance biased); modes 2 / 3 always arrive as offsets computed when the picture comes in
-    int cavlc_threads = 1;               // row bands of a slice coded in parallel (threads 1 sessions; GOP-parallel ones use a thread per GOP)
-    // ---- pipelined threads-1 sessions (CRF with pictures held back anyway): the GPU stage of picture n+1 runs in a helper thread while
+    // ---- pipelined threads-1 sessions (set.pipeline: CRF with pictures held back anyway): the GPU stage of picture n+1 runs in a helper thread while
     //      the calling thread entropy-codes picture n; every picture is handed back one call later than without it ----
-    bool pipeline = false;
     std::thread gpu_thread;
     int gpu_rc = 0;                      // result of the GPU stage in flight
     int device = 0;
     int last_qp = 0, last_scenecut = 0;  // diagnostics: quantiser and scenecut flag of the last coded picture
     float last_qpm = 0.f;                // ... and its float quantiser as the device got it (x264 rc->qpm; 0 = the integer one)
     int32_t last_costs[4] = { 0, 0, 0, 0 };
-    int G = 1;                    // --threads G: GOP slots (1: none); G > 1 sessions run through `gops` alone
-    GopSlots gops;                // host/gopslots.hpp: G closed GOPs of the stream in lock-step, dealt to the visible devices
-    // X264GPU_GOP_SLOTS_RC=1, a CRF session with B pictures under --threads G: the session plans every picture as a --threads 1 session does (lookahead, slice types,
+    GopSlots gops;                // host/gopslots.hpp: set.G > 1 sessions run through it alone — G closed GOPs of the stream in lock-step, dealt to the visible devices
+    // set.slots_rc (X264GPU_GOP_SLOTS_RC=1, a CRF session with B pictures under --threads G): the session plans every picture as a --threads 1 session does (lookahead, slice types,
     // its own DPB model, RateControl::start — bmode_plan) and hands it to the slots instead of coding it; plan_count: pictures planned so far (coding order)
-    bool slots_rc = false; long plan_count = 0;
-    int slices = 1;               // x264 slice threads: slices per picture (own wavefront + own NAL each)
-    int slices_plain = 0;         // ... or x264 --slices N: the same split, filtered across the boundaries, up to one slice per macroblock row
+    long plan_count = 0;
     bool failed = false;                 // a GPU call failed; the session only returns errors from now on
     std::string gpu_err;                 // threads 1, pipelined: the helper thread's x264gpu_last_error() text (that buffer is thread-local)
     std::vector<x264gpu_mb> h_mb2;       // pipelined sessions: second download buffers (one picture's land while the one before is coded)
     std::vector<int16_t> h_lv2;
     // ---- sessions with B pictures (threads 1; x264 --bframes N --b-pyramid): the picture types and the coding order come from host/slicetype.hpp, the DPB, the
     //      reference lists and the slice header's share of them from host/dpb.hpp ----
-    int bframes = 0, bpyramid = 0, log2_max_poc_lsb = 0;
-    // dpbmode: the session runs on the DPB model (host/dpb.hpp) and x264gpu_encode_pictures — every session with B pictures, and sessions
-    // without them that use --weightp 2 (whose duplicate references need explicit lists); weightp: the effective --weightp (0 or 2)
-    bool dpbmode = false; int weightp = 0;
     Dpb dpb;
     SliceType slicetype;                 // the display-order and coding-order queues, every picture's type
     std::vector<float *> q_tree;         // device, per queue slot: the quantiser offsets the macroblock-tree left with the picture (AQ offsets until it ran)
@@ -143,12 +126,12 @@ struct x264_t {
                      const int16_t *d_mvs[2] = { nullptr, nullptr };          // the lookahead's vectors towards reference 0 of each list (nullptr: none)
                      int ctx = 0; unsigned slots_used = 0; bool last_minigop_b = false; };
     void *ev_la = nullptr;               // the default stream's position when a picture is issued: its upload, offsets and lowres vectors are complete behind it
-    std::vector<LaunchCtx> lctx; std::deque<PicPlan> fl; int inflight = 1; int slot_writer[8] = { -1, -1, -1, -1, -1, -1, -1, -1 }; int last_retired_slot = -1;
+    std::vector<LaunchCtx> lctx; std::deque<PicPlan> fl; int slot_writer[8] = { -1, -1, -1, -1, -1, -1, -1, -1 }; int last_retired_slot = -1;
     std::vector<int64_t> all_pts;        // every pts seen, in display order (the dts delay line)
     long coded_count = 0;
-    // --direct temporal / auto (x264 h->stat.i_direct_score, frame->i_poc_l0ref0): 1 spatial, 2 temporal, 3 auto; the running skip-probe counts of
+    // --direct temporal / auto (set.direct_mode; x264 h->stat.i_direct_score, frame->i_poc_l0ref0): the running skip-probe counts of
     // temporal [0] / spatial [1] prediction; the POC behind reference 0 of list 0 of every kept picture (INT_MIN: it had none)
-    int direct_mode = 1, direct_score[2] = { 0, 0 }, slot_l0ref0poc[8] = { 0 };
+    int direct_score[2] = { 0, 0 }, slot_l0ref0poc[8] = { 0 };
     char last_direct_char = '-';
 };
 
@@ -169,42 +152,31 @@ static int cavlc_threads_default(int dflt)
     return clampi(e ? atoi(e) : dflt, 1, 64);
 }
 
-static int pick_level(const x264_param_t *p, int mbs, int refs)
-{
-    double fps = p->i_fps_den ? (double)p->i_fps_num / p->i_fps_den : 25.0;
-    for (int i = 0; x264_levels[i].level_idc; i++) {
-        const x264_level_t &l = x264_levels[i];
-        if (l.level_idc == 9) continue;
-        if (l.frame_size >= mbs && l.mbps >= (int)(mbs * fps) && l.dpb >= mbs * refs) return l.level_idc;
-    }
-    return 62;
-}
-
 static const char kSeiText[] = "x264vfw-mi355x hot path r1 - H.264/MPEG-4 AVC codec - options: cavlc ip p8x8 i4x4 i8x8 8x8dct hex ref<=4 cqp";
 
 static SpsParams make_sps(const x264_t *h)
 {
     const x264_param_t &p = h->param;
     SpsParams s = {};
-    s.profile_idc = h->profile_idc; s.level_idc = h->level_idc; s.sps_id = p.i_sps_id;
-    s.mbw = h->mbw; s.mbh = h->mbh; s.crop_right = h->mbw * 16 - p.i_width; s.crop_bottom = h->mbh * 16 - p.i_height;
-    s.num_ref_frames = h->param.i_frame_reference; s.log2_max_frame_num = h->log2_max_frame_num;
+    s.profile_idc = h->set.profile_idc; s.level_idc = h->set.level_idc; s.sps_id = p.i_sps_id;
+    s.mbw = h->set.mbw; s.mbh = h->set.mbh; s.crop_right = h->set.mbw * 16 - p.i_width; s.crop_bottom = h->set.mbh * 16 - p.i_height;
+    s.num_ref_frames = h->param.i_frame_reference; s.log2_max_frame_num = h->set.log2_max_frame_num;
     s.sar_w = p.vui.i_sar_width; s.sar_h = p.vui.i_sar_height; s.fullrange = p.vui.b_fullrange;
     s.colorprim = p.vui.i_colorprim; s.transfer = p.vui.i_transfer; s.colmatrix = p.vui.i_colmatrix;
     s.overscan = p.vui.i_overscan; s.vidformat = p.vui.i_vidformat;
     s.num_units_in_tick = p.i_timebase_num; s.time_scale = p.i_timebase_den * 2;
-    s.constraint_set0 = h->profile_idc == 66; s.constraint_set1 = h->profile_idc <= 77;
+    s.constraint_set0 = h->set.profile_idc == 66; s.constraint_set1 = h->set.profile_idc <= 77;
     s.mv_range = h->param.analyse.i_mv_range;
-    if (h->dpbmode) { s.num_ref_frames = h->dpb.max_dpb; s.log2_max_poc_lsb = h->log2_max_poc_lsb; s.num_reorder_frames = h->dpb.num_reorder; }
-    s.hrd = h->hrd;
+    if (h->set.dpbmode) { s.num_ref_frames = h->dpb.max_dpb; s.log2_max_poc_lsb = h->set.log2_max_poc_lsb; s.num_reorder_frames = h->dpb.num_reorder; }
+    s.hrd = h->set.hrd;
     return s;
 }
 static PpsParams make_pps(const x264_t *h)
 {
-    PpsParams pp = { h->param.i_sps_id, h->param.i_sps_id, h->param.b_cabac, h->param.i_frame_reference, h->pic_init_qp, h->param.analyse.i_chroma_qp_offset,
+    PpsParams pp = { h->param.i_sps_id, h->param.i_sps_id, h->param.b_cabac, h->param.i_frame_reference, h->set.pic_init_qp, h->param.analyse.i_chroma_qp_offset,
                      h->param.analyse.b_transform_8x8 };
-    if (h->bframes && h->param.analyse.b_weighted_bipred) pp.weighted_bipred_idc = 2;
-    pp.weighted_pred = h->weightp > 0;
+    if (h->set.bframes && h->param.analyse.b_weighted_bipred) pp.weighted_bipred_idc = 2;
+    pp.weighted_pred = h->set.weightp > 0;
     return pp;
 }
 // access unit delimiter (--aud, 7.3.2.4, Table 7-5): primary_pic_type 0 = I slices only, 1 = I and P, 2 = I, P and B (what x264 writes for its three
@@ -249,11 +221,11 @@ static bool begin_access_unit(const x264_t *h, std::vector<uint8_t> &bytes, std:
     if (sets) write_sets(h, bytes, off, types, false);
     if (pic_type == PIC_IDR) {
         off.push_back(bytes.size()); types.push_back(6);
-        write_sei_buffering_period(bytes, h->hrd, p.i_sps_id, tm->initial_cpb_removal_delay, tm->initial_cpb_removal_delay_offset, annexb, bytes.empty());
+        write_sei_buffering_period(bytes, h->set.hrd, p.i_sps_id, tm->initial_cpb_removal_delay, tm->initial_cpb_removal_delay_offset, annexb, bytes.empty());
     }
     if (sets && sei) { off.push_back(bytes.size()); types.push_back(6); write_sei_version(bytes, kSeiText, annexb); }
     off.push_back(bytes.size()); types.push_back(6);
-    write_sei_pic_timing(bytes, h->hrd, tm->cpb_removal_delay, tm->dpb_output_delay, annexb, bytes.empty());
+    write_sei_pic_timing(bytes, h->set.hrd, tm->cpb_removal_delay, tm->dpb_output_delay, annexb, bytes.empty());
     return sets;
 }
 // the slices of the picture behind what the access unit holds so far, their NAL units tagged 5 (IDR) or 1
@@ -269,10 +241,10 @@ static SliceParams slice_params_base(const x264_t *h)
 {
     const x264_param_t &p = h->param;
     SliceParams sp = {};
-    sp.mbw = h->mbw; sp.mbh = h->mbh; sp.pic_init_qp = h->pic_init_qp; sp.log2_max_frame_num = h->log2_max_frame_num; sp.log2_max_poc_lsb = h->log2_max_poc_lsb;
+    sp.mbw = h->set.mbw; sp.mbh = h->set.mbh; sp.pic_init_qp = h->set.pic_init_qp; sp.log2_max_frame_num = h->set.log2_max_frame_num; sp.log2_max_poc_lsb = h->set.log2_max_poc_lsb;
     sp.pps_id = p.i_sps_id; sp.num_ref_default = p.i_frame_reference; sp.num_ref1_default = 1;
     sp.disable_deblock_idc = p.b_deblocking_filter ? 0 : 1; sp.alpha_off_div2 = p.i_deblocking_filter_alphac0; sp.beta_off_div2 = p.i_deblocking_filter_beta;
-    sp.transform8x8_mode = p.analyse.b_transform_8x8; sp.cabac = p.b_cabac; sp.slices_plain = h->slices_plain;
+    sp.transform8x8_mode = p.analyse.b_transform_8x8; sp.cabac = p.b_cabac; sp.slices_plain = h->set.slices_plain;
     return sp;
 }
 static int x264_type_of(int pic_type)
@@ -282,7 +254,7 @@ static int x264_type_of(int pic_type)
 // x264's dts of the k-th coded picture: the pts of display picture k - delay; the first `delay` ones are shifted back by the delay's duration
 static int64_t coded_dts(const x264_t *h, long k)
 {
-    const long delay = !h->bframes ? 0 : h->bpyramid ? 2 : 1;
+    const long delay = !h->set.bframes ? 0 : h->set.bpyramid ? 2 : 1;
     const size_t np = h->all_pts.size();
     if (k >= delay) return h->all_pts[(size_t)(k - delay) < np ? (size_t)(k - delay) : np - 1];
     return h->all_pts[(size_t)k < np ? (size_t)k : np - 1] - (h->all_pts[(size_t)delay < np ? (size_t)delay : np - 1] - h->all_pts[0]);
@@ -297,382 +269,18 @@ static void fill_pic_out(x264_picture_t *pic_out, int i_type, bool keyframe, int
 }
 
 extern "C" {
-// ---- x264_encoder_open, step by step (each step logs what it changes or why it fails; a failed step leaves the teardown to x264_encoder_close) ----
-static int psy_trellis_q8(const x264_param_t &p) { return p.analyse.i_trellis ? (int)(p.analyse.f_psy_trellis / 4 * 256 + 0.5f) : 0; }      // h->mb.i_psy_trellis
-static int psy_rd_q8(const x264_param_t &p) { return p.analyse.i_subpel_refine >= 6 ? (int)(p.analyse.f_psy_rd * 256.0f + 0.5f) : 0; }      // h->mb.i_psy_rd
-
-// the toolset: what this pipeline implements of the analysis options, slices and threads (reported back via x264_encoder_parameters)
-static void open_toolset(x264_t *h)
-{
-    x264_param_t &p = h->param;
-    // ---- effective parameters: what this round's pipeline implements (reported back via encoder_parameters) ----
-    // B pictures: on the device in CABAC sessions, one GOP in flight (settled below, once those are known)
-    p.i_bframe = clampi(p.i_bframe, 0, 16);
-    if (p.i_frame_reference > 5) { xlog(&p, X264_LOG_INFO, "ref %d -> 5 (DPB of the MI355X path holds up to 5 references)\n", p.i_frame_reference); p.i_frame_reference = 5; }
-    if (p.i_frame_reference < 1) p.i_frame_reference = 1;
-    p.analyse.b_mixed_references = p.analyse.b_mixed_references && p.i_frame_reference > 1;      // x264 validate_parameters
-    p.b_cabac = p.b_cabac != 0;
-    if (p.b_cabac && p.i_cabac_init_idc != 0) { xlog(&p, X264_LOG_WARNING, "cabac-idc %d: only the context tables of cabac_init_idc 0 (x264's default) are in the MI355X path: cabac-idc 0\n", p.i_cabac_init_idc); p.i_cabac_init_idc = 0; }
-    // --weightp: settled below with the B-picture settings (2 = x264's blind duplicate of reference 0 in sessions that run on the DPB model;
-    // the fade analysis that produces other weights — x264_weights_analyse, all that --weightp 1 does — is not implemented)
-    p.analyse.i_weighted_pred = clampi(p.analyse.i_weighted_pred, X264_WEIGHTP_NONE, X264_WEIGHTP_SMART); p.analyse.b_weighted_bipred = p.analyse.b_weighted_bipred != 0;
-    p.analyse.b_transform_8x8 = p.analyse.b_transform_8x8 != 0;
-    if (p.analyse.inter & X264_ANALYSE_PSUB8x8) xlog(&p, X264_LOG_WARNING, "partitions p4x4 (8x4 / 4x8 / 4x4 searches inside P_8x8) are not implemented in the MI355X path: p8x8 stays, p4x4 off\n");
-    p.analyse.inter &= X264_ANALYSE_I4x4 | X264_ANALYSE_I8x8 | X264_ANALYSE_PSUB16x16 | X264_ANALYSE_BSUB16x16; p.analyse.intra &= X264_ANALYSE_I4x4 | X264_ANALYSE_I8x8;
-    if (!p.analyse.b_transform_8x8) { p.analyse.inter &= ~X264_ANALYSE_I8x8; p.analyse.intra &= ~X264_ANALYSE_I8x8; }   // as x264 validate_parameters
-    p.analyse.i_trellis = clampi(p.analyse.i_trellis, 0, 2);          // settled below, once the sub-pel level is known
-    p.i_scenecut_threshold = clampi(p.i_scenecut_threshold, 0, 100);
-    if (p.analyse.i_me_method > X264_ME_ESA) { xlog(&p, X264_LOG_WARNING, "me tesa is not implemented in the MI355X path yet: me esa\n"); p.analyse.i_me_method = X264_ME_ESA; }
-    p.analyse.i_me_range = clampi(p.analyse.i_me_range, 4, p.analyse.i_me_method == X264_ME_UMH ? 64 : 16);     // x264 caps dia/hex at 16; esa: the LDS search window
-    // subme 6 / 7 = RD mode decision in P and I slices (x264's i_mbrd 1): on the device, with the bit counts of the session's entropy coder
-    // (CAVLC: exact; CABAC: x264's size-only coder on the slice's context states, which the device carries through the macroblock loop);
-    // 8 adds RD refinement of the chosen type's vectors and intra modes in I and P slices (i_mbrd 2: x264_me_refine_qpel_rd, intra_rd_refine; B slices
-    // analyse one level down, i.e. as at subme 7): on the device in CABAC sessions under --me hex / umh.  9 adds the refinement in B slices (per-list
-    // x264_me_refine_qpel_rd, x264_me_refine_bidir_rd, intra_rd_refine), chroma in their sub-pel costs and the deblock-aware RD costs.  10 and 11 (QP-RD,
-    // full-RD trellis) are not implemented.  The highest level whose behaviour IS implemented is reported back
-    if (p.analyse.i_subpel_refine > 9) { xlog(&p, X264_LOG_WARNING, "subme %d: QP-RD / full-RD trellis of the levels above 9 are not implemented yet: subme 9\n", p.analyse.i_subpel_refine); p.analyse.i_subpel_refine = 9; }
-    if (p.analyse.i_subpel_refine >= 8 && (!p.b_cabac || (p.analyse.i_me_method != X264_ME_HEX && p.analyse.i_me_method != X264_ME_UMH))) {
-        xlog(&p, X264_LOG_WARNING, "subme %d (RD refinement) needs CABAC and me hex / umh in the MI355X path: subme 7\n", p.analyse.i_subpel_refine); p.analyse.i_subpel_refine = 7;
-    }
-    p.analyse.i_subpel_refine = clampi(p.analyse.i_subpel_refine, 0, 9);
-    // trellis 1 = the final encode of every macroblock quantised by x264's trellis search on the slice's CABAC state: on the device where that state
-    // lives, i.e. in CABAC sessions with RD (subme >= 6); trellis 2 = also the block encodes of the intra analysis and every RD candidate
-    const int trellis_asked = p.analyse.i_trellis;
-    if (p.analyse.i_trellis && (!p.b_cabac || p.analyse.i_subpel_refine < 6)) {
-        xlog(&p, X264_LOG_WARNING, "trellis %d needs CABAC and subme >= 6 in the MI355X path (the search reads the CABAC state the device carries for RD): trellis 0\n", p.analyse.i_trellis);
-        p.analyse.i_trellis = 0;
-    }
-    NoiseReduction::check_toolset(p);          // --nr: inter residuals denoised in the macroblock loop (host/noisereduction.hpp); the toolset's share of its rules; psy-trellis gives way to it once the session's mode has passed too (open_quantisers)
-    p.analyse.b_psy = p.analyse.b_psy != 0;
-    if (!p.analyse.b_psy) { p.analyse.f_psy_rd = 0; p.analyse.f_psy_trellis = 0; }       // x264 validate_parameters
-    p.analyse.f_psy_rd = p.analyse.f_psy_rd < 0 ? 0 : p.analyse.f_psy_rd > 10 ? 10 : p.analyse.f_psy_rd;
-    // psy-trellis (--psy-rd a:b, tune film / grain / stillimage): the search's distortion term that rewards keeping the source's energy, in every luma
-    // trellis site on the device.  x264 drops it silently without psy or trellis; here it also needs what the device's psy search is built for
-    p.analyse.f_psy_trellis = p.analyse.f_psy_trellis < 0 ? 0 : p.analyse.f_psy_trellis > 10 ? 10 : p.analyse.f_psy_trellis;
-    if (!trellis_asked) p.analyse.f_psy_trellis = 0;
-    if (p.analyse.f_psy_trellis > 0) {
-        const char *missing = !p.b_cabac ? "CABAC" : p.analyse.i_subpel_refine < 6 ? "subme >= 6" :
-                              p.analyse.i_me_method != X264_ME_HEX && p.analyse.i_me_method != X264_ME_UMH ? "me hex / umh" : nullptr;
-        if (missing) { xlog(&p, X264_LOG_WARNING, "psy-trellis needs %s in the MI355X path (the psy search is built for CABAC trellis sessions under me hex / umh): psy-trellis 0\n", missing); p.analyse.f_psy_trellis = 0; }
-    }
-    // psy RD raises luma quality at chroma's cost, so x264 lowers the chroma quantiser offset to compensate (encoder.c, validate / mb init)
-    int eff_chroma_qp_offset = p.analyse.i_chroma_qp_offset;
-    if (psy_rd_q8(p)) eff_chroma_qp_offset -= p.analyse.f_psy_rd < 0.25f ? 1 : 2;
-    h->cqo_without_psy_trellis = clampi(eff_chroma_qp_offset, -12, 12);
-    if (psy_trellis_q8(p)) eff_chroma_qp_offset -= p.analyse.f_psy_trellis < 0.25f ? 1 : 2;
-    eff_chroma_qp_offset = clampi(eff_chroma_qp_offset, -12, 12);
-    p.analyse.i_chroma_qp_offset = eff_chroma_qp_offset;          // x264 changes the parameter in place too: the PPS carries it
-    p.analyse.b_fast_pskip = p.analyse.b_fast_pskip != 0;
-    p.analyse.b_chroma_me = p.analyse.b_chroma_me != 0;
-    if (p.b_interlaced) { xlog(&p, X264_LOG_WARNING, "interlaced coding is not implemented in the MI355X path: progressive\n"); p.b_interlaced = 0; }
-    if (p.b_constrained_intra) { xlog(&p, X264_LOG_WARNING, "constrained-intra is not implemented in the MI355X path: off\n"); p.b_constrained_intra = 0; }
-    if (p.b_intra_refresh) { xlog(&p, X264_LOG_WARNING, "intra-refresh is not implemented in the MI355X path: off\n"); p.b_intra_refresh = 0; }
-    // --sliced-threads / --tune zerolatency: i_threads is the number of slices per picture (x264 validate_parameters: at most one per four
-    // macroblock rows; auto = as many as that allows, where x264 would count host cores) and there is one GOP in flight
-    h->slices = 1;
-    if (p.b_sliced_threads) {
-        const int max_slices = (p.i_height + 15) / 16 / 4 > 1 ? (p.i_height + 15) / 16 / 4 : 1;
-        h->slices = p.i_threads <= 0 ? max_slices : p.i_threads < max_slices ? p.i_threads : max_slices;
-        if (p.i_threads > 0 && h->slices != p.i_threads) xlog(&p, X264_LOG_INFO, "sliced threads %d -> %d (four macroblock rows per slice)\n", p.i_threads, h->slices);
-        p.i_threads = 1;
-        if (h->slices < 2) p.b_sliced_threads = 0;
-        // x264 has no word for "slice threads AND several GOPs in flight"; this library can do both (slices x GOP slots wavefronts per stream).
-        // X264GPU_GOP_SLOTS=G asks for it: the --threads G mode below (fixed keyint, delay (G-1) x keyint) with every picture in slices
-        if (const char *gs = getenv("X264GPU_GOP_SLOTS")) { const int g = atoi(gs); if (g > 1) p.i_threads = g; }
-        if (p.i_slice_count > 1) xlog(&p, X264_LOG_INFO, "slices %d ignored under slice threads (%d slices)\n", p.i_slice_count, h->slices);
-        if (h->slices > 1) p.i_slice_count = 0;
-    }
-    // --slices N (x264 slices_write: slice i ends at macroblock row (mbh * (i + 1) + N / 2) / N, the split slice threads use too; validate_parameters
-    // clips N to the macroblock rows): every slice a wavefront of its own here, which is what makes one stream faster without any delay.
-    // Unlike slice threads the loop filter crosses the boundaries (disable_deblocking_filter_idc 0).
-    if (!p.b_sliced_threads && p.i_slice_count > 1) {
-        const int mbh = (p.i_height + 15) / 16;
-        p.i_slice_count = p.i_slice_count < mbh ? p.i_slice_count : mbh;
-        h->slices = p.i_slice_count; h->slices_plain = h->slices > 1;
-    } else if (!p.b_sliced_threads) p.i_slice_count = 0;
-    p.i_threads = clampi(p.i_threads, 1, 256);                 // --threads G: GOPs coded in lock-step (1 = no delay)
-}
-
-// VBV: x264 validate_parameters' rules for --vbv-maxrate / --vbv-bufsize / --vbv-init / --nal-hrd, and which sessions run it here (single-pass CRF / ABR, one
-// picture at a time on the DPB model).  Leaves the effective values in the parameters and h->vbv; runs before the picture structure is settled
-static void open_vbv(x264_t *h)
-{
-    x264_param_t &p = h->param;
-    h->vbv = false;
-    if (p.rc.i_vbv_max_bitrate > 0 || p.rc.i_vbv_buffer_size > 0) {
-        // (sessions that end up at a constant quantiser: open_quantisers maps CRF below 1 and ABR without a bitrate to it)
-        const bool cqp = p.rc.i_rc_method == X264_RC_CQP || (p.rc.i_rc_method == X264_RC_CRF && p.rc.f_rf_constant < 1.0f) || (p.rc.i_rc_method == X264_RC_ABR && p.rc.i_bitrate <= 0);
-        const char *be = getenv("X264GPU_BATCH");
-        const char *why = p.i_threads > 1 ? "threads 1 (GOP slots are coded in lock-step, before the sizes of the pictures in front of them are known)" :
-                          be && atoi(be) >= 2 ? "a session of its own (X264GPU_BATCH codes the sessions of a group in lock-step)" :
-                          p.rc.b_stat_read ? "a single pass (the second pass' VBV plan, x264's vbv_pass2, is not implemented)" : nullptr;
-        if (cqp) xlog(&p, X264_LOG_WARNING, "VBV is incompatible with constant QP, ignored.\n");
-        else if (why) xlog(&p, X264_LOG_WARNING, "VBV (vbv-maxrate / vbv-bufsize) needs %s in the MI355X path: unconstrained\n", why);
-        else {
-            const bool is_abr = p.rc.i_rc_method == X264_RC_ABR;
-            if (p.rc.i_vbv_buffer_size > 0 && p.rc.i_vbv_max_bitrate <= 0) {
-                if (is_abr) { xlog(&p, X264_LOG_WARNING, "VBV maxrate unspecified, assuming CBR\n"); p.rc.i_vbv_max_bitrate = p.rc.i_bitrate; }
-                else { xlog(&p, X264_LOG_WARNING, "VBV bufsize set but maxrate unspecified, ignored\n"); p.rc.i_vbv_buffer_size = 0; }
-            } else if (p.rc.i_vbv_max_bitrate > 0 && p.rc.i_vbv_buffer_size <= 0) { xlog(&p, X264_LOG_WARNING, "VBV maxrate specified, but no bufsize, ignored\n"); p.rc.i_vbv_max_bitrate = 0; }
-            if (p.rc.i_vbv_max_bitrate > 0 && p.rc.i_vbv_buffer_size > 0) {
-                if (is_abr && p.rc.i_vbv_max_bitrate < p.rc.i_bitrate) { xlog(&p, X264_LOG_WARNING, "max bitrate less than average bitrate, assuming CBR\n"); p.rc.i_bitrate = p.rc.i_vbv_max_bitrate; }
-                // x264_ratecontrol_init_reconfigurable: at least one picture's worth of buffer; --vbv-init above 1 is kbit, and the buffer starts with at least one picture's arrival
-                const double fps = p.i_fps_num ? (double)p.i_fps_num / p.i_fps_den : 25.0;
-                if (p.rc.i_vbv_buffer_size < (int)(p.rc.i_vbv_max_bitrate / fps)) {
-                    p.rc.i_vbv_buffer_size = (int)(p.rc.i_vbv_max_bitrate / fps);
-                    xlog(&p, X264_LOG_WARNING, "VBV buffer size cannot be smaller than one frame, using %d kbit\n", p.rc.i_vbv_buffer_size);
-                }
-                auto clipf = [](float v, float lo, float hi) { return v < lo ? lo : v > hi ? hi : v; };
-                if (p.rc.f_vbv_buffer_init > 1.f) p.rc.f_vbv_buffer_init = clipf(p.rc.f_vbv_buffer_init / p.rc.i_vbv_buffer_size, 0.f, 1.f);
-                const float one = (float)((p.rc.i_vbv_max_bitrate * 1000.0 / fps) / (p.rc.i_vbv_buffer_size * 1000.0));
-                p.rc.f_vbv_buffer_init = clipf(p.rc.f_vbv_buffer_init > one ? p.rc.f_vbv_buffer_init : one, 0.f, 1.f);
-                h->vbv = true;
-            }
-        }
-    }
-    if (!h->vbv) { p.rc.i_vbv_max_bitrate = 0; p.rc.i_vbv_buffer_size = 0; }
-    p.i_nal_hrd = clampi(p.i_nal_hrd, X264_NAL_HRD_NONE, X264_NAL_HRD_CBR);
-    if (p.i_nal_hrd && !h->vbv) { xlog(&p, X264_LOG_WARNING, "NAL HRD parameters require VBV parameters\n"); p.i_nal_hrd = X264_NAL_HRD_NONE; }
-    if (p.i_nal_hrd == X264_NAL_HRD_CBR && (p.rc.i_rc_method != X264_RC_ABR || p.rc.i_vbv_max_bitrate != p.rc.i_bitrate)) {
-        xlog(&p, X264_LOG_WARNING, "CBR HRD requires constant bitrate\n"); p.i_nal_hrd = X264_NAL_HRD_VBR;
-    }
-}
-
-// picture structure: B pictures, --weightp, and whether the session runs on the DPB model or in a batch
-static void open_modes(x264_t *h)
-{
-    x264_param_t &p = h->param;
-    if (p.i_bframe) {
-        // (below --subme 7 x264 analyses B slices without RD: k_mb_b.inc's NORD flow; from 7 up their RD decisions count CABAC sizes or CAVLC bits)
-        // (--threads G: closed GOPs in lock-step carry B pictures when every GOP has the same picture structure and quantisers: constant quantiser)
-        const char *why = (p.i_threads > 1 && p.rc.i_rc_method != X264_RC_CQP && !h->slots_rc) ? "threads 1, or a constant quantiser with --threads G" : p.i_keyint_max < 2 ? "keyint > 1" :
-                          (p.rc.i_rc_method == X264_RC_ABR && p.rc.i_bitrate <= 0) ? "constant-quantiser, CRF or ABR rate control with a bitrate" : nullptr;
-        if (why) { xlog(&p, X264_LOG_WARNING, "B-frames need %s in the MI355X path: bframes 0\n", why); p.i_bframe = 0; }
-    }
-    if (p.i_bframe && p.i_threads > 1) {
-        if (p.i_bframe_adaptive) { xlog(&p, X264_LOG_INFO, "b-adapt needs threads 1 (GOPs in lock-step have a fixed structure): b-adapt 0\n"); p.i_bframe_adaptive = 0; }
-        if (p.analyse.i_direct_mv_pred == 3) { xlog(&p, X264_LOG_INFO, "direct auto needs threads 1 (its choice follows the pictures coded before, across GOPs): spatial\n"); p.analyse.i_direct_mv_pred = 1; }
-    }
-    if (p.i_bframe) {
-        p.i_bframe_adaptive = clampi(p.i_bframe_adaptive, 0, 2);
-        if (p.i_bframe_pyramid == 1) { xlog(&p, X264_LOG_INFO, "b-pyramid strict -> normal\n"); p.i_bframe_pyramid = 2; }
-        if (p.i_bframe < 2) p.i_bframe_pyramid = 0;
-        if (p.b_open_gop) { xlog(&p, X264_LOG_WARNING, "open-gop is not implemented in the MI355X path: closed GOPs\n"); p.b_open_gop = 0; }
-        if (p.analyse.i_direct_mv_pred < 1 || p.analyse.i_direct_mv_pred > 3) { xlog(&p, X264_LOG_INFO, "direct %d -> spatial (B macroblocks without direct prediction are not in the MI355X path)\n", p.analyse.i_direct_mv_pred); p.analyse.i_direct_mv_pred = 1; }
-        // (temporal direct prediction is a flag a stream of the group's encoder; auto's choice needs the probe counts read back behind every B picture, which would serialise queued rounds)
-        if (p.analyse.i_direct_mv_pred == 3 && getenv("X264GPU_BATCH")) { xlog(&p, X264_LOG_INFO, "direct auto: not in cross-session batches (its choice waits for every B picture's probe counts): spatial\n"); p.analyse.i_direct_mv_pred = 1; }
-    } else { p.i_bframe_pyramid = 0; p.analyse.b_weighted_bipred = 0; }
-    h->bframes = p.i_bframe; h->bpyramid = p.i_bframe_pyramid ? 1 : 0;
-    h->direct_mode = p.i_bframe ? p.analyse.i_direct_mv_pred : 1;
-    if (p.i_keyint_max <= 0) p.i_keyint_max = 1;
-    if (p.analyse.i_weighted_pred == X264_WEIGHTP_SIMPLE && !h->bframes) { xlog(&p, X264_LOG_INFO, "weightp 1 (weights for fades, no duplicate references) runs in sessions with B pictures only: weightp 0\n"); p.analyse.i_weighted_pred = X264_WEIGHTP_NONE; }
-    if (p.analyse.i_weighted_pred == X264_WEIGHTP_SMART && !h->bframes) {
-        // without B pictures the session can still run on the DPB model, if nothing of the other path is asked for
-        const bool tree = p.rc.b_mb_tree && p.rc.i_rc_method != X264_RC_CQP && p.rc.i_lookahead > 0;
-        const char *why = p.i_threads > 1 ? "threads 1" : tree ? "no mbtree" :
-                          (p.rc.i_rc_method == X264_RC_ABR && p.rc.i_bitrate <= 0) ? "constant-quantiser, CRF or ABR rate control with a bitrate" : p.i_keyint_max < 2 ? "keyint > 1" : nullptr;
-        if (why) { xlog(&p, X264_LOG_WARNING, "weightp 2 without B-frames needs %s in the MI355X path: weightp 0\n", why); p.analyse.i_weighted_pred = X264_WEIGHTP_NONE; }
-    }
-    if (p.analyse.i_weighted_pred == X264_WEIGHTP_SMART && p.i_frame_reference < 2) p.analyse.i_weighted_pred = X264_WEIGHTP_NONE;      // a duplicate needs two references (x264: never placed)
-    h->weightp = p.analyse.i_weighted_pred;
-    h->dpbmode = h->bframes > 0 || h->weightp == X264_WEIGHTP_SMART || h->vbv;          // (VBV: the path that codes one picture at a time and can code it again)
-    if (const char *be = getenv("X264GPU_BATCH")) {
-        // cross-session batcher: this session joins (or starts) a group of N sessions coded in lock-step, if its picture structure is fixed
-        const int bn = atoi(be);
-        if (bn >= 2) {
-            // (macroblock-tree, --aq-mode 2 / 3 and --direct temporal leave every picture's type alone: the member's lookahead runs them, the group carries what it decides)
-            const char *why = p.i_threads > 1 ? "threads 1" : h->slices > 1 || p.b_sliced_threads ? "one slice per picture" : p.i_scenecut_threshold > 0 ? "scenecut 0" :
-                              (h->bframes && p.i_bframe_adaptive) ? "b-adapt 0" : p.rc.i_rc_method == X264_RC_ABR ? "constant-quantiser or CRF rate control" : nullptr;
-            if (why) xlog(&p, X264_LOG_WARNING, "X264GPU_BATCH needs %s (picture k must have the same type in every session of a batch): this session runs on its own\n", why);
-            else { h->batch.want = bn; h->dpbmode = true; }
-        }
-    }
-    if (h->dpbmode && !h->bframes) { p.rc.b_mb_tree = 0; }
-    if (h->weightp) xlog(&p, X264_LOG_INFO, "weightp %d: weights for fades from the lookahead (luma, and the chroma planes beside it)%s\n", h->weightp, h->weightp == X264_WEIGHTP_SMART ? ", duplicates of reference 0 on every P picture" : "");
-    h->keyint = p.i_keyint_max;
-}
-
-// rate control: which method the session really runs (passes of a 2-pass encode, zones, AQ, macroblock-tree), the quantisers, profile and level, the DPB model
-static void open_quantisers(x264_t *h)
-{
-    x264_param_t &p = h->param;
-    RateControl &rc = h->rc;
-    // rate control: constant QP (X264_RC_CQP, codec.c:1498-1502) and single-pass CRF without AQ / mbtree (codec.c:1504-1507, the
-    // driver's default session) when one GOP is in flight; ABR and CRF under --threads > 1 map to their nominal quantiser
-    int qp = p.rc.i_rc_method == X264_RC_CQP ? p.rc.i_qp_constant : p.rc.i_rc_method == X264_RC_CRF ? (int)(p.rc.f_rf_constant + 0.5f) : 26;
-    rc.crf = p.rc.i_rc_method == X264_RC_CRF && p.rc.f_rf_constant >= 1.0f;       // also under --threads G: its quantisers follow from the lookahead costs alone
-    // 2-pass: the second pass plans every picture's quantiser from the first pass' statistics; sessions on the DPB model (B pictures or --weightp 2)
-    rc.pass2 = p.rc.b_stat_read && p.rc.i_rc_method == X264_RC_ABR && p.rc.i_bitrate > 0 && p.i_threads <= 1 && h->dpbmode && p.rc.psz_stat_in && !getenv("X264GPU_BATCH");
-    rc.pass1 = p.rc.b_stat_write && !p.rc.b_stat_read && p.i_threads <= 1 && h->dpbmode && p.rc.psz_stat_out && !getenv("X264GPU_BATCH");
-    if ((p.rc.b_stat_read && !rc.pass2) || (p.rc.b_stat_write && !p.rc.b_stat_read && !rc.pass1)) {
-        // a pass whose statistics cannot be honoured keeps its rate control: it runs as the single-pass session of the same method (ABR at i_bitrate
-        // for the driver's multipass encodes, codec.c:1509-1527), as every pass did before 2-pass existed here — not at a constant quantiser
-        xlog(&p, X264_LOG_WARNING, "2-pass statistics need threads 1 and B-frames or weightp 2 (the DPB-model path) in the MI355X path: this pass runs as a single pass without them\n");
-        if (!rc.pass2) p.rc.b_stat_read = 0;
-        if (!rc.pass1) p.rc.b_stat_write = 0;
-    }
-    rc.abr = p.rc.i_rc_method == X264_RC_ABR && p.i_threads <= 1 && p.rc.i_bitrate > 0 && !p.rc.b_stat_read;      // single pass, no VBV
-    if (p.rc.b_stat_write && p.rc.b_stat_read && !rc.pass2) xlog(&p, X264_LOG_INFO, "this pass runs without the statistics: they stay as the first pass wrote them\n");
-    if (p.rc.i_rc_method != X264_RC_CQP && !rc.by_cost() && !rc.pass2) xlog(&p, X264_LOG_WARNING, "this rate control mode is not implemented yet (ABR with --threads > 1): constant qp %d\n", qp);
-    if (qp < 1) { xlog(&p, X264_LOG_WARNING, "lossless is not supported: qp 1\n"); qp = 1; }
-    if (!rc.by_cost() && !rc.pass2) p.rc.i_rc_method = X264_RC_CQP;
-    if ((rc.pass1 || rc.pass2) && p.rc.b_mb_tree) {
-        if (!MbTreeStats::opted_in()) { xlog(&p, X264_LOG_INFO, "2-pass: the macroblock-tree statistics file is not implemented in the MI355X path: mbtree 0 in both passes\n"); p.rc.b_mb_tree = 0; }
-        else if (rc.pass2) {
-            // the second pass has no future pictures: no lookahead, no tree of its own — kept pictures take the offsets the first pass' tree left in <stats>.mbtree,
-            // the plan takes the tree's RCEQ.  The session is set up as the tree-less one (rc-lookahead 0) and reports mbtree 1 (x264_encoder_open, once every part is open).
-            // Needs what 2-pass needs (threads 1, the DPB-model path, no X264GPU_BATCH: rc.pass2 says so); VBV and zones in a second pass stay as they are
-            h->tstats.reading = rc.tree_read = h->tstats.check_read(p, p.rc.psz_stat_in, h->nmb);
-            p.rc.b_mb_tree = 0;
-        }
-        // (a first pass keeps its tree: the single-pass CRF / ABR + tree session plus the statistics; whether the tree really runs is settled below)
-    }
-    rc.parse_zones(p);
-    if (!rc.zones.empty()) xlog(&p, X264_LOG_INFO, "%d zone%s (quantiser / bitrate factor per range of pictures)\n", (int)rc.zones.size(), rc.zones.size() > 1 ? "s" : "");
-    if (!rc.zones.empty() && rc.pass2) xlog(&p, X264_LOG_WARNING, "zones are not applied to the second pass' plan in the MI355X path (the first pass and single-pass sessions honour them)\n");
-    if (h->vbv && (!rc.by_cost() || rc.pass2)) {          // (open_vbv admitted a session whose rate control fell back since)
-        xlog(&p, X264_LOG_WARNING, "VBV is incompatible with constant QP, ignored.\n");
-        h->vbv = false; p.rc.i_vbv_max_bitrate = 0; p.rc.i_vbv_buffer_size = 0; p.i_nal_hrd = X264_NAL_HRD_NONE;
-    }
-    rc.vbv = h->vbv; rc.filler = h->vbv && p.i_nal_hrd == X264_NAL_HRD_CBR;
-    NoiseReduction::check_modes(p, h->dpbmode);
-    if (p.analyse.i_noise_reduction && p.analyse.f_psy_trellis > 0) {
-        // nr runs (toolset and mode have passed; from here on only a device failure stops it, and that fails the open): psy-trellis gives way, with its share of the
-        // chroma quantiser offset (the macroblock loop has psy instantiations and denoising instantiations, none with both: the build would double again)
-        xlog(&p, X264_LOG_WARNING, "psy-trellis is not run beside noise reduction in the MI355X path (nr %d wins): psy-trellis 0\n", p.analyse.i_noise_reduction);
-        p.analyse.f_psy_trellis = 0; p.analyse.i_chroma_qp_offset = h->cqo_without_psy_trellis;
-    }
-    if (p.i_slice_max_size > 0 || p.i_slice_max_mbs > 0) { xlog(&p, X264_LOG_WARNING, "slice-max-size / slice-max-mbs are not implemented in the MI355X path (slices are cut by --slices N or slice threads only)\n"); p.i_slice_max_size = p.i_slice_max_mbs = 0; }
-    if (p.b_fake_interlaced || p.b_pic_struct) { xlog(&p, X264_LOG_WARNING, "fake-interlaced / pic-struct are not implemented in the MI355X path: off\n"); p.b_fake_interlaced = p.b_pic_struct = 0; }
-    if (p.b_bluray_compat) { xlog(&p, X264_LOG_WARNING, "bluray-compat is not implemented in the MI355X path: off\n"); p.b_bluray_compat = 0; }
-    // adaptive quantisation: variance AQ (mode 1) under CRF / ABR; x264 itself switches AQ off under constant QP and at strength 0
-    if (p.rc.i_rc_method == X264_RC_CQP || p.rc.f_aq_strength <= 0) p.rc.i_aq_mode = X264_AQ_NONE;
-    // macroblock-tree: needs a rate-controlled session and pictures held back (rc-lookahead); x264 switches it off under constant QP
-    if (p.rc.i_rc_method == X264_RC_CQP || p.rc.i_lookahead <= 0) p.rc.b_mb_tree = 0;
-    if (p.rc.b_mb_tree && p.i_threads > 1 && !h->slots_rc) { xlog(&p, X264_LOG_INFO, "mbtree needs threads 1 (GOPs in lock-step are coded before what follows them is seen): mbtree 0\n"); p.rc.b_mb_tree = 0; }
-    p.rc.b_mb_tree = p.rc.b_mb_tree != 0;
-    h->tstats.writing = rc.tree_write = rc.pass1 && p.rc.b_mb_tree && MbTreeStats::opted_in();
-    // (VBV plans over the lookahead too, with or without the tree: x264's vbv_lookahead; rc-lookahead 0 leaves it the reactive algorithm)
-    { const int cap = p.i_keyint_max < 250 ? (p.i_keyint_max > 1 ? p.i_keyint_max : 1) : 250;
-      p.rc.i_lookahead = p.rc.b_mb_tree ? clampi(p.rc.i_lookahead, 1, cap) : h->vbv ? clampi(p.rc.i_lookahead, 0, cap) : 0; }
-    p.rc.i_aq_mode = clampi(p.rc.i_aq_mode, 0, 3);
-    if (p.rc.i_aq_mode > X264_AQ_VARIANCE && !h->dpbmode) {
-        xlog(&p, X264_LOG_WARNING, "aq-mode %d needs B-frames or weightp 2 (the DPB-model path) in the MI355X path: aq-mode 1\n", p.rc.i_aq_mode); p.rc.i_aq_mode = X264_AQ_VARIANCE;
-    }
-    p.rc.i_qp_constant = clampi(qp, 1, 51);
-    p.rc.i_qp_min = clampi(p.rc.i_qp_min, 1, 51); p.rc.i_qp_max = clampi(p.rc.i_qp_max, p.rc.i_qp_min, 51);
-    if (p.i_threads > 1 && p.i_scenecut_threshold) { xlog(&p, X264_LOG_INFO, "scenecut needs threads 1 (GOPs in lock-step have a fixed structure): scenecut 0\n"); p.i_scenecut_threshold = 0; }
-    // x264 validate_parameters: min-keyint auto = min(keyint / 10, fps), then [1, keyint / 2 + 1]
-    if (p.i_keyint_min <= 0) { const int fps = (int)(p.i_fps_num / (p.i_fps_den ? p.i_fps_den : 1)); p.i_keyint_min = p.i_keyint_max / 10 < fps ? p.i_keyint_max / 10 : fps; }
-    p.i_keyint_min = clampi(p.i_keyint_min, 1, p.i_keyint_max / 2 + 1);
-    h->keyint_min = p.i_keyint_min;
-    h->qp_p = p.rc.i_qp_constant;
-    h->qp_i = clampi((int)(h->qp_p - 6.0 * log2(p.rc.f_ip_factor > 0 ? p.rc.f_ip_factor : 1.0) + 0.5), 1, 51);
-    h->pic_init_qp = rc.by_cost() ? 26 : clampi(h->qp_p, 0, 51);          // CRF moves the slice quantiser both ways: centre the +-26 range of slice_qp_delta
-    h->profile_idc = p.analyse.b_transform_8x8 ? 100 : p.b_cabac ? 77 : 66;        // High for the 8x8 transform, Main for CABAC alone, else Baseline-compatible
-    h->level_idc = p.i_level_idc > 0 ? p.i_level_idc : pick_level(&p, h->nmb, p.i_frame_reference);
-    p.i_level_idc = h->level_idc;
-    h->log2_max_frame_num = 4;
-    {   // x264 sps init: max_frame_num = keyint * (1 + b-pyramid) + 1
-        const long max_frame_num = (long)(h->keyint < 65536 ? h->keyint : 65535) * (h->bpyramid + 1) + 1;
-        while ((1L << h->log2_max_frame_num) <= max_frame_num && h->log2_max_frame_num < 16) h->log2_max_frame_num++;
-    }
-    if (h->weightp && h->profile_idc == 66) h->profile_idc = 77;                  // explicit weighted prediction is a Main profile tool
-    if (h->dpbmode) {
-        // x264 sps init: pic_order_cnt_type 0 with room for the largest POC distance of a mini-GOP (type 2 without B pictures); the DPB model owns
-        // frame_num / lists / marking
-        h->dpb.configure(p.i_frame_reference, h->bframes, h->bpyramid, h->log2_max_frame_num, h->weightp);
-        const int max_delta_poc = (h->bframes + 2) * (h->bpyramid + 1) * 2;
-        h->log2_max_poc_lsb = h->bframes ? 4 : 0;
-        while (h->bframes && (1 << h->log2_max_poc_lsb) <= max_delta_poc * 2) h->log2_max_poc_lsb++;
-        h->level_idc = p.i_level_idc > 0 ? p.i_level_idc : pick_level(&p, h->nmb, h->dpb.max_dpb);
-        p.i_level_idc = h->level_idc;
-    }
-    if (h->vbv && p.i_nal_hrd) {
-        // x264_ratecontrol_init_reconfigurable, "Init HRD": rate and size in the value / scale notation (the VBV then runs on what the notation keeps of them), the
-        // lengths of the delay fields from the longest delays the session can produce (a buffering period is at most keyint pictures long, "arbitrary" MAX_DURATION 0.5 s
-        // a picture — and never shorter than the two ticks a picture that constant-frame-rate pictures really take)
-        HrdParams &hr = h->hrd;
-        const int rate = p.rc.i_vbv_max_bitrate * 1000, size = p.rc.i_vbv_buffer_size * 1000;
-        hr.present = 1; hr.cbr = p.i_nal_hrd == X264_NAL_HRD_CBR;
-        hr.bit_rate_scale = clampi(__builtin_ctz((unsigned)rate) - 6, 0, 15); hr.bit_rate_value = rate >> (hr.bit_rate_scale + 6); hr.bit_rate_unscaled = hr.bit_rate_value << (hr.bit_rate_scale + 6);
-        hr.cpb_size_scale = clampi(__builtin_ctz((unsigned)size) - 4, 0, 15); hr.cpb_size_value = size >> (hr.cpb_size_scale + 4); hr.cpb_size_unscaled = hr.cpb_size_value << (hr.cpb_size_scale + 4);
-        const double ticks = 0.5 * (double)(p.i_timebase_den * 2) / p.i_timebase_num;
-        double max_cpb = p.i_keyint_max * ticks; if (max_cpb < 2.0 * p.i_keyint_max) max_cpb = 2.0 * p.i_keyint_max;
-        double max_dpb = h->dpb.max_dpb * ticks; if (max_dpb < 2.0 * (h->dpb.num_reorder + h->bframes + 2)) max_dpb = 2.0 * (h->dpb.num_reorder + h->bframes + 2);
-        const int max_cpb_output_delay = max_cpb < (double)INT_MAX ? (int)max_cpb : INT_MAX, max_dpb_output_delay = max_dpb < (double)INT_MAX ? (int)max_dpb : INT_MAX;
-        const int max_delay = (int)(90000.0 * (double)hr.cpb_size_unscaled / hr.bit_rate_unscaled + 0.5);
-        auto bits = [](int v) { return v > 0 ? 32 - __builtin_clz((unsigned)v) : 0; };
-        hr.initial_cpb_removal_delay_length = 2 + clampi(bits(max_delay), 4, 22);
-        hr.cpb_removal_delay_length = clampi(bits(max_cpb_output_delay), 4, 31);
-        hr.dpb_output_delay_length = clampi(bits(max_dpb_output_delay), 4, 31);
-        rc.hrd_rate = hr.bit_rate_unscaled; rc.hrd_size = hr.cpb_size_unscaled;
-        if (hr.bit_rate_value < 1 || hr.cpb_size_value < 1) { xlog(&p, X264_LOG_WARNING, "nal-hrd: rate or size too small for the HRD's notation: none\n"); hr = HrdParams(); p.i_nal_hrd = X264_NAL_HRD_NONE; rc.hrd_rate = rc.hrd_size = 0; rc.filler = false; }
-    }
-}
-
-// what the device encoder(s) are created with; settles the GOP-slot count, --mvrange and the pictures in flight on the way
-static x264gpu_config open_device_config(x264_t *h)
-{
-    x264_param_t &p = h->param;
-    x264gpu_config cfg = {};
-    // (quantisers planned ahead: a ring picture has up to three rows of the plan store beside it)
-    h->G = GopSlots::fit(p, h->keyint, h->slots_rc ? 3 * (size_t)h->nmb * 4 : 0);
-    if (h->G <= 1) h->slots_rc = false;          // (nothing to run in parallel: the session is the --threads 1 one)
-    cfg.width = p.i_width; cfg.height = p.i_height; cfg.streams = h->G; cfg.refs = p.i_frame_reference; cfg.slices = h->slices; cfg.slices_plain = h->slices_plain; cfg.cabac = p.b_cabac;
-    cfg.qp_i = h->qp_i; cfg.qp_p = h->qp_p; cfg.me_range = p.analyse.i_me_range; cfg.subme = p.analyse.i_subpel_refine;
-    cfg.deblock = p.b_deblocking_filter; cfg.deblock_alpha = p.i_deblocking_filter_alphac0; cfg.deblock_beta = p.i_deblocking_filter_beta;
-    cfg.chroma_qp_offset = p.analyse.i_chroma_qp_offset;
-    cfg.rd = p.analyse.i_subpel_refine >= 8 ? 63 : p.analyse.i_subpel_refine >= 6; cfg.psy_rd_q8 = psy_rd_q8(p);      // 63: RD + every refinement site (x264's i_mbrd 2)
-    if (p.analyse.i_subpel_refine >= 9 && p.b_deblocking_filter) cfg.rd |= 64;          // h->mb.b_deblock_rdo: whole-macroblock RD costs measured after the loop filter
-    cfg.psy_trellis_q8 = psy_trellis_q8(p);
-    cfg.trellis = p.analyse.i_trellis == 2 ? 63 + 64 : p.analyse.i_trellis ? 63 : 0;         // every quantiser call of the final encode; + 64: of the analysis too
-    cfg.psy = cfg.rd && p.analyse.b_psy;           // x264: the chroma lambda offset table follows b_psy, whatever the psy-rd strength
-    cfg.deadzone_inter = p.analyse.i_luma_deadzone[0]; cfg.deadzone_intra = p.analyse.i_luma_deadzone[1];
-    cfg.dct_decimate = p.analyse.b_dct_decimate;
-    // P slices follow analyse.inter, I slices analyse.intra (bit8 marks the separate I-slice set)
-    cfg.partitions = ((p.analyse.inter & X264_ANALYSE_PSUB16x16) ? 1 : 0) | ((p.analyse.inter & X264_ANALYSE_I4x4) ? 2 : 0) | ((p.analyse.inter & X264_ANALYSE_I8x8) ? 4 : 0) |
-                     0x100 | ((p.analyse.intra & X264_ANALYSE_I4x4) ? 0x200 : 0) | ((p.analyse.intra & X264_ANALYSE_I8x8) ? 0x400 : 0) |
-                     ((p.analyse.inter & X264_ANALYSE_BSUB16x16) ? 0x800 : 0);      // B slices: b8x8
-    cfg.dct8x8 = p.analyse.b_transform_8x8;
-    cfg.me_method = p.analyse.i_me_method == X264_ME_DIA ? 0 : p.analyse.i_me_method == X264_ME_HEX ? 1 : p.analyse.i_me_method == X264_ME_UMH ? 2 : 3;
-    cfg.aq_mode = p.rc.i_aq_mode == X264_AQ_VARIANCE; cfg.aq_strength = p.rc.f_aq_strength * 1.0397f;
-    h->aq_mode = p.rc.i_aq_mode;
-    cfg.mixed_refs = p.analyse.b_mixed_references && (p.analyse.inter & X264_ANALYSE_PSUB16x16) != 0;
-    cfg.chroma_me = p.analyse.b_chroma_me && p.analyse.i_subpel_refine >= 5;     // x264: h->mb.b_chroma_me in P slices
-    cfg.fast_pskip = p.analyse.b_fast_pskip;
-    // x264 validate_parameters: --mvrange defaults to the level's limit (x264_levels[].mv_range), never above 512 here
-    if (p.analyse.i_mv_range <= 0) {
-        p.analyse.i_mv_range = 512;
-        for (int i = 0; x264_levels[i].level_idc; i++) if (x264_levels[i].level_idc == h->level_idc) p.analyse.i_mv_range = x264_levels[i].mv_range;
-    }
-    p.analyse.i_mv_range = clampi(p.analyse.i_mv_range, 32, 512);
-    cfg.mv_range = p.analyse.i_mv_range;
-    h->inflight = 1;
-    if (p.analyse.i_noise_reduction && h->dpbmode && p.i_bframe > 0 && getenv("X264GPU_INFLIGHT"))
-        xlog(&p, X264_LOG_INFO, "nr: one picture in flight (X264GPU_INFLIGHT is not used: the session has one noise-reduction state, moved on in coding order)\n");
-    if (h->dpbmode && p.i_bframe > 0 && h->G == 1 && !h->batch.want && !h->rc.reads_sizes() && h->direct_mode != 3 && !p.analyse.i_noise_reduction) {
-        // (--direct auto chooses a B picture's mode from the skip counts of the one before, ABR and 2-pass a picture's quantiser from the sizes of the ones before:
-        //  those sessions code one picture at a time)
-        const char *ie = getenv("X264GPU_INFLIGHT");
-        const int want = getenv("X264GPU_DUMP_RECORDS") ? 1 : ie ? atoi(ie) : 4,          // (the debugging dump follows the serial path)
-                  extra = want - 1 < 7 - h->dpb.max_dpb ? want - 1 : 7 - h->dpb.max_dpb;
-        if (extra >= 1) { h->inflight = extra + 1; h->dpb.extra_slots = extra; }
-    }
-    if (h->dpbmode) { cfg.dpb = h->dpb.max_dpb + h->dpb.extra_slots; cfg.weightb = p.analyse.b_weighted_bipred; }
-    return cfg;
-}
-
+// ---- x264_encoder_open, step by step: what the session runs is settled first (host/settings.hpp); the steps here only create what it says (each logs why it fails; a
+//      failed step leaves the teardown to x264_encoder_close) ----
 // the device side: the staging buffer, then the GOP slots' encoders and rings per device, or a seat in a batch group, or the session's own encoder with its launch contexts
 static bool open_device(x264_t *h)
 {
     x264_param_t &p = h->param;
-    x264gpu_config cfg = open_device_config(h);
+    x264gpu_config cfg = h->set.device_config(p);
     const size_t insz = (size_t)p.i_width * p.i_height * 3 / 2;
     (void)x264gpu_get_device(&h->device);
-    h->ql.open(p, h->G > 1);          // --psnr / --ssim: from here on h->ql.flags says whether the session computes them
+    h->ql.open(p, h->set.G > 1);          // --psnr / --ssim: from here on h->ql.flags says whether the session computes them
     bool ok_setup = x264gpu_malloc((void **)&h->d_in, insz) == X264GPU_OK;
-    if (ok_setup && h->G > 1) {
+    if (ok_setup && h->set.G > 1) {
         // the access unit of a slot's picture (a pool thread of the unit's): AUD, the sets in front of an IDR picture (the SEI in the stream's first GOP only), the slices
         const x264_t *ch = h;
         auto write_coded = [ch](GopSlots::Coded &cd, int pic_type, long gop, SliceParams sp, const x264gpu_mb *mb, const int16_t *lv) {
@@ -680,54 +288,54 @@ static bool open_device(x264_t *h)
             cd.idr = pic_type == PIC_IDR; cd.i_type = x264_type_of(pic_type);
             begin_access_unit(ch, cd.bytes, cd.off, cd.types, pic_type, gop == 0);
             sp.idr_pic_id = (int)(gop & 0xffff);
-            write_slices(cd.bytes, cd.off, cd.types, sp, ch->slices, mb, lv, ch->param.b_annexb != 0, cd.idr, nullptr, 1);
+            write_slices(cd.bytes, cd.off, cd.types, sp, ch->set.slices, mb, lv, ch->param.b_annexb != 0, cd.idr, nullptr, 1);
         };
-        GopSlots::Setup su = { h->G, h->keyint, h->nmb, h->qp_i, h->qp_p, h->bframes, h->bpyramid, h->weightp, h->log2_max_frame_num, h->direct_mode, h->dpbmode,
+        GopSlots::Setup su = { h->set.G, h->set.keyint, h->set.nmb, h->set.qp_i, h->set.qp_p, h->set.bframes, h->set.bpyramid, h->set.weightp, h->set.log2_max_frame_num, h->set.direct_mode, h->set.dpbmode,
                                h->device, slice_params_base(h), write_coded };
-        if (h->slots_rc) {
+        if (h->set.slots_rc) {
             // what the session's own lookahead will hand the slots with every planned picture (bmode_plan): offsets from the tree or --aq-mode 2 / 3, vectors from the
             // lookahead object the tree opens; the lookahead's wait is x264's i_slicetype_length
             su.planned = true;
             su.plan_offsets = p.rc.b_mb_tree || (p.rc.i_aq_mode >= 2 && p.rc.f_aq_strength > 0);
             su.plan_mvs = p.rc.b_mb_tree != 0;
-            su.plan_wait = p.rc.b_mb_tree && p.rc.i_lookahead > h->bframes ? p.rc.i_lookahead : h->bframes;
-            if (p.rc.b_mb_tree && h->weightp)
-                xlog(&p, X264_LOG_INFO, "weightp %d in GOP slots: a fade's explicit weights are not coded (the slots of a device call share them; the lookahead still weighs fades for its costs)\n", h->weightp);
+            su.plan_wait = p.rc.b_mb_tree && h->set.lookahead_asked > h->set.bframes ? h->set.lookahead_asked : h->set.bframes;
+            if (p.rc.b_mb_tree && h->set.weightp)
+                xlog(&p, X264_LOG_INFO, "weightp %d in GOP slots: a fade's explicit weights are not coded (the slots of a device call share them; the lookahead still weighs fades for its costs)\n", h->set.weightp);
         }
         return h->gops.open(p, cfg, h->rc, su);
     } else if (ok_setup && h->batch.want) {
         // what the session's own lookahead will hand the group with every picture (bmode_plan): offsets from the tree or --aq-mode 2 / 3, vectors from the lookahead object
         // the tree (or a VBV plan) opens; sessions that differ in any of it, or in what shapes it, form groups of their own
         Batch::Side side;
-        const bool la_object = p.rc.b_mb_tree || (h->vbv && p.rc.i_lookahead > 0);
+        const bool la_object = p.rc.b_mb_tree || (h->set.vbv && h->set.lookahead_asked > 0);
         side.offsets = p.rc.b_mb_tree || (p.rc.i_aq_mode >= 2 && p.rc.f_aq_strength > 0);
         side.mvs = la_object;
-        side.key = (p.rc.b_mb_tree ? 1 : 0) | p.rc.i_aq_mode << 1 | h->direct_mode << 4 | p.rc.i_lookahead << 8;
-        ok_setup = h->batch.join(cfg, h->batch.want, insz, (size_t)h->nmb, h->ql.flags, p.analyse.i_noise_reduction, side);
+        side.key = (p.rc.b_mb_tree ? 1 : 0) | p.rc.i_aq_mode << 1 | h->set.direct_mode << 4 | h->set.lookahead_asked << 8;
+        ok_setup = h->batch.join(cfg, h->batch.want, insz, (size_t)h->set.nmb, h->ql.flags, p.analyse.i_noise_reduction, side);
         if (ok_setup) xlog(&p, X264_LOG_INFO, "X264GPU_BATCH: stream %d of a batch of %d sessions%s%s\n", h->batch.index(), h->batch.size(), h->batch.queued() ? " (rounds queued: uploads overlap the device)" : "",
                            side.offsets && side.mvs ? "; the group carries each member's quantiser offsets and lookahead vectors" : side.offsets ? "; the group carries each member's quantiser offsets" :
                            side.mvs ? "; the group carries each member's lookahead vectors" : "");
-        if (ok_setup && la_object && h->weightp)
-            xlog(&p, X264_LOG_INFO, "weightp %d in a batch: a fade's explicit weights are not coded (the streams of a device call share them; the lookahead still weighs fades for its costs)\n", h->weightp);
+        if (ok_setup && la_object && h->set.weightp)
+            xlog(&p, X264_LOG_INFO, "weightp %d in a batch: a fade's explicit weights are not coded (the streams of a device call share them; the lookahead still weighs fades for its costs)\n", h->set.weightp);
     } else if (ok_setup) {
         ok_setup = x264gpu_encoder_create(&h->gpu, &cfg) == X264GPU_OK &&
-                   x264gpu_malloc((void **)&h->d_mb, (size_t)h->nmb * sizeof(x264gpu_mb)) == X264GPU_OK &&
-                   x264gpu_malloc((void **)&h->d_lv, (size_t)h->nmb * X264GPU_MB_LEVELS * sizeof(int16_t)) == X264GPU_OK &&
+                   x264gpu_malloc((void **)&h->d_mb, (size_t)h->set.nmb * sizeof(x264gpu_mb)) == X264GPU_OK &&
+                   x264gpu_malloc((void **)&h->d_lv, (size_t)h->set.nmb * X264GPU_MB_LEVELS * sizeof(int16_t)) == X264GPU_OK &&
                    (!h->ql.flags || x264gpu_malloc((void **)&h->d_q, sizeof(x264gpu_quality)) == X264GPU_OK);
         ok_setup = ok_setup && h->nr.open(p, h->gpu);
-        if (ok_setup && h->inflight > 1) {
-            h->lctx.resize((size_t)h->inflight);
+        if (ok_setup && h->set.inflight > 1) {
+            h->lctx.resize((size_t)h->set.inflight);
             ok_setup = x264gpu_event_create(&h->ev_la) == X264GPU_OK;
-            for (int i = 0; i < h->inflight && ok_setup; i++) {
+            for (int i = 0; i < h->set.inflight && ok_setup; i++) {
                 x264_t::LaunchCtx &c = h->lctx[(size_t)i];
                 if (i == 0) { c.gpu = h->gpu; c.d_mb = h->d_mb; c.d_lv = h->d_lv; c.d_q = h->d_q; }
                 else ok_setup = x264gpu_encoder_create_view(&c.gpu, h->gpu) == X264GPU_OK &&
-                                x264gpu_malloc((void **)&c.d_mb, (size_t)h->nmb * sizeof(x264gpu_mb)) == X264GPU_OK &&
-                                x264gpu_malloc((void **)&c.d_lv, (size_t)h->nmb * X264GPU_MB_LEVELS * sizeof(int16_t)) == X264GPU_OK &&
+                                x264gpu_malloc((void **)&c.d_mb, (size_t)h->set.nmb * sizeof(x264gpu_mb)) == X264GPU_OK &&
+                                x264gpu_malloc((void **)&c.d_lv, (size_t)h->set.nmb * X264GPU_MB_LEVELS * sizeof(int16_t)) == X264GPU_OK &&
                                 (!h->ql.flags || x264gpu_malloc((void **)&c.d_q, sizeof(x264gpu_quality)) == X264GPU_OK);
                 ok_setup = ok_setup && x264gpu_stream_create(&c.stream) == X264GPU_OK && x264gpu_event_create(&c.ev) == X264GPU_OK;
             }
-            if (ok_setup) xlog(&p, X264_LOG_INFO, "up to %d pictures of the session in flight (pictures that share only finished references; the stream is the serial one)\n", h->inflight);
+            if (ok_setup) xlog(&p, X264_LOG_INFO, "up to %d pictures of the session in flight (pictures that share only finished references; the stream is the serial one)\n", h->set.inflight);
         }
     }
     if (!ok_setup) {
@@ -737,72 +345,40 @@ static bool open_device(x264_t *h)
     return true;
 }
 
-// lookahead and slice-type objects, how many pictures are held back, the queue's device ring
+// lookahead and slice-type objects, the queue's device ring
 static bool open_lookahead(x264_t *h)
 {
     x264_param_t &p = h->param;
     const size_t insz = (size_t)p.i_width * p.i_height * 3 / 2;
-    if ((p.i_scenecut_threshold > 0 && !h->dpbmode) || h->rc.by_cost() || h->aq_mode >= 2 || h->tstats.reading) {       // (sessions on the DPB model take scene cuts from x264's own analysis below; a second pass over the tree file: the AQ kernel only)
+    if (h->set.lookahead) {
         if (x264gpu_lookahead_create(&h->la, p.i_width, p.i_height, 1, p.analyse.i_me_range, p.analyse.i_subpel_refine) != X264GPU_OK ||
             x264gpu_malloc((void **)&h->d_la, 4 * sizeof(int32_t)) != X264GPU_OK) {
             xlog(&p, X264_LOG_ERROR, "GPU lookahead setup failed: %s\n", x264gpu_last_error());
             return false;
         }
     }
-    // lookahead queue: rc-lookahead pictures are held back when the macroblock-tree is on (x264's sync lookahead), none otherwise
-    h->mbtree = p.rc.b_mb_tree && h->la != nullptr;
-    h->L = h->mbtree || h->vbv ? p.rc.i_lookahead : 0;
-    // pictures are held back anyway and the quantisers do not depend on coded sizes: overlap the GPU stage of the next picture with
-    // the entropy coding of this one (one more picture of delay); X264GPU_HOST_PIPELINE=0 keeps the two stages in one call
-    { const char *pe = getenv("X264GPU_HOST_PIPELINE"); h->pipeline = h->G == 1 && h->L > 0 && h->rc.crf && !(pe && pe[0] == '0'); }
-    h->Q = h->L + 1 + (h->pipeline ? 1 : 0);
-    if (h->dpbmode) {
-        if (h->L > 60) { xlog(&p, X264_LOG_INFO, "rc-lookahead %d -> 60 in sessions with B pictures (the lookahead keeps every queued picture's half-resolution planes and searches on the device)\n", h->L); h->L = 60; p.rc.i_lookahead = 60; }
-        h->pipeline = false; h->Q = h->L + 2 * (h->bframes + 1) + 2;      // the lookahead window + display-order queue + the mini-GOP being coded
-    }
-    int st_wait = h->bframes > h->L ? h->bframes : h->L;          // x264 i_slicetype_length
-    // x264 h->frames.i_delay: the trellis over picture types looks max(bframes, 3) * 4 pictures ahead
-    if (h->dpbmode && h->bframes && p.i_bframe_adaptive == 2) { const int d = (h->bframes > 3 ? h->bframes : 3) * 4; if (d > st_wait) st_wait = d; if (h->Q < st_wait + 2 * (h->bframes + 1) + 2) h->Q = st_wait + 2 * (h->bframes + 1) + 2; }
-    if (h->dpbmode && h->inflight > 1) h->Q += h->inflight + h->bframes + 1;           // ... + the pictures in flight (their source pictures and offsets are read when their kernels run)
-    if (h->dpbmode && h->Q > 128) {          // the lookahead object holds 128 pictures
-        const int over = h->Q - 128;
-        xlog(&p, X264_LOG_INFO, "lookahead window shortened by %d pictures (128 pictures are held at most)\n", over);
-        h->L = h->L > over ? h->L - over : 0; p.rc.i_lookahead = h->L;
-        if (st_wait > 128 - 2 * (h->bframes + 1) - 2) st_wait = 128 - 2 * (h->bframes + 1) - 2;
-        h->Q = 128;
-    }
-    h->rc.vbv_lookahead = h->vbv && h->L > 0;
-    if (h->vbv) {
-        p.rc.i_lookahead = h->L;
-        xlog(&p, X264_LOG_INFO, "VBV: maxrate %d kbit/s, bufsize %d kbit, init %.3f%s; %s; x264's row-level re-quantisation is replaced by picture re-encode: a picture that would under-run the buffer is coded again at a higher quantiser\n",
-             p.rc.i_vbv_max_bitrate, p.rc.i_vbv_buffer_size, (double)p.rc.f_vbv_buffer_init, p.i_nal_hrd == X264_NAL_HRD_CBR ? ", nal-hrd cbr" : p.i_nal_hrd ? ", nal-hrd vbr" : "",
-             h->L > 0 ? "quantisers planned over the lookahead" : "rc-lookahead 0: the reactive algorithm");
-        if (p.b_vfr_input) xlog(&p, X264_LOG_INFO, "VBV: variable frame rate durations are not implemented in the MI355X path: every picture stays in the buffer for 1 / fps\n");
-        if (p.rc.f_rf_constant_max > 0) xlog(&p, X264_LOG_WARNING, "crf-max is not implemented in the MI355X path: ignored\n");
-    }
-    h->aq_strength = h->aq_mode == X264_AQ_VARIANCE ? p.rc.f_aq_strength * 1.0397f : h->aq_mode >= 2 ? p.rc.f_aq_strength : 0.f;      // (modes 2 / 3: the plain strength, x264_adaptive_quant_frame scales it by the picture's mean itself)
-    h->tree_strength = 5.0f * (1.0f - p.rc.f_qcompress);
-    h->q_raw.assign((size_t)h->Q, nullptr); h->q_info.assign((size_t)h->Q, nullptr); h->q_aq.assign((size_t)h->Q, nullptr); h->q_tree.assign((size_t)h->Q, nullptr);
-    if (h->dpbmode && !h->slicetype.open(p, h->rc, { h->Q, st_wait, h->mbw, h->mbh, h->bframes, h->bpyramid, h->weightp, h->mbtree, h->vbv, h->aq_strength, h->tree_strength,
+    h->set.log_lookahead(p);
+    h->q_raw.assign((size_t)h->set.Q, nullptr); h->q_info.assign((size_t)h->set.Q, nullptr); h->q_aq.assign((size_t)h->set.Q, nullptr); h->q_tree.assign((size_t)h->set.Q, nullptr);
+    if (h->set.dpbmode && !h->slicetype.open(p, h->rc, { h->set.Q, h->set.st_wait, h->set.mbw, h->set.mbh, h->set.bframes, h->set.bpyramid, h->set.weightp, h->set.mbtree, h->set.vbv, h->set.aq_strength, h->set.tree_strength,
                                                      h->q_raw.data(), h->q_aq.data(), h->q_tree.data() })) return false;
-    if (h->Q == 1) h->q_raw[0] = h->d_in;            // no delay: the staging buffer is the one slot; with a delay the ring is separate,
+    if (h->set.Q == 1) h->q_raw[0] = h->d_in;            // no delay: the staging buffer is the one slot; with a delay the ring is separate,
                                                      // because a zero-copy caller rewrites the staging buffer every call
     {
         // one device block per array, cut into the queue's slots (an allocation and a release each cost a fraction of a millisecond: thousands of sessions open and close)
         bool ok = true;
-        const size_t Q = (size_t)h->Q, insz_al = (insz + 255) & ~(size_t)255, nmbf = ((size_t)h->nmb * sizeof(float) + 255) & ~(size_t)255, ninfo = ((size_t)h->nmb * 4 * sizeof(int32_t) + 255) & ~(size_t)255;
-        const bool want_aq = h->mbtree || h->slicetype.aq_costs || h->aq_mode >= 2 || h->tstats.reading, want_tree = (h->mbtree && h->dpbmode) || h->tstats.reading;
+        const size_t Q = (size_t)h->set.Q, insz_al = (insz + 255) & ~(size_t)255, nmbf = ((size_t)h->set.nmb * sizeof(float) + 255) & ~(size_t)255, ninfo = ((size_t)h->set.nmb * 4 * sizeof(int32_t) + 255) & ~(size_t)255;
+        const bool want_aq = h->set.mbtree || h->slicetype.aq_costs || h->set.aq_mode >= 2 || h->tstats.reading, want_tree = (h->set.mbtree && h->set.dpbmode) || h->tstats.reading;
         if (!h->q_raw[0]) ok = x264gpu_malloc((void **)&h->q_block[0], Q * insz_al) == X264GPU_OK;
-        if (ok && h->mbtree) ok = x264gpu_malloc((void **)&h->q_block[1], Q * ninfo) == X264GPU_OK;
+        if (ok && h->set.mbtree) ok = x264gpu_malloc((void **)&h->q_block[1], Q * ninfo) == X264GPU_OK;
         if (ok && want_aq) ok = x264gpu_malloc((void **)&h->q_block[2], Q * nmbf) == X264GPU_OK;
         if (ok && want_tree) ok = x264gpu_malloc((void **)&h->q_block[3], Q * nmbf) == X264GPU_OK;
         for (size_t i = 0; i < Q && ok; i++) {
             if (!h->q_raw[i]) h->q_raw[i] = (uint8_t *)h->q_block[0] + i * insz_al;
-            if (h->mbtree) h->q_info[i] = (int32_t *)((uint8_t *)h->q_block[1] + i * ninfo);
+            if (h->set.mbtree) h->q_info[i] = (int32_t *)((uint8_t *)h->q_block[1] + i * ninfo);
             if (want_aq) h->q_aq[i] = (float *)((uint8_t *)h->q_block[2] + i * nmbf);
             if (want_tree) h->q_tree[i] = (float *)((uint8_t *)h->q_block[3] + i * nmbf);
         }
-        if (ok && h->mbtree) ok = x264gpu_malloc((void **)&h->d_tree, (size_t)h->nmb * sizeof(float)) == X264GPU_OK;
+        if (ok && h->set.mbtree) ok = x264gpu_malloc((void **)&h->d_tree, (size_t)h->set.nmb * sizeof(float)) == X264GPU_OK;
         if (!ok) {
             xlog(&p, X264_LOG_ERROR, "GPU lookahead queue setup failed: %s\n", x264gpu_last_error());
             return false;
@@ -816,12 +392,11 @@ static void open_host_buffers(x264_t *h)
 {
     x264_param_t &p = h->param;
     const size_t insz = (size_t)p.i_width * p.i_height * 3 / 2;
-    { const unsigned hw = std::thread::hardware_concurrency(); h->cavlc_threads = h->G > 1 ? 1 : cavlc_threads_default(hw >= 32 ? 16 : hw >= 16 ? 8 : hw >= 4 ? (int)hw / 2 : 1); }
     h->h_in.resize(insz);
     // (a batch session whose pictures are downloaded and coded by its helper threads keeps the records in the two deferred slots instead: 7 MB less to clear per open)
     // (... and GOP slots own their download buffers)
-    if (!h->batch.overlap() && h->G == 1) { h->h_mb.resize((size_t)h->nmb); h->h_lv.resize((size_t)h->nmb * X264GPU_MB_LEVELS); }
-    if (h->pipeline) { h->h_mb2.resize(h->h_mb.size()); h->h_lv2.resize(h->h_lv.size()); }
+    if (!h->batch.overlap() && h->set.G == 1) { h->h_mb.resize((size_t)h->set.nmb); h->h_lv.resize((size_t)h->set.nmb * X264GPU_MB_LEVELS); }
+    if (h->set.pipeline) { h->h_mb2.resize(h->h_mb.size()); h->h_lv2.resize(h->h_lv.size()); }
 }
 
 x264_t *x264_encoder_open(x264_param_t *param)
@@ -838,25 +413,13 @@ x264_t *x264_encoder_open(x264_param_t *param)
     x264_param_t &p = h->param;
     if (p.rc.psz_stat_in) { h->stat_in = p.rc.psz_stat_in; p.rc.psz_stat_in = &h->stat_in[0]; }     // codec.c:1386 stack buffers
     if (p.rc.psz_stat_out) { h->stat_out = p.rc.psz_stat_out; p.rc.psz_stat_out = &h->stat_out[0]; }
-    h->mbw = (p.i_width + 15) / 16; h->mbh = (p.i_height + 15) / 16; h->nmb = h->mbw * h->mbh;
-    if (!p.i_timebase_num || !p.i_timebase_den) { p.i_timebase_num = p.i_fps_den; p.i_timebase_den = p.i_fps_num; }
-
-    open_toolset(h);
-    {   // GOP slots with quantisers planned ahead (opt-in): CRF with B pictures under --threads G, nothing that reads coded sizes or shares the session's state
-        const char *se = getenv("X264GPU_GOP_SLOTS_RC"), *be = getenv("X264GPU_BATCH");
-        h->slots_rc = se && atoi(se) == 1 && p.i_threads > 1 && p.rc.i_rc_method == X264_RC_CRF && p.rc.f_rf_constant >= 1.0f && p.i_bframe > 0 && p.i_keyint_max >= 2 &&
-                      p.i_keyint_max < (1 << 20) && p.rc.i_vbv_max_bitrate <= 0 && p.rc.i_vbv_buffer_size <= 0 && !p.rc.b_stat_read && !p.rc.b_stat_write && !(be && atoi(be) >= 2) &&
-                      !p.analyse.i_noise_reduction;
-    }
-    open_vbv(h);
-    open_modes(h);
-    open_quantisers(h);
-    if (!open_device(h) || !open_lookahead(h) || !h->rc.open(p, h->mbw, h->mbh, h->bframes, h->qp_i, h->qp_p) ||
-        !h->tstats.open(p, p.rc.psz_stat_in, p.rc.psz_stat_out, h->nmb)) { x264_encoder_close(h); return nullptr; }
+    h->settled_at_open.settle(p, h->rc, h->dpb, h->tstats, h->batch.want);
+    if (!open_device(h) || !open_lookahead(h) || !h->rc.open(p, h->set.mbw, h->set.mbh, h->set.bframes, h->set.qp_i, h->set.qp_p) ||
+        !h->tstats.open(p, p.rc.psz_stat_in, p.rc.psz_stat_out, h->set.nmb)) { x264_encoder_close(h); return nullptr; }
     if (h->tstats.reading) p.rc.b_mb_tree = 1;          // reported back: the second pass codes with the first pass' tree (every reader of the flag has run)
     open_host_buffers(h);
-    xlog(&p, X264_LOG_INFO, "MI355X hot path: %dx%d, %d MBs, CQP I:%d P:%d, keyint %d, level %d\n", p.i_width, p.i_height, h->nmb,
-         h->qp_i, h->qp_p, h->keyint, h->level_idc);
+    xlog(&p, X264_LOG_INFO, "MI355X hot path: %dx%d, %d MBs, CQP I:%d P:%d, keyint %d, level %d\n", p.i_width, p.i_height, h->set.nmb,
+         h->set.qp_i, h->set.qp_p, h->set.keyint, h->set.level_idc);
     return h;
 }
 
@@ -864,7 +427,7 @@ void x264_encoder_parameters(x264_t *h, x264_param_t *param)
 {
     if (!h || !param) return;
     *param = h->param;
-    if (h->slices > 1 && !h->slices_plain && h->G <= 1) param->i_threads = h->slices;      // slice threads: i_threads is the slice count, as in x264
+    if (h->set.slices > 1 && !h->set.slices_plain && h->set.G <= 1) param->i_threads = h->set.slices;      // slice threads: i_threads is the slice count, as in x264
 }
 
 static void publish_nals(x264_t *h, x264_nal_t **pp_nal, int *pi_nal, const std::vector<int> &types)
@@ -916,7 +479,7 @@ static int gop_slots_pop(x264_t *h, x264_nal_t **pp_nal, int *pi_nal, x264_pictu
     if (gs.with_b()) {
         for (size_t i = 0; i < h->nals.size(); i++) if (c.types[i] == 1 || c.types[i] == 5) h->nals[i].i_ref_idc = c.ref_idc;
         // coding order: the picture's own pts (its display place in its GOP) and x264's dts
-        const long k = c.index, gop_base = k - k % h->keyint;
+        const long k = c.index, gop_base = k - k % h->set.keyint;
         const size_t np = h->all_pts.size(), di = (size_t)(gop_base + c.disp);
         fill_pic_out(pic_out, c.i_type, c.idr, h->all_pts[di < np ? di : np - 1], coded_dts(h, k), nullptr);
     } else fill_pic_out(pic_out, c.idr ? X264_TYPE_IDR : X264_TYPE_P, c.idr, c.pts, c.pts, nullptr);
@@ -933,7 +496,7 @@ static int gpu_stage(x264_t *h, size_t idx, int buf, bool async)
     const x264_param_t &p = h->param;
     x264_t::QEntry &e = h->queue[idx];
     const bool idr = e.type == 2, intra_pic = e.type == 1;
-    if (h->mbtree) {
+    if (h->set.mbtree) {
         // macroblock_tree: this picture and the P pictures behind it that (transitively) reference it; an intra picture ends the chain
         const int32_t *info[256]; const float *aq[256];
         int n = 0;
@@ -943,7 +506,7 @@ static int gpu_stage(x264_t *h, size_t idx, int buf, bool async)
             info[n] = h->q_info[(size_t)q.slot]; aq[n] = h->q_aq[(size_t)q.slot];
             if (++n == 256) break;
         }
-        if (x264gpu_lookahead_mbtree(h->la, info, h->aq_strength != 0.f ? aq : nullptr, n, h->tree_strength, h->d_tree, nullptr) != X264GPU_OK ||
+        if (x264gpu_lookahead_mbtree(h->la, info, h->set.aq_strength != 0.f ? aq : nullptr, n, h->set.tree_strength, h->d_tree, nullptr) != X264GPU_OK ||
             x264gpu_encoder_set_mb_qp_offsets(h->gpu, h->d_tree) != X264GPU_OK) {
             xlog(&p, X264_LOG_ERROR, "x264_encoder_encode: macroblock-tree failed: %s\n", x264gpu_last_error());
             return -1;
@@ -980,13 +543,13 @@ static int encode_queued(x264_t *h, x264_nal_t **pp_nal, int *pi_nal, x264_pictu
 {
     const x264_param_t &p = h->param;
     if (!h->queue.front().launched) {
-        if (gpu_stage(h, 0, 0, h->pipeline) < 0) return -1;
-        if (h->pipeline && !flushing) return 0;              // its results are collected by the next call
+        if (gpu_stage(h, 0, 0, h->set.pipeline) < 0) return -1;
+        if (h->set.pipeline && !flushing) return 0;              // its results are collected by the next call
     }
     join_gpu(h);
     if (h->gpu_rc) { xlog(&p, X264_LOG_ERROR, "x264_encoder_encode: GPU hot path failed: %s\n", h->gpu_err.c_str()); return -1; }
     // pipelined: the next picture has its whole lookahead window (or the input has ended): start its GPU stage behind this one's coding
-    if (h->pipeline && h->queue.size() >= 2 && (flushing || (int)h->queue.size() >= h->L + 2) &&
+    if (h->set.pipeline && h->queue.size() >= 2 && (flushing || (int)h->queue.size() >= h->set.L + 2) &&
         gpu_stage(h, 1, h->queue.front().buf ^ 1, true) < 0) return -1;
     const x264_t::QEntry e = h->queue.front();
     const bool idr = e.type == 2, intra_pic = e.type == 1;
@@ -1007,12 +570,12 @@ static int encode_queued(x264_t *h, x264_nal_t **pp_nal, int *pi_nal, x264_pictu
     sp.idr = idr; sp.idr_pic_id = h->idr_pic_id; sp.nal_ref_idc = idr ? 3 : 2;
     sp.num_ref = h->frames_since_idr < p.i_frame_reference ? (h->frames_since_idr > 0 ? h->frames_since_idr : 1) : p.i_frame_reference;
     h->last_stats.skip = 0;
-    write_slices(h->out, h->nal_off, types, sp, h->slices, hmb, hlv, p.b_annexb != 0, idr, &h->last_stats, h->cavlc_threads);
+    write_slices(h->out, h->nal_off, types, sp, h->set.slices, hmb, hlv, p.b_annexb != 0, idr, &h->last_stats, h->set.cavlc_threads);
     publish_nals(h, pp_nal, pi_nal, types);
     fill_pic_out(pic_out, x264_type_of(type), idr, e.pts, e.pts, &e.img);
-    if (h->ql.flags) h->ql.frame_end(p, h->hq[e.buf], st == X264GPU_SLICE_P ? 1 : 0, mean_mb_qp(hmb, (size_t)h->nmb), 2 * h->frames_since_idr, h->out.size());
+    if (h->ql.flags) h->ql.frame_end(p, h->hq[e.buf], st == X264GPU_SLICE_P ? 1 : 0, mean_mb_qp(hmb, (size_t)h->set.nmb), 2 * h->frames_since_idr, h->out.size());
     if (idr) h->idr_pic_id = (h->idr_pic_id + 1) & 0xffff;
-    h->frame_num = (h->frame_num + 1) & ((1 << h->log2_max_frame_num) - 1);
+    h->frame_num = (h->frame_num + 1) & ((1 << h->set.log2_max_frame_num) - 1);
     h->rc.end(h->out.size(), type, h->frame_no, e.qpf);          // (no statistics file off the DPB model)
     h->frames_since_idr++;
     h->frame_no++;
@@ -1026,8 +589,8 @@ static int encode_queued(x264_t *h, x264_nal_t **pp_nal, int *pi_nal, x264_pictu
 // order two ticks apart: 2 x (display index - coding index + the reorder depth))
 static bool au_timing(const x264_t *h, const SliceType::Pic &pl, AuTiming &tm)
 {
-    if (!h->hrd.present) return false;
-    const double rate = h->hrd.bit_rate_unscaled, size = h->hrd.cpb_size_unscaled;
+    if (!h->set.hrd.present) return false;
+    const double rate = h->set.hrd.bit_rate_unscaled, size = h->set.hrd.cpb_size_unscaled;
     const double fill = h->rc.buffer_fill_final < 0 ? 0 : h->rc.buffer_fill_final > size ? size : h->rc.buffer_fill_final;
     tm.initial_cpb_removal_delay = (uint32_t)floor(90000.0 * fill / rate);
     tm.initial_cpb_removal_delay_offset = (uint32_t)floor(90000.0 * size / rate) - tm.initial_cpb_removal_delay;
@@ -1065,13 +628,13 @@ static void bmode_plan(x264_t *h, x264_t::PicPlan &f, x264gpu_encoder *gpu, long
     for (size_t i = 0; i < behind.size() && nf < 16 && behind[i].type == PIC_B; i++) { fc[nf] = (int)(coded_index + 1 + (long)i); ff[nf] = behind[i].e.frame; nf++; }
     // (the explicit weights of a picture are the same in every stream of a device call: a member of a batch group, whose lookahead would find its own, codes fades unweighted)
     // (... and so does a session whose pictures are coded by GOP slots)
-    const DpbPlan plan = h->dpb.plan(pl.type, pl.e.frame, nf, fc, ff, pl.type == PIC_P && pl.e.w.on && !h->batch.joined() && !h->slots_rc ? &pl.e.w : nullptr);
+    const DpbPlan plan = h->dpb.plan(pl.type, pl.e.frame, nf, fc, ff, pl.type == PIC_P && pl.e.w.on && !h->batch.joined() && !h->set.slots_rc ? &pl.e.w : nullptr);
     f.nal_ref_idc = plan.nal_ref_idc;
     x264gpu_pic &pic = f.pic;
     pic = plan.pic;
     const RateControl::BRefs near = { { pic.slot[0][0], pic.slot[1][0] }, { abs(pic.poc - plan.list_poc[0][0]), abs(pic.poc - plan.list_poc[1][0]) } };      // (read for a B picture)
     const bool is_b = pl.type == PIC_B || pl.type == PIC_BREF;
-    if (h->vbv) {
+    if (h->set.vbv) {
         // x264 frame->i_bframes / b_last_minigop_bframe (every picture of a mini-GOP knows how many B pictures it holds), and the header NAL units the
         // access unit opens with (x264_ratecontrol_start's overhead)
         if (!is_b) h->minigop_b = (int)behind.size();          // (what is left of the mini-GOP in the coding queue: its B pictures)
@@ -1079,7 +642,7 @@ static void bmode_plan(x264_t *h, x264_t::PicPlan &f, x264gpu_encoder *gpu, long
         h->rc.vbv_picture(&pl.e.planned, h->minigop_b, f.last_minigop_b, au_overhead_bits(h, pl));
     }
     pic.qp = h->rc.start(pl.type, pl.e.frame, pl.e.costs, &near, &f.qpf);
-    if (h->vbv) {
+    if (h->set.vbv) {
         x264_t::VbvInfo &v = h->last_vbv;
         v.valid = true; v.fill_before = h->rc.buffer_fill; v.qp_novbv = h->rc.qp_novbv; v.qp_clipped = f.qpf; v.frame_size_planned = h->rc.frame_size_planned;
         v.planned = pl.e.planned; v.attempts = 1; v.filler = 0; v.overhead_bits = au_overhead_bits(h, pl);
@@ -1087,13 +650,13 @@ static void bmode_plan(x264_t *h, x264_t::PicPlan &f, x264gpu_encoder *gpu, long
     // x264_ratecontrol_mb_qp: a macroblock's quantiser is round(rc->qpm + its AQ / macroblock-tree offset) with qpm the picture's FLOAT quantiser
     pic.qpm = near_qpm(f.qpf, pic.qp);
     f.direct_auto_write = false;
-    if (is_b && h->direct_mode != 1) {
+    if (is_b && h->set.direct_mode != 1) {
         // x264 slice_header_init: temporal direct prediction is considered only when the co-located picture's reference 0 is this picture's reference 0;
         // --direct auto (serial only: sessions with pictures in flight never run it): the mode whose skip probe passed more often so far
         // (h->stat.i_direct_score), every macroblock probing both again
         bool spatial = true;
         if (pic.nref[0] && pic.nref[1] && h->slot_l0ref0poc[pic.slot[1][0]] == plan.list_poc[0][0]) {
-            f.direct_auto_write = serial && h->direct_mode == 3;
+            f.direct_auto_write = serial && h->set.direct_mode == 3;
             spatial = f.direct_auto_write ? h->direct_score[1] > h->direct_score[0] : false;
         }
         pic.direct_temporal = !spatial; pic.direct_auto = f.direct_auto_write;
@@ -1106,15 +669,15 @@ static void bmode_plan(x264_t *h, x264_t::PicPlan &f, x264gpu_encoder *gpu, long
         if (gpu) { x264gpu_encoder_set_lowres_mvs(gpu, f.d_mvs[0]); x264gpu_encoder_set_lowres_mvs1(gpu, f.d_mvs[1]); }
     }
     f.d_offsets = nullptr;
-    if (h->slicetype.analyses() && h->mbtree)          // P / I / B-reference pictures: what the tree left (AQ - tree); other B pictures: the AQ offsets alone (x264 f_qp_offset_aq)
+    if (h->slicetype.analyses() && h->set.mbtree)          // P / I / B-reference pictures: what the tree left (AQ - tree); other B pictures: the AQ offsets alone (x264 f_qp_offset_aq)
         f.d_offsets = pl.type == PIC_B ? h->q_aq[(size_t)pl.e.slot] : h->q_tree[(size_t)pl.e.slot];
     else if (h->tstats.reading) {
         // a second pass over the macroblock-tree statistics file: a kept picture's record, unpacked into its slot; every other picture the AQ offsets alone
         const int got = h->tstats.read_record(h->param, coded_index, pl.type, h->q_tree[(size_t)pl.e.slot], nullptr);
         if (got < 0) h->failed = true;
-        f.d_offsets = got > 0 ? h->q_tree[(size_t)pl.e.slot] : h->aq_strength != 0.f ? h->q_aq[(size_t)pl.e.slot] : nullptr;
+        f.d_offsets = got > 0 ? h->q_tree[(size_t)pl.e.slot] : h->set.aq_strength != 0.f ? h->q_aq[(size_t)pl.e.slot] : nullptr;
     }
-    else if (h->aq_mode >= 2 && h->aq_strength != 0.f) f.d_offsets = h->q_aq[(size_t)pl.e.slot];      // --aq-mode 2 / 3: the offsets computed when the picture arrived
+    else if (h->set.aq_mode >= 2 && h->set.aq_strength != 0.f) f.d_offsets = h->q_aq[(size_t)pl.e.slot];      // --aq-mode 2 / 3: the offsets computed when the picture arrived
     // (the serial path names a buffer only when there is one; a launch context is always told, "none" included — and so is a second pass over the tree file,
     //  whose pictures take turns between two kinds of offsets or none).  A member of a batch group has no encoder of its own (gpu == nullptr): its vectors and offsets go
     //  to the group with the picture (Batch::submit), which tells the group's encoder for all streams at once
@@ -1161,7 +724,7 @@ static bool bmode_write_au(x264_t *h, x264_t::PicPlan &f, std::vector<int> &type
     types.clear();
     const bool sets = bmode_open_au(h, f, types);
     h->last_stats.skip = 0;
-    write_slices(h->out, h->nal_off, types, f.sp, h->slices, mbs, levels, h->param.b_annexb != 0, f.pl.type == PIC_IDR, &h->last_stats, h->cavlc_threads);
+    write_slices(h->out, h->nal_off, types, f.sp, h->set.slices, mbs, levels, h->param.b_annexb != 0, f.pl.type == PIC_IDR, &h->last_stats, h->set.cavlc_threads);
     return sets;
 }
 // ... second half: the written access unit is the picture's
@@ -1174,19 +737,19 @@ static int bmode_finish_written(x264_t *h, x264_t::PicPlan &f, std::vector<int> 
     // x264_ratecontrol_end; a session that writes statistics or follows a plan is told what the picture's macroblocks were
     RateControl::PicStats ps;
     if (h->rc.pass1 || h->rc.pass2) {
-        for (size_t i = 0; i < (size_t)h->nmb; i++) {
+        for (size_t i = 0; i < (size_t)h->set.nmb; i++) {
             const x264gpu_mb &m = mbs[i];
             if (m.type <= X264GPU_MB_I16x16) ps.imb++; else if (m.type == X264GPU_MB_P_SKIP || m.type == X264GPU_MB_B_SKIP) ps.smb++; else ps.pmb++;
         }
-        ps.aq_mean = mean_mb_qp(mbs, (size_t)h->nmb); ps.mv_bits = h->last_stats.mv_bits; ps.tex_bits = h->last_stats.tex_bits; ps.direct = h->last_direct_char;
+        ps.aq_mean = mean_mb_qp(mbs, (size_t)h->set.nmb); ps.mv_bits = h->last_stats.mv_bits; ps.tex_bits = h->last_stats.tex_bits; ps.direct = h->last_direct_char;
     }
     const int filler = h->rc.end(h->out.size(), pl.type, pl.e.frame, f.qpf, &ps);
     if (filler > 0) { h->nal_off.push_back(h->out.size()); types.push_back(12); write_filler(h->out, filler - h->rc.filler_overhead(), p.b_annexb != 0); }          // --nal-hrd cbr: what the buffer cannot hold
-    if (h->vbv) { h->last_vbv.fill_after = h->rc.buffer_fill_final; h->last_vbv.filler = filler; h->last_vbv.qp_final = f.qpf; h->hrd_pics_since_bp = idr ? 1 : h->hrd_pics_since_bp + 1; }
+    if (h->set.vbv) { h->last_vbv.fill_after = h->rc.buffer_fill_final; h->last_vbv.filler = filler; h->last_vbv.qp_final = f.qpf; h->hrd_pics_since_bp = idr ? 1 : h->hrd_pics_since_bp + 1; }
     publish_nals(h, pp_nal, pi_nal, types);
     for (size_t i = 0; i < h->nals.size(); i++) if (types[i] == 1 || types[i] == 5) h->nals[i].i_ref_idc = f.nal_ref_idc;
     fill_pic_out(pic_out, x264_type_of(pl.type), idr, pl.e.pts, coded_dts(h, h->coded_count), &pl.e.img);
-    if (h->ql.flags) h->ql.frame_end(p, h->hq[0], quality_type(pl.type), mean_mb_qp(mbs, (size_t)h->nmb), f.pic.poc, h->out.size());          // (h->hq[0]: downloaded with the records)
+    if (h->ql.flags) h->ql.frame_end(p, h->hq[0], quality_type(pl.type), mean_mb_qp(mbs, (size_t)h->set.nmb), f.pic.poc, h->out.size());          // (h->hq[0]: downloaded with the records)
     bmode_count(h, idr);
     return (int)h->out.size();
 }
@@ -1237,9 +800,9 @@ static int bmode_defer(x264_t *h, x264_t::PicPlan &f, int bbuf, x264_nal_t **pp_
     x264_t::Deferred &d = h->defer[h->defer_cur];
     if (d.th.joinable()) d.th.join();          // (handed out two calls ago: long finished)
     d.out = h->out; d.off = h->nal_off; d.types = types; d.err.clear(); d.nal_ref_idc = f.nal_ref_idc; d.stats = SliceStats{ 0 };
-    d.mb.resize((size_t)h->nmb);
-    if (h->batch.packed()) d.ix.resize((size_t)h->nmb);
-    if (!d.lv) d.lv.reset(new (std::nothrow) int16_t[(size_t)h->nmb * X264GPU_MB_LEVELS]);
+    d.mb.resize((size_t)h->set.nmb);
+    if (h->batch.packed()) d.ix.resize((size_t)h->set.nmb);
+    if (!d.lv) d.lv.reset(new (std::nothrow) int16_t[(size_t)h->set.nmb * X264GPU_MB_LEVELS]);
     if (!d.lv) { xlog(&p, X264_LOG_ERROR, "x264_encoder_encode: out of memory (download buffers)\n"); h->failed = true; return -1; }
     d.i_type = x264_type_of(pl.type); d.b_keyframe = idr; d.pts = pl.e.pts; d.img = pl.e.img;
     d.qp = f.pic.qp; d.qpm = f.pic.qpm; d.scenecut = pl.e.scenecut; memcpy(d.costs, pl.e.costs, sizeof(d.costs));
@@ -1248,7 +811,7 @@ static int bmode_defer(x264_t *h, x264_t::PicPlan &f, int bbuf, x264_nal_t **pp_
     d.dts = coded_dts(h, h->coded_count);
     Batch *b = &h->batch;
     const SliceParams sp = f.sp;
-    const int slices = h->slices, threads = h->cavlc_threads, dev = h->device;
+    const int slices = h->set.slices, threads = h->set.cavlc_threads, dev = h->device;
     const bool annexb = p.b_annexb != 0;
     const long my_launched = b->launched();
     d.hurry = false;
@@ -1304,7 +867,7 @@ static int encode_bmode(x264_t *h, x264_nal_t **pp_nal, int *pi_nal, x264_pictur
             h->failed = true;
             return -1;
         }
-        if (!h->vbv) break;
+        if (!h->set.vbv) break;
         // the VBV's re-encode guard: the picture's exact size is known once its slices are written; one that would under-run the buffer (x264_ratecontrol_end's
         // "VBV underflow") is issued again — same x264gpu_pic, destination slot and source, which the device contract allows before any later picture — at a
         // quantiser raised by what its size asks for: bits fall roughly as 1 / qscale, and qscale doubles every 6.  The rate control's running state stays as
@@ -1336,7 +899,7 @@ static int encode_bmode(x264_t *h, x264_nal_t **pp_nal, int *pi_nal, x264_pictur
             fwrite(&f.pic, sizeof(f.pic), 1, fp);
             fwrite(h->h_mb.data(), sizeof(x264gpu_mb), h->h_mb.size(), fp);
             fwrite(h->h_lv.data(), sizeof(int16_t), h->h_lv.size(), fp);
-            std::vector<float> off((size_t)h->nmb, 0.f);          // ... and the per-macroblock quantiser offsets it was coded with (zeros: none handed in)
+            std::vector<float> off((size_t)h->set.nmb, 0.f);          // ... and the per-macroblock quantiser offsets it was coded with (zeros: none handed in)
             if (f.d_offsets) x264gpu_memcpy_d2h(off.data(), f.d_offsets, off.size() * sizeof(float), nullptr);
             fwrite(off.data(), sizeof(float), off.size(), fp);
             fclose(fp);
@@ -1346,7 +909,7 @@ static int encode_bmode(x264_t *h, x264_nal_t **pp_nal, int *pi_nal, x264_pictur
         // x264_encoder_frame_end ("somewhat arbitrary time constants"): the running counts decay once they exceed a picture's worth, then take this picture's
         int sc[2] = { 0, 0 };
         if (x264gpu_encoder_direct_scores(h->gpu, sc) != X264GPU_OK) { xlog(&p, X264_LOG_ERROR, "direct auto: %s\n", x264gpu_last_error()); h->failed = true; return -1; }
-        if (h->direct_score[0] + h->direct_score[1] > h->mbw * h->mbh) for (int i = 0; i < 2; i++) h->direct_score[i] = h->direct_score[i] * 9 / 10;
+        if (h->direct_score[0] + h->direct_score[1] > h->set.mbw * h->set.mbh) for (int i = 0; i < 2; i++) h->direct_score[i] = h->direct_score[i] * 9 / 10;
         for (int i = 0; i < 2; i++) h->direct_score[i] += sc[i];
     }
     int size;
@@ -1462,7 +1025,7 @@ static int encode_bmode_inflight(x264_t *h, x264_nal_t **pp_nal, int *pi_nal, x2
     // ... and hand back the oldest picture once `inflight` pictures are out (x264's frame threads: i_thread_frames - 1 more calls of delay), when a decided picture
     // waits for a context or a slot, or when the input has ended; else this call returns nothing (a delayed frame).  The pictures behind the oldest keep running:
     // in the steady state a call issues one picture and waits for one that was issued inflight - 1 calls ago.
-    if (!(flushing || (int)h->fl.size() >= h->inflight || !h->slicetype.queue().empty())) return 0;
+    if (!(flushing || (int)h->fl.size() >= h->set.inflight || !h->slicetype.queue().empty())) return 0;
     return inflight_retire(h, pp_nal, pi_nal, pic_out);
 }
 
@@ -1472,9 +1035,9 @@ int x264_encoder_encode(x264_t *h, x264_nal_t **pp_nal, int *pi_nal, x264_pictur
     *pi_nal = 0; *pp_nal = nullptr;
     if (h->failed) return -1;
     if (!pic_in) {      // flush: GOP-parallel batches, or the pictures still waiting in the lookahead queue, one per call
-        if (h->slots_rc) return encode_slots_rc(h, pp_nal, pi_nal, pic_out, true);
-        if (h->G > 1) return encode_gop_slots(h, pp_nal, pi_nal, nullptr, pic_out, false);
-        if (h->dpbmode) return h->inflight > 1 ? encode_bmode_inflight(h, pp_nal, pi_nal, pic_out, true) : encode_bmode(h, pp_nal, pi_nal, pic_out, true);
+        if (h->set.slots_rc) return encode_slots_rc(h, pp_nal, pi_nal, pic_out, true);
+        if (h->set.G > 1) return encode_gop_slots(h, pp_nal, pi_nal, nullptr, pic_out, false);
+        if (h->set.dpbmode) return h->set.inflight > 1 ? encode_bmode_inflight(h, pp_nal, pi_nal, pic_out, true) : encode_bmode(h, pp_nal, pi_nal, pic_out, true);
         return h->queue.empty() ? 0 : encode_queued(h, pp_nal, pi_nal, pic_out, true);
     }
     const x264_param_t &p = h->param;
@@ -1486,7 +1049,7 @@ int x264_encoder_encode(x264_t *h, x264_nal_t **pp_nal, int *pi_nal, x264_pictur
     // Zero-copy input (x264gpu_host_input_i420): the caller (the VfW shell after the device-side colourspace conversion)
     // already placed a tight I420 picture in the encoder's device staging buffer.
     const bool resident = pic_in->img.plane[0] == h->d_in;
-    if (h->slots_rc && h->gops.was_flushed()) { xlog(&p, X264_LOG_ERROR, "x264_encoder_encode: pictures after a flush are not supported in GOP-parallel mode\n"); return -1; }
+    if (h->set.slots_rc && h->gops.was_flushed()) { xlog(&p, X264_LOG_ERROR, "x264_encoder_encode: pictures after a flush are not supported in GOP-parallel mode\n"); return -1; }
     auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     double t0 = now(), t1;
 #define PHASE(i) do { t1 = now(); h->t_phase[i] += t1 - t0; t0 = t1; } while (0)
@@ -1497,11 +1060,11 @@ int x264_encoder_encode(x264_t *h, x264_nal_t **pp_nal, int *pi_nal, x264_pictur
         const uint8_t *src = pic_in->img.plane[pl];
         for (int y = 0; y < ph; y++, dst += pw, src += pic_in->img.i_stride[pl]) memcpy(dst, src, pw);
     }
-    if (h->G > 1 && !h->slots_rc) return encode_gop_slots(h, pp_nal, pi_nal, pic_in, pic_out, resident);
+    if (h->set.G > 1 && !h->set.slots_rc) return encode_gop_slots(h, pp_nal, pi_nal, pic_in, pic_out, resident);
     PHASE(0);
     // ---- the picture enters the lookahead queue (x264_lookahead_put_frame): upload, frame cost against the previous source picture,
     //      AQ offsets, slice-type decision (keyint / forced type / scenecut) — all causal, so they are taken on arrival ----
-    const int slot = (int)(h->la_count % h->Q);
+    const int slot = (int)(h->la_count % h->set.Q);
     uint8_t *d_raw = h->q_raw[(size_t)slot];
     void *const up = h->batch.upload_stream();          // (a batch session's: its pictures go up while the group's round runs on the compute stream)
     if ((!resident && x264gpu_memcpy_h2d(d_raw, h->h_in.data(), h->h_in.size(), up) != X264GPU_OK) ||
@@ -1511,16 +1074,16 @@ int x264_encoder_encode(x264_t *h, x264_nal_t **pp_nal, int *pi_nal, x264_pictur
     }
     x264_t::QEntry e = {};
     e.pts = pic_in->i_pts; e.slot = slot; e.img = pic_in->img;
-    bool idr = h->la_count == 0 || h->la_gop >= h->keyint || pic_in->i_type == X264_TYPE_IDR || pic_in->i_type == X264_TYPE_KEYFRAME, intra_pic = false;
+    bool idr = h->la_count == 0 || h->la_gop >= h->set.keyint || pic_in->i_type == X264_TYPE_IDR || pic_in->i_type == X264_TYPE_KEYFRAME, intra_pic = false;
     if (h->la) {
         if (h->tstats.reading) {          // (no frame costs: this session's lookahead object runs the AQ kernel alone)
-            if (h->aq_strength != 0.f && x264gpu_lookahead_aq_offsets_mode(h->la, d_raw, h->aq_mode >= 2 ? h->aq_mode : 1, h->aq_strength, h->q_aq[(size_t)slot], nullptr) != X264GPU_OK) {
+            if (h->set.aq_strength != 0.f && x264gpu_lookahead_aq_offsets_mode(h->la, d_raw, h->set.aq_mode >= 2 ? h->set.aq_mode : 1, h->set.aq_strength, h->q_aq[(size_t)slot], nullptr) != X264GPU_OK) {
                 xlog(&p, X264_LOG_ERROR, "x264_encoder_encode: lookahead failed: %s\n", x264gpu_last_error());
                 return -1;
             }
         } else
-        if (x264gpu_lookahead_frame_cost(h->la, d_raw, h->la_count == 0, h->d_la, h->mbtree ? h->q_info[(size_t)slot] : nullptr, nullptr) != X264GPU_OK ||
-            ((h->mbtree || h->slicetype.aq_costs || h->aq_mode >= 2) && h->aq_strength != 0.f && x264gpu_lookahead_aq_offsets_mode(h->la, d_raw, h->aq_mode >= 2 ? h->aq_mode : 1, h->aq_strength, h->q_aq[(size_t)slot], nullptr) != X264GPU_OK) ||
+        if (x264gpu_lookahead_frame_cost(h->la, d_raw, h->la_count == 0, h->d_la, h->set.mbtree ? h->q_info[(size_t)slot] : nullptr, nullptr) != X264GPU_OK ||
+            ((h->set.mbtree || h->slicetype.aq_costs || h->set.aq_mode >= 2) && h->set.aq_strength != 0.f && x264gpu_lookahead_aq_offsets_mode(h->la, d_raw, h->set.aq_mode >= 2 ? h->set.aq_mode : 1, h->set.aq_strength, h->q_aq[(size_t)slot], nullptr) != X264GPU_OK) ||
             x264gpu_memcpy_d2h(e.costs, h->d_la, sizeof(e.costs), nullptr) != X264GPU_OK) {
             xlog(&p, X264_LOG_ERROR, "x264_encoder_encode: lookahead failed: %s\n", x264gpu_last_error());
             return -1;
@@ -1528,7 +1091,7 @@ int x264_encoder_encode(x264_t *h, x264_nal_t **pp_nal, int *pi_nal, x264_pictur
         if (!idr && p.i_scenecut_threshold > 0 && h->la_count > 0 && !h->tstats.reading) {
             // scenecut_internal: the bias grows with the distance from the last keyframe.  A cut at or beyond min-keyint becomes
             // an IDR picture, one inside min-keyint an I picture that keeps the references (x264_slicetype_decide).
-            const int gop = h->la_gop, kmin = h->keyint_min, kmax = h->keyint;
+            const int gop = h->la_gop, kmin = h->set.keyint_min, kmax = h->set.keyint;
             const double tmax = p.i_scenecut_threshold / 100.0, tmin = kmin == kmax ? tmax : tmax * 0.25;
             double bias;
             if (gop <= kmin / 4) bias = tmin / 4;
@@ -1541,7 +1104,7 @@ int x264_encoder_encode(x264_t *h, x264_nal_t **pp_nal, int *pi_nal, x264_pictur
     e.type = idr ? 2 : intra_pic ? 1 : 0;
     h->la_gop = idr ? 1 : h->la_gop + 1;
     h->la_count++;
-    if (h->dpbmode) {
+    if (h->set.dpbmode) {
         SliceType::Frame be = {};
         be.pts = e.pts; be.frame = (int)(h->la_count - 1); be.slot = slot; be.forced = e.type; be.scenecut = e.scenecut; be.img = e.img;
         memcpy(be.costs, e.costs, sizeof(e.costs));
@@ -1552,14 +1115,14 @@ int x264_encoder_encode(x264_t *h, x264_nal_t **pp_nal, int *pi_nal, x264_pictur
         }
         h->all_pts.push_back(e.pts);
         PHASE(1);
-        const int size = h->slots_rc ? encode_slots_rc(h, pp_nal, pi_nal, pic_out, false) : h->inflight > 1 ? encode_bmode_inflight(h, pp_nal, pi_nal, pic_out, false) : encode_bmode(h, pp_nal, pi_nal, pic_out, false);
+        const int size = h->set.slots_rc ? encode_slots_rc(h, pp_nal, pi_nal, pic_out, false) : h->set.inflight > 1 ? encode_bmode_inflight(h, pp_nal, pi_nal, pic_out, false) : encode_bmode(h, pp_nal, pi_nal, pic_out, false);
         PHASE(4);
         h->t_phase[5] += 1;
         return size;
     }
     h->queue.push_back(e);
     PHASE(1);
-    if ((int)h->queue.size() <= h->L) return 0;                        // still filling the lookahead: no picture yet (codec.c:1693, size 0)
+    if ((int)h->queue.size() <= h->set.L) return 0;                        // still filling the lookahead: no picture yet (codec.c:1693, size 0)
     const int size = encode_queued(h, pp_nal, pi_nal, pic_out, false);
     PHASE(4);
     h->t_phase[5] += 1;
@@ -1567,7 +1130,7 @@ int x264_encoder_encode(x264_t *h, x264_nal_t **pp_nal, int *pi_nal, x264_pictur
     return size;
 }
 
-int x264_encoder_delayed_frames(x264_t *h) { return !h || h->failed ? 0 : h->slots_rc ? h->slicetype.delayed() + h->gops.delayed() : h->G > 1 ? h->gops.delayed() : h->dpbmode ? h->slicetype.delayed() + (int)h->fl.size() + (h->defer[0].valid ? 1 : 0) + (h->defer[1].valid ? 1 : 0) : (int)h->queue.size(); }
+int x264_encoder_delayed_frames(x264_t *h) { return !h || h->failed ? 0 : h->set.slots_rc ? h->slicetype.delayed() + h->gops.delayed() : h->set.G > 1 ? h->gops.delayed() : h->set.dpbmode ? h->slicetype.delayed() + (int)h->fl.size() + (h->defer[0].valid ? 1 : 0) + (h->defer[1].valid ? 1 : 0) : (int)h->queue.size(); }
 
 void x264_encoder_close(x264_t *h)
 {
@@ -1785,8 +1348,8 @@ int x264host_write_headers_b(int width, int height, int level_idc, int log2_max_
  * equals this pointer is encoded in place, without the host copy-in and upload (used by the VfW shell, vfw.cpp). */
 uint8_t *x264gpu_host_input_i420(x264_t *h) { return h ? h->d_in : nullptr; }
 
-long x264host_gop_slots_planned(x264_t *h) { return h && h->slots_rc ? h->gops.planned() : 0; }
-int x264host_gop_slots_recon(x264_t *h, int slot, uint8_t *i420_out) { return h && h->G > 1 && i420_out ? h->gops.recon(slot, i420_out) : -1; }
+long x264host_gop_slots_planned(x264_t *h) { return h && h->set.slots_rc ? h->gops.planned() : 0; }
+int x264host_gop_slots_recon(x264_t *h, int slot, uint8_t *i420_out) { return h && h->set.G > 1 && i420_out ? h->gops.recon(slot, i420_out) : -1; }
 
 int x264host_last_decision(x264_t *h, int *qp, int *scenecut, int32_t costs[4])
 {
@@ -1801,7 +1364,7 @@ int x264host_last_decision(x264_t *h, int *qp, int *scenecut, int32_t costs[4])
  * returns the number of pictures planned (0: not a second pass) */
 int x264host_last_vbv(x264_t *h, double out[12], int *planned_type, int *planned_satd, int cap)
 {
-    if (!h || !h->vbv || !h->last_vbv.valid) return -1;
+    if (!h || !h->set.vbv || !h->last_vbv.valid) return -1;
     const x264_t::VbvInfo &v = h->last_vbv;
     if (out) {
         const double o[12] = { v.fill_before, v.fill_after, v.qp_novbv, v.qp_clipped, v.frame_size_planned, (double)v.attempts, (double)v.filler, v.qp_final,
@@ -1825,7 +1388,7 @@ int x264host_pass2_plan(x264_t *h, double *new_qscale, double *expected_bits, in
 /* tests: the float quantiser (x264 rc->qpm) the last coded picture's macroblock quantisers were rounded from; 0 = its integer quantiser */
 float x264host_last_qpm(x264_t *h) { return h ? h->last_qpm : 0.f; }
 
-int x264host_pictures_in_flight(x264_t *h) { return h ? h->inflight : 0; }
+int x264host_pictures_in_flight(x264_t *h) { return h ? h->set.inflight : 0; }
 
 int x264host_last_quality(x264_t *h, double psnr[4], double *ssim, uint64_t ssd[3])
 {
@@ -1845,7 +1408,7 @@ int x264host_nr_offsets(x264_t *h, uint16_t out[3][64])
 
 int x264host_last_mb_qp_offsets(x264_t *h, float *dst, int n)
 {
-    if (!h || !dst || n != h->nmb) return -1;
+    if (!h || !dst || n != h->set.nmb) return -1;
     if (!h->last_offsets) return 0;
     if (x264gpu_stream_sync(nullptr) != X264GPU_OK || x264gpu_memcpy_d2h(dst, h->last_offsets, (size_t)n * sizeof(float), nullptr) != X264GPU_OK) return -1;
     return n;
@@ -1868,7 +1431,7 @@ int x264host_get_recon(x264_t *h, uint8_t *i420_out)
     uint8_t *d = nullptr;
     if (x264gpu_malloc((void **)&d, n) != X264GPU_OK) return -1;
     // (several pictures in flight: the picture handed back last — its slot is not reused before the next call issues a picture)
-    int rc = h->inflight > 1 && h->last_retired_slot >= 0 ? x264gpu_encoder_get_recon_slot(h->gpu, 0, h->last_retired_slot, d, nullptr) : x264gpu_encoder_get_recon(h->gpu, 0, d, nullptr);
+    int rc = h->set.inflight > 1 && h->last_retired_slot >= 0 ? x264gpu_encoder_get_recon_slot(h->gpu, 0, h->last_retired_slot, d, nullptr) : x264gpu_encoder_get_recon(h->gpu, 0, d, nullptr);
     if (rc == X264GPU_OK) rc = x264gpu_memcpy_d2h(i420_out, d, n, nullptr);
     x264gpu_free(d);
     return rc;

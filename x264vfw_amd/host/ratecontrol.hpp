@@ -11,7 +11,7 @@
 namespace x264host {
 
 struct RateControl {
-    // which rate control the session runs (session policy: set by x264_encoder_open before open()); none: constant quantiser
+    // which rate control the session runs (session policy: set by Settings::settle, host/settings.hpp, before open()); none: constant quantiser
     bool crf = false, abr = false;       // single pass: the quantisers follow the lookahead's frame costs (ABR: and the coded sizes)
     bool pass1 = false, pass2 = false;   // a statistics line per coded picture; every quantiser planned from the first pass' statistics
     // the macroblock-tree statistics file (host/mbtreestats.hpp; session policy as well): a first pass that writes it says so in the statistics' header; a second
@@ -19,7 +19,7 @@ struct RateControl {
     bool tree_write = false, tree_read = false;
     bool by_cost() const { return crf || abr; }
     bool reads_sizes() const { return abr || pass1 || pass2 || vbv; }          // end() feeds start(): such a session codes one picture at a time
-    // VBV (session policy as well: x264_encoder_open validates --vbv-maxrate / --vbv-bufsize / --vbv-init / --nal-hrd and leaves the effective values in the parameters)
+    // VBV (session policy as well: Settings::settle validates --vbv-maxrate / --vbv-bufsize / --vbv-init / --nal-hrd and leaves the effective values in the parameters)
     bool vbv = false, vbv_lookahead = false;          // vbv_lookahead: rc-lookahead > 0, every I / P picture comes with the planned types and costs of the pictures behind it
     bool filler = false;                              // --nal-hrd cbr: what the buffer cannot hold is sent as filler (end() says how many bytes)
     int hrd_rate = 0, hrd_size = 0;                   // --nal-hrd: the rate and size the HRD signals (value << scale: what is left of the request), which the VBV then runs on; 0: as asked
