@@ -113,6 +113,16 @@ int x264gpu_trellis_blocks_ex(const int16_t *d_coefs, int nblk, int cat, int qp,
  * strength of 0 give what x264gpu_trellis_blocks_ex gives (d_fenc_dct is then not read and may be NULL). */
 int x264gpu_trellis_blocks_psy(const int16_t *d_coefs, const int16_t *d_fenc_dct, int nblk, int cat, int qp, int intra, int psy_trellis_q8, const uint8_t *d_states460,
                                int16_t *d_levels, uint8_t *d_nz, int force_general, uint8_t *d_paths, void *stream);
+/* x264's QP-RD walk (--subme 10, mb_analyse_qp_rd; csrc/qprd.hip.h) as a primitive: n problems, one thread each, over tables instead of encodes.  Per problem p:
+ * d_cost[p][52] = the RD cost of the macroblock coded at quantiser q, d_empty[p][52] != 0 = that encode codes nothing (cbp_empty), d_cost_flip[p][52] = the cost at q
+ * with the other transform size; d_orig_qp[p] the macroblock's own quantiser, d_last_qp[p] the previous coded macroblock's (both 0..51), d_t8_eligible[p] != 0 =
+ * the transform size may be chosen.  Shared: qp_min <= qp_max within 0..51, psy (psy-rd on: one more failure is tolerated).  Out: d_qp[p] the chosen quantiser,
+ * d_flip[p] 1 = the transform size changes, d_n_asked[p] the number of encodes the walk asked for and d_asked[p][X264GPU_QPRD_ASKED_MAX] their quantisers in
+ * order (+ 256: with the other transform size).  tests/qprd_ref.py is the walk's Python twin. */
+#define X264GPU_QPRD_ASKED_MAX 64
+int x264gpu_qprd_walk(const int32_t *d_cost, const uint8_t *d_empty, const int32_t *d_cost_flip, const int32_t *d_orig_qp, const int32_t *d_last_qp,
+                      const int32_t *d_t8_eligible, int n, int qp_min, int qp_max, int psy, int32_t *d_qp, int32_t *d_flip, int32_t *d_asked, int32_t *d_n_asked,
+                      void *stream);
 int x264gpu_mc_weight(const uint8_t *d_src, size_t bytes, int scale, int denom, int offset, uint8_t *d_out, void *stream);
 /* Rows that lie anywhere in device memory into one contiguous array, in one launch on `stream`: row r of d_dst ([rows][row_bytes]) becomes a copy of the row_bytes
  * bytes at d_rows[r]; a NULL d_rows[r] gives a row of zeros.  d_rows itself is a DEVICE array of `rows` device pointers, read when the kernel runs.  Any row_bytes
@@ -288,6 +298,13 @@ typedef struct x264gpu_config {
                                * Every luma trellis site that is not a DC block (Intra_16x16 AC, 4x4, 8x8) searches with the psy term against the transform
                                * of the source block, which the macroblock loop works out once per macroblock.  Non-zero needs trellis, cabac, rd and
                                * me_method 1 or 2 (the psy search runs in kernel instantiations of its own, built for --me hex / umh) */
+    int qp_rd;                /* 1: x264's QP-RD (--subme 10, i_mbrd 3; mb_analyse_qp_rd): once a macroblock's type, partition, transform size, vectors and intra modes
+                               * are final it is coded at neighbouring quantisers as well — lambdas held — and keeps the one with the lowest RD cost; an inter macroblock
+                               * that changed quantiser then tries the other transform size.  P_SKIP / B_SKIP macroblocks are left alone.  0 = nothing changes.
+                               * Needs cabac, rd with refinement sites (63 / 63 | 64), subme 9 or 10, trellis 127 (--trellis 2 at every site) and me_method 1 or 2; not with psy_trellis_q8 nor with
+                               * x264gpu_encoder_set_nr (the walk runs in kernel instantiations of its own).  Every macroblock's quantiser then goes through the
+                               * QP_Y inheritance pass, as under AQ */
+    int qp_min, qp_max;       /* the quantisers QP-RD may choose (x264 rc.i_qp_min, min(rc.i_qp_max, 51)); both 0 = 1 .. 51 */
 } x264gpu_config;
 
 /* One picture of one stream for x264gpu_encode_pictures: slice type, quantiser and the reference lists as DPB slots — what x264's
@@ -323,6 +340,13 @@ typedef struct x264gpu_pic {
 /* --direct auto: h_scores[streams][2] = how many macroblocks of the last B picture coded with direct_auto the skip probe passed under temporal [0] /
  * spatial [1] direct prediction (x264 h->stat.frame.i_direct_score) */
 int  x264gpu_encoder_direct_scores(x264gpu_encoder *enc, int *h_scores);
+/* QP-RD sessions (cfg.qp_rd): d_log = a device buffer [streams][mb_count][X264GPU_QPRD_LOG_WORDS] of 32-bit words that the following encode calls of this launch
+ * context fill, or NULL (the default: no log).  A macroblock's entry: word 0 = n, the encodes its walk asked for (0: no walk — a skipped macroblock); word 1 =
+ * orig_qp | last_qp << 8 | chosen qp << 16 | flip << 24 (flip: the transform size changed after the walk); then n pairs in the order asked:
+ * q | cbp_empty << 8 | (coded with the other transform size) << 16, and the RD cost.  n <= X264GPU_QPRD_LOG_SAMPLES (a longer walk logs its first ones). */
+#define X264GPU_QPRD_LOG_WORDS 128
+#define X264GPU_QPRD_LOG_SAMPLES 63
+int  x264gpu_encoder_set_qprd_log(x264gpu_encoder *enc, uint32_t *d_log);
 int  x264gpu_encoder_create(x264gpu_encoder **enc, const x264gpu_config *cfg);
 /* A second LAUNCH CONTEXT over `parent`'s DPB (x264gpu_encode_pictures sessions): the picture slots and their side data are the parent's, the per-launch scratch
  * the view's own.  Pictures of one session that share only finished references — the b pictures of a mini-GOP, the next P picture, the B reference between two
@@ -414,7 +438,8 @@ int  x264gpu_encoder_profile_begin(x264gpu_encoder *enc, int max_calls);
 int  x264gpu_encoder_set_debug(x264gpu_encoder *enc, void *d_counters);
 /* diagnostics: the instantiations of the macroblock loop (k_mb_slice<M, ME, PS, RD, BS, PSY, NR>) this process has launched since the last reset, whichever
  * encoder launched them: up to `max` distinct ids into ids[] in the order of their first launch (ids may be NULL with max 0), the return value is their
- * number; reset != 0 empties the set afterwards.  An id spells the template tuple in hex digits: M << 12 | ME << 8 | RD << 4 | PS << 3 | BS << 2 | PSY << 1 | NR.
+ * number; reset != 0 empties the set afterwards.  An id spells the template tuple in hex digits: M << 12 | ME << 8 | RD << 4 | PS << 3 | BS << 2 | PSY << 1 | NR;
+ * bit 16 on top: the QP-RD instantiation of the tuple (cfg.qp_rd).
  * Host side only (a launch notes its id before it is queued); thread-safe. */
 int  x264gpu_mb_kernels_seen(uint32_t *ids, int max, int reset);
 int  x264gpu_encoder_profile_end(x264gpu_encoder *enc, void *stream, double *ms_sum, int *launches);

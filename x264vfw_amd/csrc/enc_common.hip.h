@@ -100,6 +100,9 @@ struct EncK {
     // x264 --nr (x264gpu_encoder_set_nr; behind everything else: no other field moves): non-null = the denoising instantiations of the macroblock loop (mb_slice_nr_*.hip).
     // nr_off[streams] the offsets they apply, nr_part[streams][slices] the statistics of every slice's final encodes (each slice's wavefront owns its row)
     const x264gpu_nr_offsets *nr_off; x264gpu_nr_sums *nr_part;
+    // x264 --subme 10 (cfg.qp_rd; behind everything else again): non-zero = the QP-RD instantiations of the macroblock loop (qprd_slice_*.hip), which walk the
+    // quantisers qprd_min .. qprd_max around every coded macroblock's own (qprd.hip.h); qprd_log: null, or [streams][nmb][QPRD_LOG_WORDS] — what each walk asked and got
+    int qp_rd, qprd_min, qprd_max; uint32_t *qprd_log;
 };
 // the slice quantiser of stream s
 __device__ __forceinline__ int slice_qp(const EncK &k, int s) { return k.stream_qp ? (int)k.stream_qp[s] : k.qp; }

@@ -28,6 +28,7 @@ void launch_mb_slice_b_dia(const EncK &k, int streams, hipStream_t st);
 void launch_mb_slice_b_umh(const EncK &k, int streams, hipStream_t st);
 void launch_mb_slice_b_esa(const EncK &k, int streams, hipStream_t st);
 void launch_mb_slice_psy(const EncK &k, int streams, int slice_type, hipStream_t st);       // psy-trellis sessions (mb_slice_psy_*.hip): I, P and B slices, --me hex / umh
+void launch_mb_slice_qprd(const EncK &k, int streams, int slice_type, hipStream_t st);      // QP-RD sessions (cfg.qp_rd; qprd_slice_*.hip): I, P and B slices, --me hex / umh
 void launch_mb_slice_nr(const EncK &k, int streams, int slice_type, hipStream_t st);        // --nr (x264gpu_encoder_set_nr; mb_slice_nr_*.hip): P and B slices, --me hex / umh
 void launch_nr_gather(const x264gpu_nr_sums *part, int slices, x264gpu_nr_sums *pic, int streams, hipStream_t st);      // nr_kernels.hip
 int trellis_table_ptrs(const uint16_t **su, const uint8_t **tu, const int **l2);        // prim_kernels.hip
@@ -71,6 +72,7 @@ struct x264gpu_encoder {
     void *qslab = nullptr;               // x264gpu_encoder_quality: the workgroup partials of the pass (allocated by the first call)
     // --nr (x264gpu_encoder_set_nr): the caller's offsets and per-picture statistics ([streams] each; null = the plain kernels), this context's per-slice rows
     const x264gpu_nr_offsets *nr_off = nullptr; x264gpu_nr_sums *nr_pic = nullptr, *nr_part = nullptr;
+    uint32_t *qprd_log = nullptr;          // x264gpu_encoder_set_qprd_log: the caller's buffer (null = no log)
     // adaptive quantisation: per-macroblock quantisers and the per-quantiser tables (built when aq_mode != 0)
     uint8_t *mbqp = nullptr;
     const float *ext_off = nullptr;      // quantiser offsets handed in by the caller (lookahead), [streams][nmb] single floats
@@ -130,13 +132,17 @@ static int encoder_create_impl(x264gpu_encoder **out, const x264gpu_config *cfg,
     ARG_TRY(cfg->trellis == 0 || (cfg->trellis > 0 && cfg->trellis < 128 && (cfg->trellis & 63) && cfg->rd && cfg->cabac));      // trellis sites (mask; x264 --trellis 1 = 63, --trellis 2 = 63 + 64): RD sessions with CABAC
     // psy-trellis: the luma trellis sites of the hex / umh instantiations built for it (mb_slice_psy_*.hip)
     ARG_TRY(cfg->psy_trellis_q8 == 0 || (cfg->psy_trellis_q8 > 0 && cfg->psy_trellis_q8 <= 640 && cfg->trellis && cfg->cabac && cfg->rd && (cfg->me_method == 1 || cfg->me_method == 2)));
-    ARG_TRY(!cfg->rd || (cfg->subme >= 6 && cfg->subme <= 9 && cfg->psy_rd_q8 >= 0 && cfg->psy_rd_q8 <= 2560));      // RD: x264's i_mbrd 1 (bit counts of the session's entropy coder)
+    ARG_TRY(!cfg->rd || (cfg->subme >= 6 && cfg->subme <= (cfg->qp_rd ? 10 : 9) && cfg->psy_rd_q8 >= 0 && cfg->psy_rd_q8 <= 2560));      // RD: x264's i_mbrd 1 (bit counts of the session's entropy coder)
     // rd > 1: RD refinement of the chosen type (x264 subme 8, i_mbrd 2): bit 0 on + a mask of refinement sites in bits 1..5 (x264 = all five: 63); CABAC, hex / umh
     ARG_TRY(cfg->rd >= 0 && cfg->rd < 128 && (cfg->rd < 2 || (cfg->rd & 1)) && (!(cfg->rd & 62) || (cfg->cabac && cfg->subme >= 8 && (cfg->me_method == 1 || cfg->me_method == 2))));      // bit 6: deblock-aware RD (x264 subme 9)      // (rd 0 with subme >= 8: the sub-pel iteration table of those levels without RD, as before)
     // --subme 8 and up with RD: 4 half-pel + 10 quarter-pel iterations reach 4.5 samples from the full-pel vector — only the refinement instantiations stage
     // that neighbourhood (CABAC, hex / umh); B slices search that far from subme 9 on (one level down)
     ARG_TRY(!cfg->rd || cfg->subme < 8 || (cfg->cabac && (cfg->me_method == 1 || cfg->me_method == 2)));
-    ARG_TRY(!(cfg->rd & 64) || (cfg->cabac && (cfg->me_method == 1 || cfg->me_method == 2)));          // deblock-aware RD: in the refinement instantiations
+    ARG_TRY(!(cfg->rd & 64) || (cfg->cabac && (cfg->me_method == 1 || cfg->me_method == 2)));
+    // QP-RD (x264 --subme 10): in instantiations of its own (qprd_slice_*.hip), built for CABAC sessions with RD refinement and --trellis 2 under --me hex / umh,
+    // without psy-trellis; the quantisers it may choose: qp_min .. qp_max (both 0: 1 .. 51)
+    ARG_TRY(cfg->qp_rd == 0 || (cfg->qp_rd == 1 && cfg->cabac && (cfg->rd & 1) && (cfg->rd & 62) && cfg->subme >= 9 && (cfg->trellis & 127) == 127 && (cfg->me_method == 1 || cfg->me_method == 2) && !cfg->psy_trellis_q8));
+    ARG_TRY(cfg->qp_rd == 0 || (cfg->qp_min == 0 && cfg->qp_max == 0) || (cfg->qp_min >= 0 && cfg->qp_min <= cfg->qp_max && cfg->qp_max <= 51));          // deblock-aware RD: in the refinement instantiations
     ARG_TRY(cfg->dpb == 0 || cfg->subme < 9 || (cfg->rd && cfg->cabac && (cfg->me_method == 1 || cfg->me_method == 2)));
     ARG_TRY(cfg->slices >= 0 && (cfg->slices <= 1 || cfg->slices <= (cfg->height + 15) / 16 / (cfg->slices_plain ? 1 : 4)));      // x264 slice threads: at least four macroblock rows each; --slices N: one
     ARG_TRY(cfg->slices_plain == 0 || cfg->slices_plain == 1);
@@ -331,7 +337,7 @@ int x264gpu_encoder_set_nr(x264gpu_encoder *e, const x264gpu_nr_offsets *d_off, 
 {
     ARG_TRY(e && (d_off != nullptr) == (d_pic != nullptr));
     if (!d_off) { e->nr_off = nullptr; e->nr_pic = nullptr; return X264GPU_OK; }
-    ARG_TRY(e->cfg.cabac && e->cfg.rd && e->cfg.trellis && e->cfg.subme >= 6 && (e->cfg.me_method == 1 || e->cfg.me_method == 2) && e->cfg.dpb > 0 && !e->cfg.psy_trellis_q8);
+    ARG_TRY(e->cfg.cabac && e->cfg.rd && e->cfg.trellis && e->cfg.subme >= 6 && (e->cfg.me_method == 1 || e->cfg.me_method == 2) && e->cfg.dpb > 0 && !e->cfg.psy_trellis_q8 && !e->cfg.qp_rd);
     if (!e->nr_part) {
         const size_t n = (size_t)e->cfg.streams * (e->cfg.slices > 1 ? e->cfg.slices : 1) * sizeof(x264gpu_nr_sums);
         hipError_t er = hipMalloc((void **)&e->nr_part, n);
@@ -339,6 +345,13 @@ int x264gpu_encoder_set_nr(x264gpu_encoder *e, const x264gpu_nr_offsets *d_off, 
         if (er != hipSuccess) return set_err(er == hipErrorOutOfMemory ? X264GPU_ENOMEM : X264GPU_EHIP, "nr rows", er);
     }
     e->nr_off = d_off; e->nr_pic = d_pic;
+    return X264GPU_OK;
+}
+// QP-RD: the following encode calls of this launch context write what every macroblock's walk asked and got into d_log (null: no log)
+int x264gpu_encoder_set_qprd_log(x264gpu_encoder *e, uint32_t *d_log)
+{
+    ARG_TRY(e && (!d_log || e->cfg.qp_rd));
+    e->qprd_log = d_log;
     return X264GPU_OK;
 }
 int x264gpu_encoder_set_debug(x264gpu_encoder *e, void *d_counters) { ARG_TRY(e); e->dbg = (unsigned long long *)d_counters; return X264GPU_OK; }
@@ -583,6 +596,7 @@ static int encode_core(x264gpu_encoder *e, const uint8_t *d_i420, const x264gpu_
     k.sl_rerun = e->sl_rerun; k.sl_pass = 0;
     k.psy_trellis = e->cfg.psy_trellis_q8;
     k.nr_off = slice_type == X264GPU_SLICE_I ? nullptr : e->nr_off; k.nr_part = e->nr_part;          // (I slices hold no inter residual: the plain kernels)
+    k.qp_rd = e->cfg.qp_rd; k.qprd_min = e->cfg.qp_min || e->cfg.qp_max ? e->cfg.qp_min : 1; k.qprd_max = e->cfg.qp_min || e->cfg.qp_max ? e->cfg.qp_max : 51; k.qprd_log = e->qprd_log;
     k.trellis = e->cfg.trellis; k.tr_su = nullptr; k.tr_tu = nullptr; k.tr_l2 = nullptr;
     if (k.trellis) { const int rc = trellis_table_ptrs(&k.tr_su, &k.tr_tu, &k.tr_l2); if (rc != X264GPU_OK) return rc; }
     k.ctab = nullptr;
@@ -603,7 +617,7 @@ static int encode_core(x264gpu_encoder *e, const uint8_t *d_i420, const x264gpu_
     STAGE_MARK(0);
     hipLaunchKernelGGL(k_ingest, dim3((k.cw / 4 + 255) / 256, k.ch, S), dim3(256), 0, st, k);
     // per-macroblock quantisers: always materialised (the macroblock loop reads every quantiser-dependent value per macroblock)
-    const bool aq = e->cfg.aq_mode != 0 || e->ext_off != nullptr || e->use_stream_qp;
+    const bool aq = e->cfg.aq_mode != 0 || e->ext_off != nullptr || e->use_stream_qp || e->cfg.qp_rd;          // (QP-RD: macroblocks choose quantisers of their own)
     k.stream_qp = e->use_stream_qp ? e->stream_qp + (size_t)e->stream_qp_sel * e->cfg.streams : nullptr; k.stream_qpm = e->use_stream_qp ? e->stream_qpm + (size_t)e->stream_qp_sel * e->cfg.streams : nullptr;
     k.mbqp = e->mbqp; k.q4tab = e->q4tab; k.q8tab = e->q8tab; k.lambda_tab = e->lambda_tab; k.cost_all = e->cost_all; k.aq_strength = e->cfg.aq_strength; k.qp_snap = e->cfg.aq_mode != 0; k.qpm = pic.qpm != 0.f ? pic.qpm : (float)pic.qp;
     if (e->ext_off || !e->cfg.aq_mode) hipLaunchKernelGGL(k_apply_qp_offsets, dim3((k.nmb + 255) / 256, S), dim3(256), 0, st, k, e->ext_off);
@@ -611,11 +625,11 @@ static int encode_core(x264gpu_encoder *e, const uint8_t *d_i420, const x264gpu_
     mask |= 1;
     STAGE_MARK(1);
     // the macroblock loop: one wavefront per stream, raster order (sub-pel neighbourhood margin 2 px up to subme 7, 5 px above)
-    if (slice_type == X264GPU_SLICE_I) { if (k.psy_trellis) launch_mb_slice_psy(k, S, X264GPU_SLICE_I, st); else launch_mb_slice_intra(k, S, st); }        // (RD instantiations inside, chosen by k.rd)
+    if (slice_type == X264GPU_SLICE_I) { if (k.qp_rd) launch_mb_slice_qprd(k, S, X264GPU_SLICE_I, st); else if (k.psy_trellis) launch_mb_slice_psy(k, S, X264GPU_SLICE_I, st); else launch_mb_slice_intra(k, S, st); }        // (RD instantiations inside, chosen by k.rd)
     else {
         const auto launch_b = k.me_method == 0 ? launch_mb_slice_b_dia : k.me_method == 2 ? launch_mb_slice_b_umh : k.me_method == 3 ? launch_mb_slice_b_esa : launch_mb_slice_b_hex;
         const auto launch_p = k.me_method == 0 ? launch_mb_slice_dia : k.me_method == 2 ? launch_mb_slice_umh : k.me_method == 3 ? launch_mb_slice_esa : launch_mb_slice_hex;
-        const auto launch = [&](const EncK &kk, int streams, bool big_margin, hipStream_t s_) { if (kk.nr_off) launch_mb_slice_nr(kk, streams, bslice ? X264GPU_SLICE_B : X264GPU_SLICE_P, s_); else if (kk.psy_trellis) launch_mb_slice_psy(kk, streams, bslice ? X264GPU_SLICE_B : X264GPU_SLICE_P, s_); else if (bslice) launch_b(kk, streams, s_); else launch_p(kk, streams, big_margin, s_); };
+        const auto launch = [&](const EncK &kk, int streams, bool big_margin, hipStream_t s_) { if (kk.qp_rd) launch_mb_slice_qprd(kk, streams, bslice ? X264GPU_SLICE_B : X264GPU_SLICE_P, s_); else if (kk.nr_off) launch_mb_slice_nr(kk, streams, bslice ? X264GPU_SLICE_B : X264GPU_SLICE_P, s_); else if (kk.psy_trellis) launch_mb_slice_psy(kk, streams, bslice ? X264GPU_SLICE_B : X264GPU_SLICE_P, s_); else if (bslice) launch_b(kk, streams, s_); else launch_p(kk, streams, big_margin, s_); };
         if (k.sl_stat) hipLaunchKernelGGL(k_slice_priors, dim3((S + 63) / 64), dim3(64), 0, st, k, S, 1);
         launch(k, S, k.subme >= 8, st);
         // --slices N: slice i is final once slices 0..i-1 are, so slices - 1 rounds of "check the assumed counts, run the slices again whose

@@ -15,6 +15,7 @@
 #include "k_analyse.hip.h"
 #include "intra8.hip.h"
 #include "rd.hip.h"
+#include "qprd.hip.h"
 
 namespace x264gpu {
 
@@ -904,7 +905,10 @@ namespace x264gpu {
 // The trellis sites of a macroblock's FINAL encode (x264 --trellis 1; k.trellis = the mask of sites, 63 = all): what they need to run the
 // search of trellis.hip.h on the slice's live context variables (read only)
 enum { TR_P4 = 1, TR_P8 = 2, TR_C = 4, TR_I16 = 8, TR_I4 = 16, TR_I8 = 32 };
-struct TrCtx { int on; uint32_t r, r8, model; TrellisTab tt; static constexpr bool is_psy = false; };
+struct TrCtx { int on; uint32_t r, r8, model; TrellisTab tt; static constexpr bool is_psy = false; static constexpr bool is_lq = false; };
+// ... of the QP-RD instantiations (k_mb_slice's QPRD): a candidate quantiser's searches run under the trellis lambdas of the macroblock's OWN quantiser, which
+// lies dql (luma) / dqc (chroma) above the one the call site passes (0 outside the QP-RD phases)
+struct TrCtxQ : TrCtx { int dql = 0, dqc = 0; static constexpr bool is_lq = true; };
 // ... of the psy-trellis instantiations (k_mb_slice's PSY): + the transform of the macroblock's SOURCE samples, worked out once per macroblock (fd4: its
 // sixteen 4x4 blocks, 16 entries each in scan order, the block order of the levels; fd8: its four 8x8 blocks, 64 each), and x264's i_psy_trellis
 struct TrCtxPsy : TrCtx { const int16_t *fd4, *fd8; int psy; static constexpr bool is_psy = true; };
@@ -926,6 +930,9 @@ __device__ __forceinline__ unsigned trellis_run(const TR &tr, int16_t *coefs, in
             TrellisPsy<true> p;
             p.fstride = fstride == TR_FSTRIDE_SAME ? stride : fstride; p.fdct = (const lds_i16 *)(fd + b0 * p.fstride); p.q8 = tr.psy;
             out |= (trellis_blocks<CAT, false, true>((lds_i16 *)(coefs + b0 * stride), stride, min(8, nblk - b0), qp, intra, tr.model, tr.tt, CAT == 5 ? tr.r8 : tr.r, p) & 0xffu) << b0;
+        } else if constexpr (TR::is_lq) {
+            const int lq = qp + (CAT == 3 || CAT == 4 ? tr.dqc : tr.dql);
+            out |= (trellis_blocks<CAT, false, false, true>((lds_i16 *)(coefs + b0 * stride), stride, min(8, nblk - b0), qp | lq << 8, intra, tr.model, tr.tt, CAT == 5 ? tr.r8 : tr.r) & 0xffu) << b0;
         } else
             out |= (trellis_blocks<CAT>((lds_i16 *)(coefs + b0 * stride), stride, min(8, nblk - b0), qp, intra, tr.model, tr.tt, CAT == 5 ? tr.r8 : tr.r) & 0xffu) << b0;       // (bit 8: the levels-of-one loop ran)
     }
@@ -1379,8 +1386,9 @@ __device__ __forceinline__ int mb_intra_chroma_cost(const EncK &k, MbLds<M> &L, 
 // chroma residual with x264's variance early termination (oracle encode_chroma).  Lanes 0..31: plane = lane >> 4,
 // 4x4 block = (lane >> 2) & 3, row = lane & 3.
 // ------------------------------------------------------------------------------------------------
+template <class TR = TrCtx>          // (the context's own type: the QP-RD instantiations' carries the quantiser of the lambdas, which a TrCtx * would drop)
 __device__ __forceinline__ uint32_t mb_chroma_residual(uint32_t enc, uint32_t pred, const Q4 &q, bool inter, bool decimate, int lane, int16_t *lv,
-                                                       unsigned &nnz_bits, int &cbp_chroma, const TrCtx *tr = nullptr,
+                                                       unsigned &nnz_bits, int &cbp_chroma, const TR *tr = nullptr,
                                                        const uint16_t *nro = nullptr, uint16_t *nr_pend = nullptr)
 {
     // nro (the denoising instantiations, inter macroblocks only): the stream's offsets in LDS — the blocks are denoised before the 2x2 DC is taken out (its
@@ -1691,6 +1699,9 @@ __device__ __forceinline__ void b_predict(const EncK &k, const MbCtx &c, const B
 // BS: B slice (PS is set as well: an inter slice) — RD instantiations with CABAC only; its own analysis and candidate order (k_mb_b.inc)
 // PSY: psy-trellis (cfg.psy_trellis_q8 != 0; RD >= 3 only) — instantiations of their own (mb_slice_psy_*.hip): the source transform of every macroblock in
 // LDS (1 KB beside MbLds: these instantiations alone give up the eighth wavefront a CU) and the psy variant of the search at the luma sites
+// QPRD: x264 --subme 10 (cfg.qp_rd; RD 6 without PSY and NR) — instantiations of their own (qprd_slice_*.hip): where the decision machines say "commit", the decided
+// macroblock first goes through candidate passes at the quantisers the walk of qprd.hip.h asks for (lambdas held, the quantiser tables re-bound per pass), then is
+// committed at the one it chose.  Everything of it sits under `if constexpr (QPRD)` or folds away: the other instantiations compile to what they were
 // NR: x264 --nr (x264gpu_encoder_set_nr; RD >= 3 inter slices without PSY) — instantiations of their own (mb_slice_nr_*.hip): every inter residual the loop
 // transforms (final encodes, RD candidates, sub-block encodes of the refinement, skip probes) is denoised with the stream's offsets before it is quantised.  The
 // offsets in use are staged once per slice (96 of them, 192 B of LDS: with them the loop still fits eight wavefronts a CU).  Statistics take the FINAL encode of the inter macroblocks
@@ -1698,12 +1709,13 @@ __device__ __forceinline__ void b_predict(const EncK &k, const MbCtx &c, const B
 // committed) until its type is known, then lanes add their sums per index into the slice's own row of k.nr_part — 64-bit sums (a coefficient is below 2^15 and the largest picture,
 // 4096x2304, has 589 824 4x4 luma blocks: a sum stays below 2^35; 32 bits would wrap), no atomics: a row has one writer, entry i always through lane i, and a
 // repeated slice pass of --slices N starts its row again, so a macroblock's final encode counts exactly once
-template <int M, int ME, bool PS, int RD = 0, bool BS = false, bool PSY = false, bool NR = false>
+template <int M, int ME, bool PS, int RD = 0, bool BS = false, bool PSY = false, bool NR = false, bool QPRD = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MB_WAVES_PER_EU, 4))) void k_mb_slice(EncK k)
 {
+    static_assert(!QPRD || (RD == 6 && !PSY && !NR), "QP-RD: the refinement instantiations with --trellis 2, without psy-trellis and noise reduction");
     static_assert(!PSY || RD >= 3, "psy-trellis: instantiations with the trellis quantiser");
     static_assert(!NR || (RD >= 3 && PS && !PSY), "nr: inter slices of trellis sessions, without psy-trellis");
-    using TRC = std::conditional_t<PSY, TrCtxPsy, TrCtx>;
+    using TRC = std::conditional_t<PSY, TrCtxPsy, std::conditional_t<QPRD, TrCtxQ, TrCtx>>;
     __shared__ __attribute__((aligned(16))) int16_t psy_fd[PSY ? 512 : 1];          // (referenced in PSY instantiations only: the others allocate nothing)
     static_assert(!BS || PS, "B slices are inter slices");
     static_assert(RD != 7 || BS, "RD 7: B slices only");
@@ -1813,6 +1825,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MB_WAVES_PER
         c.nref = k.nref;
         const Q4 &q_li = k.q4tab[c.qp * 4 + 0], &q_lp = k.q4tab[c.qp * 4 + 1], &q_ci = k.q4tab[c.qpc * 4 + 2], &q_cp = k.q4tab[c.qpc * 4 + 3];
         const Q8 &q8i = k.q8tab[c.qp * 2 + 0], &q8p = k.q8tab[c.qp * 2 + 1];
+        const Q4 &o_li = q_li, &o_lp = q_lp, &o_ci = q_ci, &o_cp = q_cp;          // (by other names: the encode passes below shadow them, QPRD)
+        const Q8 &o8i = q8i, &o8p = q8p;
         const bool left = c.mbx > 0, top = c.sy > 0, topright = top && c.mbx + 1 < k.mbw, topleft = top && left;
         const int mbx = c.mbx, mby = c.mby;
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
@@ -2306,6 +2320,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MB_WAVES_PER
         int rf8_v[8] = { 0, 0, 0, 0, 0, 0, 0, 0 }, rf8c_v[8] = { 0, 0, 0, 0, 0, 0, 0, 0 }, rf8_cbp = 0;
         uint32_t rf8c_lo = 0, rf8c_hi = 0;
         unsigned rf8_n4 = 0;
+        // QP-RD (QPRD instantiations; qprd.hip.h): the walk's state (qw_on: 0 not begun, 1 under way, 2 over), what it answered last, the transform size
+        // the decision left, the samples logged; the macroblock's own quantisers, whose lambdas hold throughout
+        QprdWalk qw;
+        int qw_on = 0, qw_act = 0, qw_t8 = 0, qw_n = 0;
+        const int qw_qp0 = c.qp, qw_qpc0 = c.qpc;
+        if constexpr (QPRD) {
+            qprd_start(qw, c.qp, last_qp, 0, 51, 0, 0);
+            if (k.qprd_log && lane == 0) k.qprd_log[((size_t)s * k.nmb + mbi) * QPRD_LOG_WORDS] = 0;          // (a macroblock without a walk: no samples)
+        }
         if constexpr (BS) {
             rd_run = true; commit = false;
             const int ci_ = (lane >> 2) & 3;
@@ -2330,12 +2353,16 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MB_WAVES_PER
             uni_all(rf_cx, rf_cy, rf_cdir, rf_mvpx, rf_mvpy, rf_mv0x, rf_mv0y, rf_f4, rf_f8, rf_lmx, rf_lmy, rf_priced, rf_done, rf_ref, rf_slot, rf_pm8, rf_b0, rf_b1); \
             uni_all(rf_bcost, rf_cost, rf_amvd, rf_l, rf_mvp0x, rf_mvp0y, rf_mvp1x, rf_mvp1y, rf_bm1x, rf_bm1y, rf_c1x, rf_c1y, rf_bestj, rf_amvd1, rf_nnzc); \
             uni_all(rf_cm, rf_bm, rf_bdct, rf_cbpc, rf_cbp_i8, rf_old, rf_list, rf8_cbp, rf8_n4); \
+        } \
+        if constexpr (QPRD) { \
+            uni_all(qw.st, qw.orig, qw.last, qw.qmin, qw.qmax, qw.psy, qw.t8ok, qw.di, qw.dir, qw.thr, qw.fail, qw.prev, qw.chk_q, qw.chk_c, qw.q, qw.bcost, qw.bqp, qw.origcost); \
+            uni_all(qw.origcbp, qw.last_tried, qw.empty, qw.flip, qw_on, qw_act, qw_t8, qw_n, c.qp, c.qpc); \
         } } while (0)
         for (;;) {
         RELANE();
         STATE_UNIFORM();
         if constexpr (BS) {
-            if (rd_run && !commit) {
+            if (rd_run && !commit && !(QPRD && qw_on)) {
                 if (!rf_on || rf_kind == 2) {          // (the refinement of an inter type runs inside k_mb_b.inc's last phase: k_mb_b_rdrefine.inc)
 #include "k_mb_b.inc"
                 }
@@ -2349,7 +2376,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MB_WAVES_PER
                 }
             }
         } else if constexpr (RD) {
-            if (rd_run && !commit) {
+            if (rd_run && !commit && !(QPRD && qw_on)) {
                 // next candidate in x264's order: P16x16, 16x8, 8x16, 8x8 (x264_mb_analyse_p_rd), the other transform size of the winner
                 // (x264_mb_analyse_transform_rd), I16x16, I4x4, I8x8 (x264_intra_rd); then the final pass
                 const int c16 = pslice ? rl(S.cost, ME_16) : MB_COST_MAX;
@@ -2411,12 +2438,29 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MB_WAVES_PER
                 }
             }
         }
+        if constexpr (QPRD) {
+            // x264_macroblock_analyse, i_mbrd 3: type, partition, transform size, vectors and modes are final (the machines above said commit) — before the
+            // macroblock is coded for good, mb_analyse_qp_rd: candidate passes of exactly that macroblock at the quantisers the walk asks for
+            if (k.qp_rd && rd_run && commit && !qw_on) {
+                qw_on = 2;
+                if (e_type != X264GPU_MB_P_SKIP && e_type != X264GPU_MB_B_SKIP) {
+                    const bool inter_t = e_type >= X264GPU_MB_P_L0;
+                    qw_t8 = e_t8 > 0;
+                    qw_act = qprd_start(qw, c.qp, last_qp, k.qprd_min, k.qprd_max, k.psy_rd_q8 != 0, inter_t && k.dct8x8 && e_t8 >= 0);
+                    if (qw_act != QPRD_DONE) { qw_on = 1; qw_n = 0; commit = false; }          // (DONE: its quantiser lies outside the range QP-RD chooses from)
+                }
+            }
+        }
         STATE_UNIFORM();
         nnz = 0; cbp_luma = 0; cbp_chroma = 0;
+        // the quantiser tables of what this pass codes: the macroblock's own, but for a QP-RD candidate's
+        const Q4 &q_li = QPRD ? k.q4tab[c.qp * 4 + 0] : o_li, &q_lp = QPRD ? k.q4tab[c.qp * 4 + 1] : o_lp, &q_ci = QPRD ? k.q4tab[c.qpc * 4 + 2] : o_ci, &q_cp = QPRD ? k.q4tab[c.qpc * 4 + 3] : o_cp;
+        const Q8 &q8i = QPRD ? k.q8tab[c.qp * 2 + 0] : o8i, &q8p = QPRD ? k.q8tab[c.qp * 2 + 1] : o8p;
         TRC trc;                                                // trellis: the final pass of RD sessions with CABAC (x264 --trellis 1)
         if constexpr (PSY) tr_psy_init(trc, psy_fd, k.psy_trellis);
         trc.on = 0; trc.r = 0; trc.r8 = 0; trc.model = 0; trc.tt.size_unary = nullptr; trc.tt.trans_unary = nullptr; trc.tt.lambda2 = nullptr;
         if constexpr (RD >= 3) {
+            if constexpr (QPRD) { trc.dql = qw_qp0 - c.qp; trc.dqc = qw_qpc0 - c.qpc; }          // (the trellis lambdas stay those of the macroblock's own quantisers)
             if ((commit || TRL2) && (k.trellis & 63) && rdon) { trc.on = k.trellis & 63; trc.r = cab.r; trc.r8 = cab.r8; trc.model = cab_modelv; trc.tt.size_unary = k.tr_su; trc.tt.trans_unary = k.tr_tu; trc.tt.lambda2 = k.tr_l2; }
         }
         int rd_t8cur = 0;                                         // transform_size_8x8_flag of what this pass codes
@@ -2929,7 +2973,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MB_WAVES_PER
                 if (commit && lane == 0) recd.transform8x8 = 1;
                 if (commit && lane < 16) recd.i4_mode[lane] = L.modes8[lane];
                 nnz = IR.nnz8; cbp_luma = IR.cbp8;
-                const bool tri8 = TRL && !TRL2 && (trc.on & TR_I8) != 0;         // (--trellis 2: the analysis' blocks were searched already, they are final)
+                // (--trellis 2: the analysis' blocks were searched already, they are final — at the macroblock's own quantiser: once a QP-RD walk has begun, every
+                //  pass codes the blocks again with the analysis' modes, at the quantiser of the pass)
+                const bool tri8 = TRL && (QPRD && (qw_on == 1 || qw_n > 0) ? true : !TRL2) && (trc.on & TR_I8) != 0;
                 if (tri8) nnz = mb_encode_i8x8_trellis(k, L, c, cz, q8i, trc, lvw, cbp_luma);
                 {
                     const uint32_t rz = *(const uint32_t *)(tile8 + zy * IT_STRIDE + zx);
@@ -2941,7 +2987,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MB_WAVES_PER
             } else if (e_type == X264GPU_MB_I4x4) {
                 if (commit && lane < 16) recd.i4_mode[lane] = L.modes4[lane];
                 nnz = IR.nnz4;
-                const bool tri4 = TRL && !TRL2 && (trc.on & TR_I4) != 0;
+                const bool tri4 = TRL && (QPRD && (qw_on == 1 || qw_n > 0) ? true : !TRL2) && (trc.on & TR_I4) != 0;
                 if (tri4) nnz = mb_encode_i4x4_trellis<M, RD != 5 && RD != 6>(k, L, c, cz, t4, q_li, trc, lvw);
                 for (int i8 = 0; i8 < 4; i8++) if ((nnz >> (4 * i8)) & 15) cbp_luma |= 1 << i8;
                 {
@@ -3151,6 +3197,25 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MB_WAVES_PER
                     else cost = dist + (int)(((unsigned long long)cab_total(tmp) * (unsigned long long)lambda2 + 32768) >> 16);
                 }
                 cost = uni(cost);          // (wave-uniform, but the bit count came through vector code: say so, or every RD cost of the macroblock lives in a vector register)
+                if constexpr (QPRD) {
+                    if (qw_on == 1) {
+                        // cbp_empty: x264's h->mb.cbp of this encode is 0 (under CABAC it carries the Intra_16x16 DC flag besides the two patterns)
+                        const int empty = !cbp_luma && !cbp_chroma && !(rec_type == X264GPU_MB_I16x16 && ((nnz >> 24) & 1));
+                        uint32_t *lg = k.qprd_log ? k.qprd_log + ((size_t)s * k.nmb + mbi) * QPRD_LOG_WORDS : nullptr;
+                        if (lg && lane == 0 && qw_n < QPRD_LOG_MAX) { lg[2 + 2 * qw_n] = (uint32_t)c.qp | (uint32_t)empty << 8 | (uint32_t)(qw_act == QPRD_FLIP) << 16; lg[3 + 2 * qw_n] = (uint32_t)cost; }
+                        qw_n++;
+                        qw_act = qprd_step(qw, cost, empty);
+                        c.qp = min(max(qw.q, 0), 51);          // the quantiser asked for next; at the end the chosen one
+                        c.qpc = (int)d_chroma_qp_table[min(max(c.qp + k.chroma_qp_offset, 0), 51)];
+                        if (qw.t8ok) e_t8 = (qw_act == QPRD_FLIP || (qw_act == QPRD_DONE && qw.flip)) ? !qw_t8 : qw_t8;
+                        if (qw_act == QPRD_DONE) {
+                            qw_on = 2; commit = true;
+                            if (lane == 0) recd.qp = (uint8_t)c.qp;
+                            if (lg && lane == 0) { lg[0] = (uint32_t)min(qw_n, QPRD_LOG_MAX); lg[1] = (uint32_t)qw.orig | (uint32_t)qw.last << 8 | (uint32_t)c.qp << 16 | (uint32_t)qw.flip << 24; }
+                        }
+                        continue;
+                    }
+                }
                 if constexpr (REF) {
                     if (!part_pass) {
                         // what this whole-macroblock encode leaves in x264's non_zero_count cache (flags; an 8x8 transform block sets its four entries alike)
@@ -3389,6 +3454,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MB_WAVES_PER
 // Every launch notes on the host which instantiation it is (mb_kernels_seen.hip; x264gpu_mb_kernels_seen hands the set out), so that a test can prove which of the
 // compiled kernels it ran: the id spells the template tuple in hex digits, 0x<M><ME><RD><PS BS PSY NR> (tests/mb_instantiations.py packs the same way).
 void mb_kernel_note(uint32_t id);
+// (the QP-RD instantiations — k_mb_slice's eighth argument — go out through mb_launch_qprd: bit 16 of the id)
+template <int M, int ME, bool PS, int RD, bool BS = false>
+static inline void mb_launch_qprd(const EncK &k, int streams, hipStream_t st)
+{
+    mb_kernel_note((uint32_t)(1 << 16 | M << 12 | ME << 8 | RD << 4 | PS << 3 | BS << 2));
+    hipLaunchKernelGGL((k_mb_slice<M, ME, PS, RD, BS, false, false, true>), dim3(streams, k.slices > 1 ? k.slices : 1), dim3(64), 0, st, k);
+}
 template <int M, int ME, bool PS, int RD = 0, bool BS = false, bool PSY = false, bool NR = false>
 static inline void mb_launch(const EncK &k, int streams, hipStream_t st)
 {

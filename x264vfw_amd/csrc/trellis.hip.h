@@ -79,7 +79,9 @@ template <int N> __device__ __forceinline__ unsigned long long tr_row_shr(unsign
 typedef __attribute__((address_space(3))) int16_t lds_i16;
 template <bool PSY> struct TrellisPsy {};
 template <> struct TrellisPsy<true> { const lds_i16 *fdct; int fstride; int q8; };      // block b of the call: fdct + b * fstride (its own stride: one source block may serve several candidates)
-template <int CAT, bool FORCE_GENERAL = false, bool PSY = false>
+// LQ (the QP-RD instantiations of the macroblock loop): qp = the quantiser of the tables | the quantiser of lambda2 << 8 — x264's QP-RD codes a macroblock at
+// other quantisers under the trellis lambdas of its own (mb_analyse_init_qp is not called again).
+template <int CAT, bool FORCE_GENERAL = false, bool PSY = false, bool LQ = false>
 __device__ __noinline__ unsigned trellis_blocks(lds_i16 *coefs, int stride, int nblk, int qp, bool intra, uint32_t model, TrellisTab tt, uint32_t reg, TrellisPsy<PSY> psy = {})
 {
     static_assert(!PSY || CAT == 1 || CAT == 2 || CAT == 5, "psy-trellis: luma blocks that are not DC blocks");
@@ -93,7 +95,8 @@ __device__ __noinline__ unsigned trellis_blocks(lds_i16 *coefs, int stride, int 
     const int n = lane & 7, g = lane >> 3, base = lane & ~7;
     const bool blk_on = g < nblk;
     lds_i16 *mine = coefs + g * stride;
-    const int lambda2 = tt.lambda2[(intra ? 52 : 0) + qp];
+    const int lambda2 = tt.lambda2[(intra ? 52 : 0) + (LQ ? qp >> 8 : qp)];
+    if constexpr (LQ) qp &= 255;
     // quantiser, rounding offset, inverse and distortion weight of every coefficient class (three for 4x4 blocks, six for 8x8, one for DC
     // blocks), worked out once: the divisions stay out of the loop
     constexpr int NCLS = DC ? 1 : CAT == 5 ? 6 : 3;

@@ -33,6 +33,7 @@ void Settings::settle(x264_param_t &p, RateControl &rc, Dpb &dpb, MbTreeStats &t
     if (const char *e = getenv("X264GPU_HOST_PIPELINE")) env.pipeline_off = e[0] == '0';
     if (const char *e = getenv("X264GPU_CAVLC_THREADS")) { env.cavlc_threads_set = true; env.cavlc_threads = atoi(e); }
     env.mbtree_stats = MbTreeStats::opted_in();
+    if (const char *e = getenv("X264GPU_QP_RD")) env.qp_rd = atoi(e) == 1;
 
     mbw = (p.i_width + 15) / 16; mbh = (p.i_height + 15) / 16; nmb = mbw * mbh;
     if (!p.i_timebase_num || !p.i_timebase_den) { p.i_timebase_num = p.i_fps_den; p.i_timebase_den = p.i_fps_num; }
@@ -78,6 +79,15 @@ void Settings::toolset(x264_param_t &p)
     // analyse one level down, i.e. as at subme 7): on the device in CABAC sessions under --me hex / umh.  9 adds the refinement in B slices (per-list
     // x264_me_refine_qpel_rd, x264_me_refine_bidir_rd, intra_rd_refine), chroma in their sub-pel costs and the deblock-aware RD costs.  10 and 11 (QP-RD,
     // full-RD trellis) are not implemented.  The highest level whose behaviour IS implemented is reported back
+    // With X264GPU_QP_RD=1, 10 (QP-RD, i_mbrd 3: the quantisers around a decided macroblock's own, on RD cost) runs on the device in CABAC sessions under --me hex /
+    // umh with --trellis 2 and AQ (the last two are x264's own conditions); whether it does is settled in quantisers(), once AQ is — until then the session is a subme 9 one
+    if (env.qp_rd && p.analyse.i_subpel_refine > 9) {
+        if (p.analyse.i_subpel_refine > 10) xlog(&p, X264_LOG_INFO, "subme %d: full RD without early termination (the level above 10) is not built: subme 10\n", p.analyse.i_subpel_refine);
+        const char *missing = !p.b_cabac ? "CABAC" : p.analyse.i_me_method != X264_ME_HEX && p.analyse.i_me_method != X264_ME_UMH ? "me hex / umh" : nullptr;
+        if (missing) xlog(&p, X264_LOG_WARNING, "subme 10 (QP-RD) needs %s in the MI355X path: subme 9\n", missing);
+        else qprd_asked = true;
+        p.analyse.i_subpel_refine = 9;
+    }
     if (p.analyse.i_subpel_refine > 9) { xlog(&p, X264_LOG_WARNING, "subme %d: QP-RD / full-RD trellis of the levels above 9 are not implemented yet: subme 9\n", p.analyse.i_subpel_refine); p.analyse.i_subpel_refine = 9; }
     if (p.analyse.i_subpel_refine >= 8 && (!p.b_cabac || (p.analyse.i_me_method != X264_ME_HEX && p.analyse.i_me_method != X264_ME_UMH))) {
         xlog(&p, X264_LOG_WARNING, "subme %d (RD refinement) needs CABAC and me hex / umh in the MI355X path: subme 7\n", p.analyse.i_subpel_refine); p.analyse.i_subpel_refine = 7;
@@ -301,6 +311,12 @@ void Settings::quantisers(x264_param_t &p, RateControl &rc, Dpb &dpb, MbTreeStat
     aq_mode = p.rc.i_aq_mode;
     p.rc.i_qp_constant = clampi(qp, 1, 51);
     p.rc.i_qp_min = clampi(p.rc.i_qp_min, 1, 51); p.rc.i_qp_max = clampi(p.rc.i_qp_max, p.rc.i_qp_min, 51);
+    if (qprd_asked) {
+        // --subme 10 under X264GPU_QP_RD=1 (toolset() left the session at subme 9): x264's own rule first, then what the device's QP-RD kernels are not built beside
+        if (p.analyse.i_trellis != 2 || !p.rc.i_aq_mode) xlog(&p, X264_LOG_WARNING, "subme 10 (QP-RD) requires trellis 2 and aq-mode > 0, as in x264 (%s missing): subme 9\n", p.analyse.i_trellis != 2 ? p.rc.i_aq_mode ? "trellis 2" : "both" : "aq-mode > 0");
+        else if (p.analyse.i_noise_reduction || p.analyse.f_psy_trellis > 0) xlog(&p, X264_LOG_INFO, "subme 10: QP-RD is not run beside %s in the MI355X path (%s keeps its kernels): subme 9\n", p.analyse.i_noise_reduction ? "noise reduction" : "psy-trellis", p.analyse.i_noise_reduction ? "nr" : "psy-trellis");
+        else { qp_rd = true; p.analyse.i_subpel_refine = 10; }
+    }
     if (p.i_threads > 1 && p.i_scenecut_threshold) { xlog(&p, X264_LOG_INFO, "scenecut needs threads 1 (GOPs in lock-step have a fixed structure): scenecut 0\n"); p.i_scenecut_threshold = 0; }
     // x264 validate_parameters: min-keyint auto = min(keyint / 10, fps), then [1, keyint / 2 + 1]
     if (p.i_keyint_min <= 0) { const int fps = (int)(p.i_fps_num / (p.i_fps_den ? p.i_fps_den : 1)); p.i_keyint_min = p.i_keyint_max / 10 < fps ? p.i_keyint_max / 10 : fps; }
@@ -432,6 +448,7 @@ x264gpu_config Settings::device_config(const x264_param_t &p) const
     cfg.rd = p.analyse.i_subpel_refine >= 8 ? 63 : p.analyse.i_subpel_refine >= 6; cfg.psy_rd_q8 = psy_rd_q8(p);      // 63: RD + every refinement site (x264's i_mbrd 2)
     if (p.analyse.i_subpel_refine >= 9 && p.b_deblocking_filter) cfg.rd |= 64;          // h->mb.b_deblock_rdo: whole-macroblock RD costs measured after the loop filter
     cfg.psy_trellis_q8 = psy_trellis_q8(p);
+    if (qp_rd) { cfg.qp_rd = 1; cfg.qp_min = p.rc.i_qp_min; cfg.qp_max = p.rc.i_qp_max; }          // (x264: rc.i_qp_min .. min(rc.i_qp_max, 51); both clipped to 1 .. 51 in quantisers())
     cfg.trellis = p.analyse.i_trellis == 2 ? 63 + 64 : p.analyse.i_trellis ? 63 : 0;         // every quantiser call of the final encode; + 64: of the analysis too
     cfg.psy = cfg.rd && p.analyse.b_psy;           // x264: the chroma lambda offset table follows b_psy, whatever the psy-rd strength
     cfg.deadzone_inter = p.analyse.i_luma_deadzone[0]; cfg.deadzone_intra = p.analyse.i_luma_deadzone[1];

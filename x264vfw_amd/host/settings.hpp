@@ -24,6 +24,7 @@ struct Settings {
         bool pipeline_off = false;                      // X264GPU_HOST_PIPELINE=0
         bool cavlc_threads_set = false; int cavlc_threads = 0;      // X264GPU_CAVLC_THREADS=N
         bool mbtree_stats = false;                      // X264GPU_MBTREE_STATS=1 (MbTreeStats::opted_in)
+        bool qp_rd = false;                             // X264GPU_QP_RD=1: --subme 10 runs QP-RD where the session can (else it is subme 9, as without the variable)
     } env;
 
     int mbw = 0, mbh = 0, nmb = 0;
@@ -39,6 +40,8 @@ struct Settings {
     int keyint = 250, keyint_min = 25;
     int qp_i = 23, qp_p = 23, pic_init_qp = 26;
     int profile_idc = 66, level_idc = 40, log2_max_frame_num = 8, log2_max_poc_lsb = 0;
+    bool qp_rd = false;           // x264's QP-RD runs (--subme 10 under X264GPU_QP_RD=1; settled in quantisers(), once AQ is); qprd_asked: --subme 10 / 11 came in and waits for that
+    bool qprd_asked = false;
     int cqo_without_psy_trellis = 0;      // the chroma quantiser offset without psy-trellis' share (what remains when psy-trellis gives way to nr)
     int G = 1;                    // --threads G: GOP slots (1: none)
     bool slots_rc = false;        // ... whose pictures the session plans ahead as a --threads 1 session does (X264GPU_GOP_SLOTS_RC=1)

@@ -43,7 +43,7 @@ class Config(C.Structure):
     _fields_ = [(n, C.c_float if n == "aq_strength" else C.c_int) for n in (
         "width", "height", "streams", "refs", "qp_i", "qp_p", "me_range", "subme", "deblock",
         "deblock_alpha", "deblock_beta", "chroma_qp_offset", "deadzone_inter", "deadzone_intra",
-        "dct_decimate", "partitions", "dct8x8", "me_method", "chroma_me", "mixed_refs", "aq_mode", "aq_strength", "fast_pskip", "mv_range", "cabac", "rd", "psy", "psy_rd_q8", "slices", "trellis", "slices_plain", "dpb", "weightb", "psy_trellis_q8")]
+        "dct_decimate", "partitions", "dct8x8", "me_method", "chroma_me", "mixed_refs", "aq_mode", "aq_strength", "fast_pskip", "mv_range", "cabac", "rd", "psy", "psy_rd_q8", "slices", "trellis", "slices_plain", "dpb", "weightb", "psy_trellis_q8", "qp_rd", "qp_min", "qp_max")]
 
 
 class Pic(C.Structure):
@@ -82,6 +82,8 @@ def make_pic(slice_type, qp, poc, dst, keep, l0=(), l1=()):
 
 
 MB_LEVELS = 416
+QPRD_LOG_WORDS, QPRD_LOG_SAMPLES = 128, 63          # X264GPU_QPRD_LOG_WORDS / _SAMPLES: an entry of x264gpu_encoder_set_qprd_log's buffer
+QPRD_ASKED_MAX = 64          # X264GPU_QPRD_ASKED_MAX: a row of x264gpu_qprd_walk's d_asked
 
 _SIGS = {
     "x264gpu_abi_version": (_i, []),
@@ -147,6 +149,8 @@ _SIGS = {
     "x264gpu_trellis_blocks": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "x264gpu_trellis_blocks_ex": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp]),
     "x264gpu_trellis_blocks_psy": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp]),
+    "x264gpu_qprd_walk": (_i, [_vp] * 6 + [_i] * 4 + [_vp] * 5),
+    "x264gpu_encoder_set_qprd_log": (_i, [_vp, _vp]),
     "x264gpu_encoder_set_nr": (_i, [_vp, _vp, _vp]),
     "x264gpu_nr_update": (_i, [_vp, _vp, _vp, _i, _i, _vp]),
     "x264gpu_denoise_blocks": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
