@@ -419,6 +419,13 @@ typedef struct x264gpu_nr_sums { uint64_t sum[3][64]; uint32_t count[3], pad; } 
  * re-issued picture is exact.  NULL, NULL returns to the plain kernels.  EINVAL unless the session is what the denoising instantiations of the macroblock loop are
  * built for: cabac, rd, trellis, subme >= 6, me_method 1 / 2, a DPB-model session (cfg.dpb > 0), no psy-trellis.  Both arrays must stay valid while calls use them. */
 int x264gpu_encoder_set_nr(x264gpu_encoder *enc, const x264gpu_nr_offsets *d_off /* [streams] */, x264gpu_nr_sums *d_pic /* [streams] */);
+/* The same contract for every inter toolset the macroblock loop has: any cabac, rd, trellis, subme and me_method (CAVLC sessions, sessions without RD or without
+ * the trellis quantiser, me dia / esa).  A session that x264gpu_encoder_set_nr admits runs the kernels it runs there; every other one runs the denoising sibling
+ * of its plain kernel (x264gpu_mb_kernels_seen: bit 17 beside the NR bit).  The rule is x264's: an inter residual is denoised wherever the loop transforms it
+ * before quantising — final encodes, RD candidates (CAVLC bit counts and CABAC sizes alike), skip probes; without RD that is the probes and the final encode.
+ * The SATD choice between the 4x4 and the 8x8 transform reads the residual as it is.  EINVAL for cfg.dpb == 0, psy-trellis and cfg.qp_rd.  NULL, NULL returns
+ * to the plain kernels.  Either entry replaces what the other one set. */
+int x264gpu_encoder_set_nr_any(x264gpu_encoder *enc, const x264gpu_nr_offsets *d_off /* [streams] */, x264gpu_nr_sums *d_pic /* [streams] */);
 /* x264_noise_reduction_update per stream, queued on `stream`: d_state += d_pic (d_pic NULL: the state as it is); per category, a count above 1 << 18 (category 1:
  * 1 << 16) halves the sums and the count; then, in 64-bit integers, off[cat][i] = min((strength * count + sum / 2) / (sum * weight2[cat][i] / 256 + 1), 32767)
  * (x264 lets a uint16 wrap; no coefficient exceeds int16, so the clamp zeroes what the true value would zero), off[cat][0] = 0.  weight2: the squared-norm weights
@@ -439,7 +446,7 @@ int  x264gpu_encoder_set_debug(x264gpu_encoder *enc, void *d_counters);
 /* diagnostics: the instantiations of the macroblock loop (k_mb_slice<M, ME, PS, RD, BS, PSY, NR>) this process has launched since the last reset, whichever
  * encoder launched them: up to `max` distinct ids into ids[] in the order of their first launch (ids may be NULL with max 0), the return value is their
  * number; reset != 0 empties the set afterwards.  An id spells the template tuple in hex digits: M << 12 | ME << 8 | RD << 4 | PS << 3 | BS << 2 | PSY << 1 | NR;
- * bit 16 on top: the QP-RD instantiation of the tuple (cfg.qp_rd).
+ * bit 16 on top: the QP-RD instantiation of the tuple (cfg.qp_rd); bit 17 on top: a denoising instantiation that only x264gpu_encoder_set_nr_any reaches.
  * Host side only (a launch notes its id before it is queued); thread-safe. */
 int  x264gpu_mb_kernels_seen(uint32_t *ids, int max, int reset);
 int  x264gpu_encoder_profile_end(x264gpu_encoder *enc, void *stream, double *ms_sum, int *launches);

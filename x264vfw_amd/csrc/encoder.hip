@@ -30,6 +30,7 @@ void launch_mb_slice_b_esa(const EncK &k, int streams, hipStream_t st);
 void launch_mb_slice_psy(const EncK &k, int streams, int slice_type, hipStream_t st);       // psy-trellis sessions (mb_slice_psy_*.hip): I, P and B slices, --me hex / umh
 void launch_mb_slice_qprd(const EncK &k, int streams, int slice_type, hipStream_t st);      // QP-RD sessions (cfg.qp_rd; qprd_slice_*.hip): I, P and B slices, --me hex / umh
 void launch_mb_slice_nr(const EncK &k, int streams, int slice_type, hipStream_t st);        // --nr (x264gpu_encoder_set_nr; mb_slice_nr_*.hip): P and B slices, --me hex / umh
+void launch_nr_any_slice(const EncK &k, int streams, int slice_type, hipStream_t st);       // --nr in every other inter toolset (x264gpu_encoder_set_nr_any; nr_any_slice_*.hip): P and B slices
 void launch_nr_gather(const x264gpu_nr_sums *part, int slices, x264gpu_nr_sums *pic, int streams, hipStream_t st);      // nr_kernels.hip
 int trellis_table_ptrs(const uint16_t **su, const uint8_t **tu, const int **l2);        // prim_kernels.hip
 int cabac_chain_table(const uint32_t **out);                                              // prim_kernels.hip
@@ -333,11 +334,14 @@ void x264gpu_encoder_destroy(x264gpu_encoder *e)
 
 int x264gpu_encoder_mb_count(const x264gpu_encoder *e) { return e ? e->k.nmb : 0; }
 // --nr: the following encode calls of this launch context run the denoising instantiations of the macroblock loop (built for what the checks below name)
-int x264gpu_encoder_set_nr(x264gpu_encoder *e, const x264gpu_nr_offsets *d_off, x264gpu_nr_sums *d_pic)
+// (the sessions whose denoising kernels are the mb_slice_nr_*.hip ones; every other inter toolset: nr_any_slice_*.hip)
+static bool nr_first_toolset(int cabac, int rd, int trellis, int subme, int me_method) { return cabac && rd && trellis && subme >= 6 && (me_method == 1 || me_method == 2); }
+static int set_nr(x264gpu_encoder *e, const x264gpu_nr_offsets *d_off, x264gpu_nr_sums *d_pic, bool any)
 {
     ARG_TRY(e && (d_off != nullptr) == (d_pic != nullptr));
     if (!d_off) { e->nr_off = nullptr; e->nr_pic = nullptr; return X264GPU_OK; }
-    ARG_TRY(e->cfg.cabac && e->cfg.rd && e->cfg.trellis && e->cfg.subme >= 6 && (e->cfg.me_method == 1 || e->cfg.me_method == 2) && e->cfg.dpb > 0 && !e->cfg.psy_trellis_q8 && !e->cfg.qp_rd);
+    ARG_TRY(any || nr_first_toolset(e->cfg.cabac, e->cfg.rd, e->cfg.trellis, e->cfg.subme, e->cfg.me_method));
+    ARG_TRY(e->cfg.dpb > 0 && !e->cfg.psy_trellis_q8 && !e->cfg.qp_rd);
     if (!e->nr_part) {
         const size_t n = (size_t)e->cfg.streams * (e->cfg.slices > 1 ? e->cfg.slices : 1) * sizeof(x264gpu_nr_sums);
         hipError_t er = hipMalloc((void **)&e->nr_part, n);
@@ -347,6 +351,9 @@ int x264gpu_encoder_set_nr(x264gpu_encoder *e, const x264gpu_nr_offsets *d_off, 
     e->nr_off = d_off; e->nr_pic = d_pic;
     return X264GPU_OK;
 }
+int x264gpu_encoder_set_nr(x264gpu_encoder *e, const x264gpu_nr_offsets *d_off, x264gpu_nr_sums *d_pic) { return set_nr(e, d_off, d_pic, false); }
+// ... in every inter toolset the loop has: a session outside the first toolset launches the denoising sibling of its plain kernel (the launch below tells them apart)
+int x264gpu_encoder_set_nr_any(x264gpu_encoder *e, const x264gpu_nr_offsets *d_off, x264gpu_nr_sums *d_pic) { return set_nr(e, d_off, d_pic, true); }
 // QP-RD: the following encode calls of this launch context write what every macroblock's walk asked and got into d_log (null: no log)
 int x264gpu_encoder_set_qprd_log(x264gpu_encoder *e, uint32_t *d_log)
 {
@@ -629,7 +636,7 @@ static int encode_core(x264gpu_encoder *e, const uint8_t *d_i420, const x264gpu_
     else {
         const auto launch_b = k.me_method == 0 ? launch_mb_slice_b_dia : k.me_method == 2 ? launch_mb_slice_b_umh : k.me_method == 3 ? launch_mb_slice_b_esa : launch_mb_slice_b_hex;
         const auto launch_p = k.me_method == 0 ? launch_mb_slice_dia : k.me_method == 2 ? launch_mb_slice_umh : k.me_method == 3 ? launch_mb_slice_esa : launch_mb_slice_hex;
-        const auto launch = [&](const EncK &kk, int streams, bool big_margin, hipStream_t s_) { if (kk.qp_rd) launch_mb_slice_qprd(kk, streams, bslice ? X264GPU_SLICE_B : X264GPU_SLICE_P, s_); else if (kk.nr_off) launch_mb_slice_nr(kk, streams, bslice ? X264GPU_SLICE_B : X264GPU_SLICE_P, s_); else if (kk.psy_trellis) launch_mb_slice_psy(kk, streams, bslice ? X264GPU_SLICE_B : X264GPU_SLICE_P, s_); else if (bslice) launch_b(kk, streams, s_); else launch_p(kk, streams, big_margin, s_); };
+        const auto launch = [&](const EncK &kk, int streams, bool big_margin, hipStream_t s_) { if (kk.qp_rd) launch_mb_slice_qprd(kk, streams, bslice ? X264GPU_SLICE_B : X264GPU_SLICE_P, s_); else if (kk.nr_off) (nr_first_toolset(kk.cabac, kk.rd, kk.trellis, kk.subme, kk.me_method) ? launch_mb_slice_nr : launch_nr_any_slice)(kk, streams, bslice ? X264GPU_SLICE_B : X264GPU_SLICE_P, s_); else if (kk.psy_trellis) launch_mb_slice_psy(kk, streams, bslice ? X264GPU_SLICE_B : X264GPU_SLICE_P, s_); else if (bslice) launch_b(kk, streams, s_); else launch_p(kk, streams, big_margin, s_); };
         if (k.sl_stat) hipLaunchKernelGGL(k_slice_priors, dim3((S + 63) / 64), dim3(64), 0, st, k, S, 1);
         launch(k, S, k.subme >= 8, st);
         // --slices N: slice i is final once slices 0..i-1 are, so slices - 1 rounds of "check the assumed counts, run the slices again whose

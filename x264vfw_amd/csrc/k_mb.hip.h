@@ -1702,7 +1702,8 @@ __device__ __forceinline__ void b_predict(const EncK &k, const MbCtx &c, const B
 // QPRD: x264 --subme 10 (cfg.qp_rd; RD 6 without PSY and NR) — instantiations of their own (qprd_slice_*.hip): where the decision machines say "commit", the decided
 // macroblock first goes through candidate passes at the quantisers the walk of qprd.hip.h asks for (lambdas held, the quantiser tables re-bound per pass), then is
 // committed at the one it chose.  Everything of it sits under `if constexpr (QPRD)` or folds away: the other instantiations compile to what they were
-// NR: x264 --nr (x264gpu_encoder_set_nr; RD >= 3 inter slices without PSY) — instantiations of their own (mb_slice_nr_*.hip): every inter residual the loop
+// NR: x264 --nr (x264gpu_encoder_set_nr: RD >= 3 under me hex / umh, mb_slice_nr_*.hip; x264gpu_encoder_set_nr_any: every other inter instantiation without PSY and
+// QPRD, nr_any_slice_*.hip) — instantiations of their own: every inter residual the loop
 // transforms (final encodes, RD candidates, sub-block encodes of the refinement, skip probes) is denoised with the stream's offsets before it is quantised.  The
 // offsets in use are staged once per slice (96 of them, 192 B of LDS: with them the loop still fits eight wavefronts a CU).  Statistics take the FINAL encode of the inter macroblocks
 // that do not end as skips: a macroblock's |coefficient| values wait in L.lv4 / L.lv8 (the intra analysis' levels, dead once an inter macroblock is being
@@ -1714,7 +1715,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MB_WAVES_PER
 {
     static_assert(!QPRD || (RD == 6 && !PSY && !NR), "QP-RD: the refinement instantiations with --trellis 2, without psy-trellis and noise reduction");
     static_assert(!PSY || RD >= 3, "psy-trellis: instantiations with the trellis quantiser");
-    static_assert(!NR || (RD >= 3 && PS && !PSY), "nr: inter slices of trellis sessions, without psy-trellis");
+    static_assert(!NR || (PS && !PSY), "nr: inter slices, without psy-trellis");
     using TRC = std::conditional_t<PSY, TrCtxPsy, std::conditional_t<QPRD, TrCtxQ, TrCtx>>;
     __shared__ __attribute__((aligned(16))) int16_t psy_fd[PSY ? 512 : 1];          // (referenced in PSY instantiations only: the others allocate nothing)
     static_assert(!BS || PS, "B slices are inter slices");
@@ -1759,23 +1760,25 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MB_WAVES_PER
     int intra_count = intra_prior, cost_qp = -1;          // intra macroblocks so far: of the slice (slice threads), of the picture (--slices N)
     // RD instantiation: levels of the candidate being costed (and of the final macroblock, before they go out), total_coeff of the left / top
     // macroblocks' blocks for the nC of the bit counts; the quantiser the previous coded macroblock left (mb_qp_delta bits)
-    __shared__ __attribute__((aligned(16))) int16_t rd_lvs[RD ? X264GPU_MB_LEVELS + (NR ? NR_OFF_N : 0) : 1];          // (NR: + the stream's offsets behind the levels, below)
+    // (NR: + the stream's offsets behind the levels, below; without RD there are no levels on chip and the offsets are all the buffer holds)
+    constexpr int NR_AT = RD ? X264GPU_MB_LEVELS : 0;
+    __shared__ __attribute__((aligned(16))) int16_t rd_lvs[RD ? X264GPU_MB_LEVELS + (NR ? NR_OFF_N : 0) : NR ? NR_OFF_N : 1];
     __shared__ uint8_t rd_ntc[2][RD == 1 ? 24 : 1];
     const uint16_t *nro = nullptr;          // NR: the stream's offsets in LDS (nr.hip.h NR_O4 / NR_OC / NR_O8), what the helpers above take
     x264gpu_nr_sums *nr_row = nullptr;      // ... and this slice's row of statistics: lane i owns sum[.][i], lanes 0..2 the counts
     if constexpr (NR) {
         // (behind the level buffer, not an LDS variable of their own: one more variable moves the others in the kernel's LDS block, and the P instantiations then
         //  need 256 registers and spill 10 - 100 of them where their plain siblings need 226 - 233 and spill none; profiles/nr.md)
-        nro = (const uint16_t *)(rd_lvs + X264GPU_MB_LEVELS);
+        nro = (const uint16_t *)(rd_lvs + NR_AT);
         const uint32_t *src = (const uint32_t *)(k.nr_off + s);
-        if (lane < NR_OFF_N / 2) ((uint32_t *)(rd_lvs + X264GPU_MB_LEVELS))[lane] = src[nr_stage_src(lane)];
+        if (lane < NR_OFF_N / 2) ((uint32_t *)(rd_lvs + NR_AT))[lane] = src[nr_stage_src(lane)];
         nr_row = k.nr_part + (size_t)s * nsl + blockIdx.y;
         nr_row->sum[0][lane] = 0; nr_row->sum[1][lane] = 0; nr_row->sum[2][lane] = 0;
         if (lane < 4) (&nr_row->count[0])[lane] = 0;          // (count[3] and the padding behind it)
     }
     if constexpr (NR) lds_sync();
 #ifdef X264GPU_POISON
-    for (int i = lane; i < (RD ? X264GPU_MB_LEVELS : 1); i += 64) rd_lvs[i] = (int16_t)0xCDCD;
+    for (int i = lane; i < (RD ? X264GPU_MB_LEVELS : NR ? 0 : 1); i += 64) rd_lvs[i] = (int16_t)0xCDCD;          // (NR without RD: the buffer holds the offsets alone)
     __builtin_amdgcn_s_waitcnt(0); __builtin_amdgcn_wave_barrier();
 #endif
     // x264_slice_write: the slice's quantiser (header, context initialisation, start of the mb_qp_delta chain) is its FIRST macroblock's
@@ -3454,12 +3457,20 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MB_WAVES_PER
 // Every launch notes on the host which instantiation it is (mb_kernels_seen.hip; x264gpu_mb_kernels_seen hands the set out), so that a test can prove which of the
 // compiled kernels it ran: the id spells the template tuple in hex digits, 0x<M><ME><RD><PS BS PSY NR> (tests/mb_instantiations.py packs the same way).
 void mb_kernel_note(uint32_t id);
-// (the QP-RD instantiations — k_mb_slice's eighth argument — go out through mb_launch_qprd: bit 16 of the id)
+// (the QP-RD instantiations — k_mb_slice's eighth argument — go out through mb_launch_qprd: bit 16 of the id; the denoising instantiations of
+//  x264gpu_encoder_set_nr_any, nr_any_slice_*.hip, through mb_launch_nr_any: bit 17 beside the NR bit)
 template <int M, int ME, bool PS, int RD, bool BS = false>
 static inline void mb_launch_qprd(const EncK &k, int streams, hipStream_t st)
 {
     mb_kernel_note((uint32_t)(1 << 16 | M << 12 | ME << 8 | RD << 4 | PS << 3 | BS << 2));
     hipLaunchKernelGGL((k_mb_slice<M, ME, PS, RD, BS, false, false, true>), dim3(streams, k.slices > 1 ? k.slices : 1), dim3(64), 0, st, k);
+}
+template <int M, int ME, int RD = 0, bool BS = false>
+static inline void mb_launch_nr_any(const EncK &k, int streams, hipStream_t st)
+{
+    static_assert(M < 16 && ME < 16 && RD < 16, "the id holds one hex digit each");
+    mb_kernel_note((uint32_t)(1 << 17 | M << 12 | ME << 8 | RD << 4 | 1 << 3 | BS << 2 | 1));
+    hipLaunchKernelGGL((k_mb_slice<M, ME, true, RD, BS, false, true>), dim3(streams, k.slices > 1 ? k.slices : 1), dim3(64), 0, st, k);
 }
 template <int M, int ME, bool PS, int RD = 0, bool BS = false, bool PSY = false, bool NR = false>
 static inline void mb_launch(const EncK &k, int streams, hipStream_t st)

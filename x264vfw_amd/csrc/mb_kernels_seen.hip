@@ -7,8 +7,8 @@
 
 namespace x264gpu {
 namespace {
-constexpr int MB_IDS_MAX = 256;                     // (the tree instantiates 103 + 5 with QP-RD)
-std::atomic<uint32_t> g_bits[2 * 65536 / 32];       // bit id: noted since the last reset (bit 16 of an id: the QP-RD instantiation of the tuple, mb_launch_qprd)
+constexpr int MB_IDS_MAX = 256;                     // (the tree instantiates 103 + 5 with QP-RD + 38 of x264gpu_encoder_set_nr_any)
+std::atomic<uint32_t> g_bits[4 * 65536 / 32];       // bit id: noted since the last reset (bit 16 of an id: the QP-RD instantiation of the tuple, mb_launch_qprd; bit 17: mb_launch_nr_any)
 uint32_t g_ids[MB_IDS_MAX];                         // the ids in the order of their first launch
 int g_n;
 std::mutex g_mu;
@@ -16,7 +16,7 @@ std::mutex g_mu;
 
 void mb_kernel_note(uint32_t id)
 {
-    id &= 0x1ffff;
+    id &= 0x3ffff;
     if (g_bits[id >> 5].load(std::memory_order_relaxed) >> (id & 31) & 1) return;
     std::lock_guard<std::mutex> lock(g_mu);
     if (g_bits[id >> 5].load(std::memory_order_relaxed) >> (id & 31) & 1) return;

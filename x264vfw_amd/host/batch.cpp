@@ -188,7 +188,7 @@ void batch_run_round(BatchGroup *g, std::unique_lock<std::mutex> &lk)
 
 }  // namespace
 
-bool Batch::join(const x264gpu_config &cfg1, int N, size_t insz, size_t nmb, int qflags, int nr, const Side &side)
+bool Batch::join(const x264gpu_config &cfg1, int N, size_t insz, size_t nmb, int qflags, int nr, bool nr_any, const Side &side)
 {
     std::lock_guard<std::mutex> lk(g_batch_mu);
     int dev = 0;
@@ -217,7 +217,7 @@ bool Batch::join(const x264gpu_config &cfg1, int N, size_t insz, size_t nmb, int
                    x264gpu_malloc((void **)&ng->d_nr_state, (size_t)N * sizeof(x264gpu_nr_sums)) != X264GPU_OK ||
                    x264gpu_memset(ng->d_nr_off, 0, (size_t)N * sizeof(x264gpu_nr_offsets), nullptr) != X264GPU_OK || x264gpu_memset(ng->d_nr_pic, 0, (size_t)N * sizeof(x264gpu_nr_sums), nullptr) != X264GPU_OK ||
                    x264gpu_memset(ng->d_nr_state, 0, (size_t)N * sizeof(x264gpu_nr_sums), nullptr) != X264GPU_OK || x264gpu_stream_sync(nullptr) != X264GPU_OK ||
-                   nr_set(ng->gpu, ng->d_nr_off, ng->d_nr_pic) != X264GPU_OK)) { batch_destroy(ng); return false; }
+                   nr_set(ng->gpu, ng->d_nr_off, ng->d_nr_pic, nr_any) != X264GPU_OK)) { batch_destroy(ng); return false; }
         if (side.offsets || side.mvs) {
             // the gathered arrays and the tables of row pointers, two generations each; the vectors' "absent" row
             const size_t rows = (size_t)N * nmb * 4;

@@ -26,11 +26,11 @@ struct Batch {
 
     // joins (or starts) the group of N sessions with this device configuration; false: setup failed (the device's last error set)
     // nr: the session's noise-reduction strength (0: none) — part of what a group's members have in common: every stream of the group's encoder then has its own
-    // offsets, statistics and state, moved on behind every round
+    // offsets, statistics and state, moved on behind every round; nr_any: the group's encoder denoises through x264gpu_encoder_set_nr_any (Settings::nr_any)
     // side: which of a picture's side inputs (SideInputs below) the session's lookahead can produce — offsets: quantiser offsets, mvs: low-resolution vectors — and
     // `key`, everything else that decides them (mbtree, aq-mode, rc-lookahead, the direct mode): members of a group agree in all three
     struct Side { bool offsets = false, mvs = false; int key = 0; };
-    bool join(const x264gpu_config &cfg, int N, size_t insz, size_t nmb, int qflags, int nr, const Side &side);
+    bool join(const x264gpu_config &cfg, int N, size_t insz, size_t nmb, int qflags, int nr, bool nr_any, const Side &side);
     // the registry lock, then the group's: the last member to go takes the group with it; a round the others were only waiting for this session to join is run first
     void leave();
     bool joined() const { return g != nullptr; }

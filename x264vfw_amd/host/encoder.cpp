@@ -311,7 +311,7 @@ static bool open_device(x264_t *h)
         side.offsets = p.rc.b_mb_tree || (p.rc.i_aq_mode >= 2 && p.rc.f_aq_strength > 0);
         side.mvs = la_object;
         side.key = (p.rc.b_mb_tree ? 1 : 0) | p.rc.i_aq_mode << 1 | h->set.direct_mode << 4 | h->set.lookahead_asked << 8;
-        ok_setup = h->batch.join(cfg, h->batch.want, insz, (size_t)h->set.nmb, h->ql.flags, p.analyse.i_noise_reduction, side);
+        ok_setup = h->batch.join(cfg, h->batch.want, insz, (size_t)h->set.nmb, h->ql.flags, p.analyse.i_noise_reduction, h->set.nr_any, side);
         if (ok_setup) xlog(&p, X264_LOG_INFO, "X264GPU_BATCH: stream %d of a batch of %d sessions%s%s\n", h->batch.index(), h->batch.size(), h->batch.queued() ? " (rounds queued: uploads overlap the device)" : "",
                            side.offsets && side.mvs ? "; the group carries each member's quantiser offsets and lookahead vectors" : side.offsets ? "; the group carries each member's quantiser offsets" :
                            side.mvs ? "; the group carries each member's lookahead vectors" : "");
@@ -322,7 +322,7 @@ static bool open_device(x264_t *h)
                    x264gpu_malloc((void **)&h->d_mb, (size_t)h->set.nmb * sizeof(x264gpu_mb)) == X264GPU_OK &&
                    x264gpu_malloc((void **)&h->d_lv, (size_t)h->set.nmb * X264GPU_MB_LEVELS * sizeof(int16_t)) == X264GPU_OK &&
                    (!h->ql.flags || x264gpu_malloc((void **)&h->d_q, sizeof(x264gpu_quality)) == X264GPU_OK);
-        ok_setup = ok_setup && h->nr.open(p, h->gpu);
+        ok_setup = ok_setup && h->nr.open(p, h->gpu, h->set.nr_any);
         if (ok_setup && h->set.inflight > 1) {
             h->lctx.resize((size_t)h->set.inflight);
             ok_setup = x264gpu_event_create(&h->ev_la) == X264GPU_OK;
@@ -572,6 +572,20 @@ static int encode_queued(x264_t *h, x264_nal_t **pp_nal, int *pi_nal, x264_pictu
     h->last_stats.skip = 0;
     write_slices(h->out, h->nal_off, types, sp, h->set.slices, hmb, hlv, p.b_annexb != 0, idr, &h->last_stats, h->set.cavlc_threads);
     publish_nals(h, pp_nal, pi_nal, types);
+    if (const char *dd = getenv("X264GPU_DUMP_RECORDS")) {          // debugging aid, in the layout of encode_bmode's dump: a picture description (slice type and quantiser alone), records, levels, zero offsets
+        char fn[512];
+        snprintf(fn, sizeof(fn), "%s/pic%04ld.bin", dd, (long)h->frame_no);
+        if (FILE *fp = fopen(fn, "wb")) {
+            x264gpu_pic dp = {};
+            dp.slice_type = st; dp.qp = qp_now;
+            const std::vector<float> off((size_t)h->set.nmb, 0.f);
+            fwrite(&dp, sizeof(dp), 1, fp);
+            fwrite(hmb, sizeof(x264gpu_mb), (size_t)h->set.nmb, fp);
+            fwrite(hlv, sizeof(int16_t), (size_t)h->set.nmb * X264GPU_MB_LEVELS, fp);
+            fwrite(off.data(), sizeof(float), off.size(), fp);
+            fclose(fp);
+        }
+    }
     fill_pic_out(pic_out, x264_type_of(type), idr, e.pts, e.pts, &e.img);
     if (h->ql.flags) h->ql.frame_end(p, h->hq[e.buf], st == X264GPU_SLICE_P ? 1 : 0, mean_mb_qp(hmb, (size_t)h->set.nmb), 2 * h->frames_since_idr, h->out.size());
     if (idr) h->idr_pic_id = (h->idr_pic_id + 1) & 0xffff;

@@ -7,7 +7,8 @@
 namespace x264host {
 
 // the device entries through their weak bindings (EINVAL when the device library lacks them): what the batcher calls for a group's streams
-int nr_set(x264gpu_encoder *gpu, const x264gpu_nr_offsets *d_off, x264gpu_nr_sums *d_pic);
+// (any: through x264gpu_encoder_set_nr_any, the entry that admits every inter toolset — sessions settled under X264GPU_NR_ANY=1)
+int nr_set(x264gpu_encoder *gpu, const x264gpu_nr_offsets *d_off, x264gpu_nr_sums *d_pic, bool any);
 int nr_update_queue(x264gpu_nr_offsets *d_off, x264gpu_nr_sums *d_state, const x264gpu_nr_sums *d_pic, int streams, int strength, void *stream);
 
 struct NoiseReduction {
@@ -16,11 +17,13 @@ struct NoiseReduction {
 
     // the rules that hang on the toolset alone (before psy-trellis is settled: nr wins over it): clips the strength to 0 .. 65536; one WARNING that names what is
     // missing, and nr 0, when the device library has no nr entries or the session is not a CABAC trellis session at subme >= 6 under me hex / umh
-    static void check_toolset(x264_param_t &p);
+    // want_any (X264GPU_NR_ANY=1): with a device library that has x264gpu_encoder_set_nr_any the entries are the whole rule — any entropy coder, subme, trellis and
+    // search method; returns whether the session was admitted that way (it then runs on the DPB model and opens through that entry).  Without the entry: the rules above
+    static bool check_toolset(x264_param_t &p, bool want_any);
     // ... on the session's mode: needs the DPB model (a batch group runs on it) and one GOP.  Runs before psy-trellis gives way: what is refused here leaves it alone
     static void check_modes(x264_param_t &p, bool dpbmode);
     // zeroed state and offsets on the device, the encoder told to denoise with them; false: a device call failed (the rules above are the device's: it takes what they pass)
-    bool open(x264_param_t &p, x264gpu_encoder *gpu);
+    bool open(x264_param_t &p, x264gpu_encoder *gpu, bool any);
     // the picture the encoder coded last is accepted: its statistics join the state, the next picture's offsets follow (queued on `stream`)
     int accepted(void *stream) const;
     int offsets(uint16_t out[3][64]) const;

@@ -34,6 +34,7 @@ void Settings::settle(x264_param_t &p, RateControl &rc, Dpb &dpb, MbTreeStats &t
     if (const char *e = getenv("X264GPU_CAVLC_THREADS")) { env.cavlc_threads_set = true; env.cavlc_threads = atoi(e); }
     env.mbtree_stats = MbTreeStats::opted_in();
     if (const char *e = getenv("X264GPU_QP_RD")) env.qp_rd = atoi(e) == 1;
+    if (const char *e = getenv("X264GPU_NR_ANY")) env.nr_any = atoi(e) == 1;
 
     mbw = (p.i_width + 15) / 16; mbh = (p.i_height + 15) / 16; nmb = mbw * mbh;
     if (!p.i_timebase_num || !p.i_timebase_den) { p.i_timebase_num = p.i_fps_den; p.i_timebase_den = p.i_fps_num; }
@@ -100,7 +101,7 @@ void Settings::toolset(x264_param_t &p)
         xlog(&p, X264_LOG_WARNING, "trellis %d needs CABAC and subme >= 6 in the MI355X path (the search reads the CABAC state the device carries for RD): trellis 0\n", p.analyse.i_trellis);
         p.analyse.i_trellis = 0;
     }
-    NoiseReduction::check_toolset(p);          // --nr: inter residuals denoised in the macroblock loop (host/noisereduction.hpp); the toolset's share of its rules; psy-trellis gives way to it once the session's mode has passed too (quantisers())
+    nr_any = NoiseReduction::check_toolset(p, env.nr_any);          // --nr: inter residuals denoised in the macroblock loop (host/noisereduction.hpp); the toolset's share of its rules; psy-trellis gives way to it once the session's mode has passed too (quantisers())
     p.analyse.b_psy = p.analyse.b_psy != 0;
     if (!p.analyse.b_psy) { p.analyse.f_psy_rd = 0; p.analyse.f_psy_trellis = 0; }       // x264 validate_parameters
     p.analyse.f_psy_rd = p.analyse.f_psy_rd < 0 ? 0 : p.analyse.f_psy_rd > 10 ? 10 : p.analyse.f_psy_rd;
@@ -230,6 +231,9 @@ void Settings::modes(x264_param_t &p, int &batch_want)
     if (p.analyse.i_weighted_pred == X264_WEIGHTP_SMART && p.i_frame_reference < 2) p.analyse.i_weighted_pred = X264_WEIGHTP_NONE;      // a duplicate needs two references (x264: never placed)
     weightp = p.analyse.i_weighted_pred;
     dpbmode = bframes > 0 || weightp == X264_WEIGHTP_SMART || vbv;          // (VBV: the path that codes one picture at a time and can code it again)
+    // --nr on the extended toolset: on the DPB model as a VBV session is, B pictures or not (the presets without them, --tune zerolatency); what that model switches
+    // off for a session without B pictures stays off.  (--threads G and all-intra sessions are left to check_modes(), which refuses them as ever)
+    if (nr_any && p.analyse.i_noise_reduction && p.i_threads <= 1 && p.i_keyint_max >= 2) dpbmode = true;
     if (env.batch >= 2) {
         // cross-session batcher: this session joins (or starts) a group of N sessions coded in lock-step, if its picture structure is fixed
         // (macroblock-tree, --aq-mode 2 / 3 and --direct temporal leave every picture's type alone: the member's lookahead runs them, the group carries what it decides)
@@ -285,6 +289,8 @@ void Settings::quantisers(x264_param_t &p, RateControl &rc, Dpb &dpb, MbTreeStat
     }
     rc.vbv = vbv; rc.filler = vbv && p.i_nal_hrd == X264_NAL_HRD_CBR;
     NoiseReduction::check_modes(p, dpbmode);
+    if (!p.analyse.i_noise_reduction) nr_any = false;
+    if (nr_any) xlog(&p, X264_LOG_INFO, "nr %d runs on the extended toolset (X264GPU_NR_ANY: the denoising kernels of every inter toolset, the session on the DPB model)\n", p.analyse.i_noise_reduction);
     if (p.analyse.i_noise_reduction && p.analyse.f_psy_trellis > 0) {
         // nr runs (toolset and mode have passed; from here on only a device failure stops it, and that fails the open): psy-trellis gives way, with its share of the
         // chroma quantiser offset (the macroblock loop has psy instantiations and denoising instantiations, none with both: the build would double again)

@@ -25,6 +25,7 @@ struct Settings {
         bool cavlc_threads_set = false; int cavlc_threads = 0;      // X264GPU_CAVLC_THREADS=N
         bool mbtree_stats = false;                      // X264GPU_MBTREE_STATS=1 (MbTreeStats::opted_in)
         bool qp_rd = false;                             // X264GPU_QP_RD=1: --subme 10 runs QP-RD where the session can (else it is subme 9, as without the variable)
+        bool nr_any = false;                            // X264GPU_NR_ANY=1: --nr in every inter toolset the device has denoising kernels for (else today's rules)
     } env;
 
     int mbw = 0, mbh = 0, nmb = 0;
@@ -42,6 +43,7 @@ struct Settings {
     int profile_idc = 66, level_idc = 40, log2_max_frame_num = 8, log2_max_poc_lsb = 0;
     bool qp_rd = false;           // x264's QP-RD runs (--subme 10 under X264GPU_QP_RD=1; settled in quantisers(), once AQ is); qprd_asked: --subme 10 / 11 came in and waits for that
     bool qprd_asked = false;
+    bool nr_any = false;          // --nr was admitted on the extended toolset (X264GPU_NR_ANY=1 and a device library with x264gpu_encoder_set_nr_any): the session runs on the DPB model
     int cqo_without_psy_trellis = 0;      // the chroma quantiser offset without psy-trellis' share (what remains when psy-trellis gives way to nr)
     int G = 1;                    // --threads G: GOP slots (1: none)
     bool slots_rc = false;        // ... whose pictures the session plans ahead as a --threads 1 session does (X264GPU_GOP_SLOTS_RC=1)

@@ -152,6 +152,7 @@ _SIGS = {
     "x264gpu_qprd_walk": (_i, [_vp] * 6 + [_i] * 4 + [_vp] * 5),
     "x264gpu_encoder_set_qprd_log": (_i, [_vp, _vp]),
     "x264gpu_encoder_set_nr": (_i, [_vp, _vp, _vp]),
+    "x264gpu_encoder_set_nr_any": (_i, [_vp, _vp, _vp]),
     "x264gpu_nr_update": (_i, [_vp, _vp, _vp, _i, _i, _vp]),
     "x264gpu_denoise_blocks": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
     "x264gpu_cabac_level_walk": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
